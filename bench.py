@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the MO-VAE training hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2]
+    python bench.py --gpus N --steps K --warmup W [--config C2] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic batch resident in HBM: forward, loss
 terms, K per-loss backward passes + Jacobian, device-side Gram / weight solve / combine (or plain
 backward for `sum`), [all-reduce of the aggregated gradient when N > 1], optimizer step.
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for how `roofline` is obtained.
+Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times exactly K steps in one block and prints the line.  --full adds
+the legs beyond the headline: the CPU baseline with its ELBO check, the roofline / per-call timings
+(see DESIGN.md "Measurement") and repeated timed blocks (median reported).  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -44,6 +49,7 @@ POOL_BATCHES = 24               # distinct synthetic batches cycled by the timed
 FP32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: bf16 MFMA, dense (--dtype bf16 only)
 HBM_PEAK_GBS = 8000.0
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs writes at most this much array data in all
 
 
 class Args:
@@ -340,6 +346,47 @@ def measure_dominant_kernel(recorded, device, reps=20, live=False):
     return rows, other
 
 
+def step_results(loss_dict, outputs, net):
+    """{name: tensor} of what one step hands its caller: the loss terms, the forward outputs (numbers among them as 0-d
+    tensors; entries that are not numbers, e.g. an absent loss, are left out) and the parameters / floating buffers after
+    the optimizer step, each family flattened into one vector in the model's own order."""
+    res = {f"loss_{k}": v for k, v in loss_dict.items()}
+    for k, v in outputs.items():
+        for i, t in enumerate(v if isinstance(v, (list, tuple)) else [v]):
+            if not isinstance(t, torch.Tensor):
+                if not hasattr(t, "__float__"):
+                    continue
+                t = torch.tensor(float(t), dtype=torch.float64)
+            res[f"out_{k}" + (f"_{i}" if isinstance(v, (list, tuple)) else "")] = t
+    res["params"] = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+    bufs = [b.detach().reshape(-1).float() for b in net.buffers() if b.is_floating_point()]
+    if bufs:
+        res["buffers"] = torch.cat(bufs)
+    return res
+
+
+def dump_outputs(path, results):
+    """Writes `results` as path/<name>.npy: float64 tensors and integer ones (code indices) as float64, everything else as
+    float32.  All arrays together hold at most DUMP_BUDGET_BYTES: the smallest are written whole, and an array larger
+    than its even share of what is left is replaced by a fixed sample of its flattened values (the same seeded, sorted
+    index set from run to run, so two builds compare element for element)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    items = sorted(results.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = DUMP_BUDGET_BYTES
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+        a = t.cpu().numpy()
+        share = left // (len(items) - i) // a.itemsize
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -347,19 +394,37 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=str, default="C2", choices=sorted(CONFIGS))
     ap.add_argument("--agg", type=str, default=None)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps each (median reported)")
-    ap.add_argument("--min-gpu-seconds", type=float, default=6.0, help="keep repeating the timed block for at least this long")
-    ap.add_argument("--elbo-check-steps", type=int, default=20, help="HIP vs oracle loss check inside the cpu_baseline leg (0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline (with the ELBO check) and the roofline / per-call timings, and repeat the timed "
+                         "block (--repeats / --min-gpu-seconds default to 5 / 6.0); off: one timed block of --steps steps")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="--full: length of the CPU baseline (default 10)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed blocks of --steps steps each (median reported; default 1, --full: 5)")
+    ap.add_argument("--min-gpu-seconds", type=float, default=None,
+                    help="keep repeating the timed block for at least this long (default 0, --full: 6.0)")
+    ap.add_argument("--elbo-check-steps", type=int, default=None,
+                    help="--full: HIP vs oracle loss check inside the cpu_baseline leg (default 20, 0 = off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline / per-call timings")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the step as one captured hipGraph (auto = on)")
-    ap.add_argument("--kernel-table", type=str, default=None, help="write the per-launch conv table (JSON) here")
+    ap.add_argument("--kernel-table", type=str, default=None, help="--full: write the per-launch conv table (JSON) here")
     ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
                     help="fp32 = the reference's arithmetic (default, the headline).  bf16 (opt-in, never the default): bf16 operands / "
                          "fp32 accumulate in the 128x128 implicit-GEMM kernels; the line's `dtype` then says bf16")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the loss terms, forward outputs and updated parameters of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        for opt in ("cpu_seconds", "elbo_check_steps", "kernel_table"):
+            if getattr(args, opt) is not None:
+                ap.error(f"--{opt.replace('_', '-')} belongs to a leg that only --full runs")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    defaults = dict(cpu_seconds=10.0, elbo_check_steps=20, repeats=5, min_gpu_seconds=6.0) if args.full else \
+        dict(repeats=1, min_gpu_seconds=0.0)
+    for k, v in defaults.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
 
     cfg = dict(CONFIGS[args.config])
     if args.agg:
@@ -387,14 +452,14 @@ def main():
     # the CPU leg runs FIRST (rank 0, N = 1): the GPU then stays busy from here to the end of the run, which is what a coarse
     # utilisation sampler around the process can see
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, args.cpu_seconds, device=device, check_steps=args.elbo_check_steps)
         torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
     net, opt, agg, a, pool = build_workload(cfg, device, capturable=use_graph)
     if dp is not None:
         dp.attach(net)
     # the roofline block (like the CPU baseline) belongs to the N = 1 line; the scaling runs report throughput only
-    want_roofline = rank == 0 and world == 1 and dp is None and not args.no_roofline
+    want_roofline = args.full and rank == 0 and world == 1 and dp is None and not args.no_roofline
     graphed = GraphedTrainStep(net, opt, agg, a, pool[0], dp=dp, record_calls=want_roofline) if use_graph else None
     if graphed is not None and dp is not None:
         # watchdog: if graph replay + collective misbehaves on this node (observed when several ranks share one
@@ -424,9 +489,9 @@ def main():
             dp.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ld = None
+        res = None
         for i in range(args.steps):
-            ld, _ = step(first + i)
+            res = step(first + i)
         torch.cuda.synchronize()
         if dp is not None:
             dp.barrier()
@@ -435,15 +500,15 @@ def main():
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             dt = float(t.item())
-        return dt, ld
+        return dt, res
 
     # the timed block is repeated (>= --repeats times, and until the GPU has been timed for --min-gpu-seconds): the reported
-    # value is the MEDIAN block, min / max are given beside it
+    # value is the MEDIAN block, min / max are given beside it.  A plain run times one block.
     times = []
-    first, ld = args.warmup, None
+    first = args.warmup
     t_begin = time.perf_counter()
     while True:
-        dt, ld = timed_block(first)
+        dt, (ld, outputs) = timed_block(first)
         first += args.steps
         times.append(dt)
         enough = len(times) >= args.repeats and (time.perf_counter() - t_begin) >= args.min_gpu_seconds
@@ -456,6 +521,8 @@ def main():
     ts = sorted(times)
     elapsed = ts[len(ts) // 2]
     final_loss = float(ld["total_loss"].item())
+    if args.dump_outputs and rank == 0:  # before the roofline leg, whose re-issued launches write the step's buffers again
+        dump_outputs(args.dump_outputs, step_results(ld, outputs, net))
 
     roofline = None
     issued_gflop = issued_gflop_x = None

@@ -39,7 +39,12 @@ def test_kl():
     gm, gl = torch.autograd.grad(v, [mu, lv])
     np.testing.assert_allclose(v.item(), fx["kl.value"], rtol=1e-6)
     np.testing.assert_allclose(gm.numpy(), fx["kl.gmu"], rtol=1e-6, atol=1e-9)
-    np.testing.assert_allclose(gl.numpy(), fx["kl.glv"], rtol=1e-6, atol=1e-9)
+    # d/dlv = (e^lv - 1) / 2B is formed as 0.5/B * e^lv - 0.5/B, which cancels near lv = 0: there its last place is that of the
+    # term 0.5/B * e^lv (7.5e-9 at lv = 0.04, B = 5), and exp may return either neighbour of a value near a rounding midpoint
+    # (MKL's AVX-512 and AVX2 paths do, at lv = 0.0413).  So each element may be one place of that term off the reference's.
+    term = (0.5 / fx["kl.mu"].shape[0] * np.exp(fx["kl.log_var"].astype(np.float64))).astype(np.float32)
+    err = np.abs(gl.numpy() - fx["kl.glv"]) - (1e-6 * np.abs(fx["kl.glv"]) + 1e-9 + np.spacing(term))
+    assert err.max() <= 0, f"d kl / d log_var off by more than one place of the e^lv term: {np.argwhere(err > 0).tolist()}"
 
 
 def test_activation_table():
@@ -196,9 +201,12 @@ def test_forward_losses_grads_and_adam_step(tag):
     for n, g in grads.items():
         want = fx["gsum." + n]
         np.testing.assert_allclose(g.numpy(), want, rtol=1e-3, atol=2e-6 * max(1.0, np.abs(want).max()), err_msg=n)
-    # Adam step + BN running statistics
+    # Adam step + BN running statistics.  The step is taken on the reference's own gradients (the oracle's are held to them
+    # just above): Adam's first step lr * g / (|g| + eps) magnifies a rounding-level difference in a gradient near eps (1e-8)
+    # some 3e4-fold, so the oracle's gradients would carry the BLAS rounding of the host's CPU (MKL's AVX-512 and AVX2 paths
+    # round differently) into the small-gradient weights
     for n, p in tr.params.items():
-        p.grad = grads[n].clone()
+        p.grad = T(fx["gsum." + n]).clone()
     tr.opt.step()
     for k in tr.sd:
         want = fx["sd1." + k]

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in "$@"; do
-  python3 $R/bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline --min-gpu-seconds 2 --kernel-table $OUT/${c}_call_table.json > $OUT/${c}_bench.json 2> $OUT/${c}_bench.err || { tail -5 $OUT/${c}_bench.err; exit 1; }
+  python3 $R/bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline --min-gpu-seconds 2 --kernel-table $OUT/${c}_call_table.json > $OUT/${c}_bench.json 2> $OUT/${c}_bench.err || { tail -5 $OUT/${c}_bench.err; exit 1; }
   python3 - <<PY
 import json
 d=json.load(open("$OUT/${c}_bench.json"))

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in "$@"; do
   case $c in C1|C2) CPU="--cpu-seconds 10 --elbo-check-steps 20";; *) CPU="--cpu-seconds 8 --elbo-check-steps 2";; esac
-  python3 $R/bench.py --config $c --steps 20 --warmup 5 $CPU --min-gpu-seconds 3 --kernel-table $OUT/${c}_call_table.json > $OUT/${c}_bench.json 2> $OUT/${c}_bench.err || { tail -5 $OUT/${c}_bench.err; exit 1; }
+  python3 $R/bench.py --full --config $c --steps 20 --warmup 5 $CPU --min-gpu-seconds 3 --kernel-table $OUT/${c}_call_table.json > $OUT/${c}_bench.json 2> $OUT/${c}_bench.err || { tail -5 $OUT/${c}_bench.err; exit 1; }
   python3 - <<PY
 import json
 d=json.load(open("$OUT/${c}_bench.json"))
@@ -32,6 +32,6 @@ PY
 done
 # the opt-in bf16 leg (never the headline): one bench line per config named in BF16_CFGS, e.g. BF16_CFGS="C3 C5"
 for c in $BF16_CFGS; do
-  python3 $R/bench.py --config $c --dtype bf16 --steps 20 --warmup 5 --cpu-seconds 8 --elbo-check-steps 2 --min-gpu-seconds 3 > $OUT/${c}_bf16_bench.json 2> $OUT/${c}_bf16_bench.err || { tail -5 $OUT/${c}_bf16_bench.err; exit 1; }
+  python3 $R/bench.py --full --config $c --dtype bf16 --steps 20 --warmup 5 --cpu-seconds 8 --elbo-check-steps 2 --min-gpu-seconds 3 > $OUT/${c}_bf16_bench.json 2> $OUT/${c}_bf16_bench.err || { tail -5 $OUT/${c}_bf16_bench.err; exit 1; }
   python3 -c "import json; d=json.load(open('$OUT/${c}_bf16_bench.json')); print('$c bf16 ms/step', round(d['ms_per_step'],4), d['dtype'], (d['roofline'] or {}).get('kernel'), (d['roofline'] or {}).get('frac'))"
 done
