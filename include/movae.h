@@ -507,6 +507,23 @@ int movae_cross_entropy_fwd(const float* logits, const int64_t* target, float* l
 int movae_cross_entropy_bwd(const float* logits, const int64_t* target, const float* lse, const float* gscale_dev, float* dlogits,
                             size_t rows, int k, movae_stream_t stream);
 
+/* ---- reconstruction metrics of the final evaluation (main.py:335-373 over utils/metrics.py ssim :14-80, ssnr :108-154,
+ * psnr :157-203) ----------------------------------------------------------------------------------------------------------
+ * One chunk of n (real, recon) image pairs of c x h x w, each operand given by its element strides (n, c, h, w) -- e.g. NCHW
+ * images and the decoder's NHWC buffer seen as NCHW, with no copy.  Like the reference, each operand is mapped to
+ * clamp((x + 1) / 2, 0, 1) if its minimum over the chunk is negative, else clamp(x, 0, 1); that decision is made on the device.
+ * SSIM uses the separable form of the reference's Gaussian window (sigma 1.5, window_size odd in 3..15) with zero padding.
+ * out (device float[3 + 3 n]): [0] ssim (mean of the SSIM map over n c h w), [1] psnr (mean over the images of
+ * 20 log10(max_val) - 10 log10(max(mse, 1e-10))), [2] ssnr (mean over the images of 10 log10(max(var(real), 1e-10) /
+ * max(mse, 1e-10)), unbiased variance), then per image: [3 + i] SSIM, [3 + n + i] MSE, [3 + 2 n + i] SSNR in dB.
+ * ws >= movae_recon_metrics_ws_bytes(n, c, h, w) bytes (the 4096-byte header included; this call uses only the scratch behind
+ * it); three launches, fixed summation order (fp64 partials, no float atomics): bit-identical results from run to run. */
+size_t movae_recon_metrics_ws_bytes(int n, int c, int h, int w);
+int movae_recon_metrics(const float* real, long long rs_n, long long rs_c, long long rs_h, long long rs_w,
+                        const float* recon, long long ps_n, long long ps_c, long long ps_h, long long ps_w,
+                        int n, int c, int h, int w, int window_size, float max_val, float* out, void* ws, size_t ws_bytes,
+                        movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,9 @@ SIGNATURES = {
     "movae_cross_entropy_ws_bytes": ([_z], _z),
     "movae_cross_entropy_fwd": ([_p, _p, _p, _p, _z, _i, _p, _z, _p], _i),
     "movae_cross_entropy_bwd": ([_p, _p, _p, _p, _p, _z, _i, _p], _i),
+    "movae_recon_metrics_ws_bytes": ([_i, _i, _i, _i], _z),
+    "movae_recon_metrics": ([_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, C.c_longlong, C.c_longlong,
+                             C.c_longlong, _i, _i, _i, _i, _i, _f, _p, _p, _z, _p], _i),
     "movae_bench_main_kernel_only": ([_i], _i),
     "movae_bench_last_kernel": ([], C.c_char_p),
     "movae_reduce_defer": ([_i], _i),

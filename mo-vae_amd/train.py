@@ -21,6 +21,7 @@ from . import aggregation
 from . import autojac
 from . import ops
 from .aggregation import COMFORT, MGDA
+from .metrics import ReconMetricAccumulator, build_hv_indicator
 from .models import get_network
 from .optim import FusedAdam, FusedAdamW, clip_grad_norm_
 from .parallel import DataParallelGrads
@@ -433,12 +434,9 @@ def train_epoch(net, train_loader, optimizer, aggregator, step, device, args, dp
 
 
 @torch.no_grad()
-def evaluate(net, loader, device, args):
-    """main.py:238-332 -- losses and codebook usage over a whole loader.  Same meters as the reference (one update per
-    batch, un-weighted, `total_loss` included; codebook usage = distinct codes seen over ALL batches, the two VQ-VAE-2
-    codebooks averaged), but nothing leaves the device inside the loop: the reference reads every loss with `.item()`
-    and concatenates every batch's indices on the host; here each batch appends one stacked loss row and ORs its codes
-    into a K-entry device mask, and the host reads both once at the end."""
+def _eval_loop(net, loader, device, on_batch=None):
+    """The loop of `evaluate`: meters of the losses and codebook usage, nothing read by the host before the end.
+    on_batch(images, outputs) sees every batch's inputs and outputs on the device (the recon-metric collection)."""
     net.eval()
     meters = {k: AverageMeter() for k in net.objectives.keys()}
     meters["total_loss"] = AverageMeter()
@@ -462,6 +460,8 @@ def evaluate(net, loader, device, args):
         elif out.get("encoding_inds_top") is not None and out.get("encoding_inds_bottom") is not None and hasattr(net, "vq_top"):
             mark("encoding_inds_top", out["encoding_inds_top"], net.vq_top.K)
             mark("encoding_inds_bottom", out["encoding_inds_bottom"], net.vq_top.K)  # main.py:296 takes K from vq_top for both
+        if on_batch is not None:
+            on_batch(images, out)
     if rows:
         for vals in torch.stack(rows).cpu().tolist():
             for k, v in zip(keys, vals):
@@ -471,6 +471,45 @@ def evaluate(net, loader, device, args):
         usage.update(sum(float(m.sum().item()) / m.numel() * 100.0 for m in used.values()) / len(used))
         meters["codebook_usage_percentage"] = usage
     return meters
+
+
+@torch.no_grad()
+def evaluate(net, loader, device, args):
+    """main.py:238-332 -- losses and codebook usage over a whole loader.  Same meters as the reference (one update per
+    batch, un-weighted, `total_loss` included; codebook usage = distinct codes seen over ALL batches, the two VQ-VAE-2
+    codebooks averaged), but nothing leaves the device inside the loop: the reference reads every loss with `.item()`
+    and concatenates every batch's indices on the host; here each batch appends one stacked loss row and ORs its codes
+    into a K-entry device mask, and the host reads both once at the end."""
+    return _eval_loop(net, loader, device)
+
+
+@torch.no_grad()
+def evaluate_with_recon_metrics(net, loader, device, args):
+    """main.py:376-463: `evaluate`'s meters and the reconstruction metrics from ONE pass over the loader -> (meters,
+    {'rfid', 'psnr', 'ssim', 'lpips'}).  The first `--max_fid_samples` (real, recon) pairs are scored in the reference's
+    128-sample chunks on the device (metrics.ReconMetricAccumulator) instead of being copied to the host; rFID and LPIPS
+    need pretrained networks and are NaN."""
+    acc = ReconMetricAccumulator(device, getattr(args, "max_fid_samples", 5000))
+    meters = _eval_loop(net, loader, device, on_batch=lambda images, out: acc.add(images, out.get("recons")))
+    return meters, acc.result()
+
+
+@torch.no_grad()
+def evaluate_recon_metrics(net, loader, device, args):
+    """main.py:466-510: the reconstruction metrics alone; the loop stops once `--max_fid_samples` pairs are taken."""
+    net.eval()
+    acc = ReconMetricAccumulator(device, getattr(args, "max_fid_samples", 5000))
+    for images, _ in loader:
+        if acc.full:
+            break
+        images = images.to(device)
+        acc.add(images, net(images).get("recons"))
+    return acc.result()
+
+
+#: the final evaluation of the last train.main run on rank 0 (main.py:1457-1470): {"losses": {key: avg}, "recon": {rfid, psnr,
+#: ssim, lpips}}; empty when it did not run (--max_fid_samples 0, other ranks)
+LAST_FINAL = {}
 
 
 # ---- data ----------------------------------------------------------------------------------------
@@ -731,6 +770,9 @@ def main(args):
         net.print_model_summary()
     step, history, best = 0, [], float("inf")
     eval_rec = {}
+    objective_keys = list(net.objectives.keys())
+    hv_indicator = build_hv_indicator(objective_keys, args)  # main.py:1283
+    LAST_FINAL.clear()
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -743,15 +785,25 @@ def main(args):
         dt = time.time() - t0
         rec = {k: m.avg for k, m in meters.items()}
         history.append(rec)
+        # main.py:1301-1325: HV of the epoch's average objective vector (nan with fewer than two objectives)
+        train_hv = hv_indicator([rec[k] for k in objective_keys]) if hv_indicator is not None else float("nan")
+        epoch_log = {"train/hv": train_hv}
         if rank0:
             n_img = (step - step0) * per_rank_bs * (1 if dp is None else dp.world_size)
-            print(f"epoch {epoch}: " + ", ".join(f"{k}: {v:.6e}" for k, v in rec.items()) + f"  [{n_img / dt:.0f} img/s]")
+            print(f"epoch {epoch}: " + ", ".join(f"{k}: {v:.6e}" for k, v in rec.items()) + f", HV: {train_hv:.2e}"
+                  + f"  [{n_img / dt:.0f} img/s]")
         if args.eval_freq and epoch % args.eval_freq == 0:
             ev = evaluate(net, test_loader, device, args)
             eval_rec = {k: m.avg for k, m in ev.items()}
             best = min(best, ev["total_loss"].avg)
+            eval_hv = hv_indicator([eval_rec[k] for k in objective_keys]) if hv_indicator is not None else None  # main.py:1372-1388
+            if eval_hv is not None:
+                epoch_log["eval/hv"] = eval_hv
             if rank0:
-                print(f"  eval: " + ", ".join(f"{k}: {m.avg:.6e}" for k, m in ev.items()))
+                print(f"  eval: " + ", ".join(f"{k}: {m.avg:.6e}" for k, m in ev.items())
+                      + (f", HV: {eval_hv:.2e}" if eval_hv is not None else ""))
+        if log is not None and rank0:
+            log(epoch_log, step)
         if scheduler is not None:
             scheduler.step()
         if args.max_steps is not None and step >= args.max_steps:
@@ -773,6 +825,15 @@ def main(args):
         if dp is not None:
             prior_loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, **loader_kw)
         _prior.train_pixelcnn_prior(net, prior_loader, device, args, save_root)
+    if rank0 and getattr(args, "max_fid_samples", 0) > 0:  # main.py:1457-1470, after the prior stage like the reference
+        final_meters, recon = evaluate_with_recon_metrics(net, test_loader, device, args)
+        losses = {k: m.avg for k, m in final_meters.items()}
+        print("final: " + ", ".join(f"eval_{k}: {v:.6e}" for k, v in losses.items())
+              + ", " + ", ".join(f"{k}: {recon[k]:.6f}" for k in ("rfid", "psnr", "ssim", "lpips")))
+        if log is not None:
+            log({**{f"final/eval_{k}": v for k, v in losses.items()}, **{f"final/{k}": recon[k] for k in ("rfid", "psnr", "ssim", "lpips")}},
+                step)
+        LAST_FINAL.update(losses=losses, recon=recon)
     if dp is not None:
         dp.shutdown()
     return history
