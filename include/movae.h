@@ -156,6 +156,10 @@ int movae_reparam_fwd(const float* mu, const float* log_var, const float* eps, f
  * where torch.randn_like + movae_reparam_fwd are four).  One such call at a time per process (the arrival count is a device global). */
 int movae_reparam_rng_fwd(const float* mu, const float* log_var, float* eps, float* z, size_t n, unsigned long long* state, int advance,
                           movae_stream_t stream);
+/* movae_reparam_rng_fwd that also fills prior[0 .. n_prior) with N(0, 1) draws from the same generator state and draw number (the
+ * counter blocks that follow eps's): the cycle branch's z_prior of the cycle / recursive-cyclic VAEs, one launch and one advance for both. */
+int movae_reparam_prior_rng_fwd(const float* mu, const float* log_var, float* eps, float* z, size_t n, float* prior, size_t n_prior,
+                                unsigned long long* state, int advance, movae_stream_t stream);
 int movae_reparam_bwd(const float* dz, const float* log_var, const float* eps, float* dmu, float* dlog_var, size_t n, movae_stream_t stream);
 
 /* ---- losses -------------------------------------------------------------------------------------
@@ -190,6 +194,21 @@ int movae_combine_losses_bwd(int nterms, int nout, const float* const* g, const 
 int movae_vae_losses_fwd(const float* recons, const float* inputs, size_t n, int kind, float rec_scale,
                          const float* mu, const float* log_var, int b, int d, float kl_scale, float* out,
                          void* ws, size_t ws_bytes, movae_stream_t stream);
+/* loss_function of the recursive-KL / cycle / recursive-cyclic VAEs (models/recursive_kl_vae.py, cycle_vae.py,
+ * recursive_cyclic_vae.py) in two launches.  out = [w_rec * recon, (anneal * w_kl * kl(mu_hat, log_var_hat)),
+ * (w_cyc * mean_b sum_d (z_prior - mu_gen)^2), total]: a term is present when its operands are (mu_hat / log_var_hat, z_prior / mu_gen
+ * nullable in pairs).  anneal: 1 when !training; else anneal_host, or with iter_dev min(++iter_dev / anneal_steps, 1) on the device.
+ * anneal_out (nullable) keeps the factor for the backward.  ws >= movae_reduce_ws_bytes(n) + 2 * movae_reduce_ws_bytes(b * d).
+ * The backward writes the cotangents of recons / mu_hat / log_var_hat / mu_gen (each output nullable) for the present cotangents
+ * g_* of the outputs (device scalars, nullable; g_tot reaches every term). */
+int movae_recursive_losses_fwd(const float* recons, const float* inputs, size_t n, int kind, const float* mu_hat, const float* log_var_hat,
+                               const float* z_prior, const float* mu_gen, int b, int d, float w_rec, float w_kl, float w_cyc,
+                               float* iter_dev, float anneal_host, float anneal_steps, int training, float* out, float* anneal_out,
+                               void* ws, size_t ws_bytes, movae_stream_t stream);
+int movae_recursive_losses_bwd(const float* recons, const float* inputs, size_t n, int kind, const float* mu_hat, const float* log_var_hat,
+                               const float* z_prior, const float* mu_gen, int b, int d, float w_rec, float w_kl, float w_cyc,
+                               const float* anneal_dev, const float* g_rec, const float* g_kl, const float* g_cyc, const float* g_tot,
+                               float* drecons, float* dmu_hat, float* dlog_var_hat, float* dmu_gen, movae_stream_t stream);
 int movae_kl_bwd(const float* mu, const float* log_var, const float* gscale_dev, float* dmu, float* dlog_var,
                  int b, int d, float scale, movae_stream_t stream);
 /* Beta-TC decomposition: models/betatc_vae.py:262-296.  out[0..2] = mi, tc, kld (unweighted means).

@@ -67,6 +67,7 @@ SIGNATURES = {
     "movae_reparam_fwd": ([_p, _p, _p, _p, _z, _p], _i),
     "movae_reparam_rng_fwd": ([_p, _p, _p, _p, _z, _p, _i, _p], _i),
     "movae_reparam_bwd": ([_p, _p, _p, _p, _p, _z, _p], _i),
+    "movae_reparam_prior_rng_fwd": ([_p, _p, _p, _p, _z, _p, _z, _p, _i, _p], _i),
     "movae_reduce_ws_bytes": ([_z], _z),
     "movae_recon_loss_fwd": ([_p, _p, _p, _z, _i, _f, _p, _z, _p], _i),
     "movae_recon_loss_bwd": ([_p, _p, _p, _p, _z, _i, _f, _p], _i),
@@ -76,6 +77,8 @@ SIGNATURES = {
     "movae_combine_losses_bwd": ([_i, _i, _p, _p, _p, _i, _p, _p], _i),
     "movae_vae_losses_fwd": ([_p, _p, _z, _i, _f, _p, _p, _i, _i, _f, _p, _p, _z, _p], _i),
     "movae_kl_bwd": ([_p, _p, _p, _p, _p, _i, _i, _f, _p], _i),
+    "movae_recursive_losses_fwd": ([_p, _p, _z, _i, _p, _p, _p, _p, _i, _i, _f, _f, _f, _p, _f, _f, _i, _p, _p, _p, _z, _p], _i),
+    "movae_recursive_losses_bwd": ([_p, _p, _z, _i, _p, _p, _p, _p, _i, _i, _f, _f, _f] + [_p] * 9 + [_p], _i),
     "movae_tc_decomp_fwd": ([_p] * 7 + [_i, _i, _p, _z, _p], _i),
     "movae_tc_decomp_bwd": ([_p] * 10 + [_i, _i, _p], _i),
     "movae_edge_weights": ([_p, _p, _p, _i, _i, _i, _i, _p, _z, _p], _i),
@@ -219,7 +222,8 @@ DEFER_PASS = frozenset(
                                                        "dgrad_wgrad_grouped_f")] +
     ["movae_bn_bwd_finalize", "movae_bn_bwd_apply", "movae_bn_bwd_finalize_apply", "movae_bn_act_bwd", "movae_bn_act_bwd_grouped",
      "movae_act_bwd", "movae_act_bwd_bias_grouped", "movae_colsum", "movae_add", "movae_axpby", "movae_copy_channels", "movae_mul",
-     "movae_nchw_to_nhwc", "movae_nhwc_to_nchw", "movae_reparam_bwd", "movae_kl_bwd", "movae_recon_loss_bwd", "movae_recon_loss_bwd_act", "movae_tc_decomp_bwd",
+     "movae_nchw_to_nhwc", "movae_nhwc_to_nchw", "movae_reparam_bwd", "movae_kl_bwd", "movae_recon_loss_bwd", "movae_recon_loss_bwd_act", "movae_recursive_losses_bwd",
+     "movae_tc_decomp_bwd",
      "movae_combine_losses_bwd", "movae_vq_bwd", "movae_linear_pair_bwd", "movae_edge_weighted_mse_bwd", "movae_edge_match_bwd",
      "movae_gated_residual_bwd"])
 _defer_arena = [0]

@@ -294,6 +294,9 @@ def _batched_pullback(features, feat_grads, rows, jb):
                 args = [got.get(i) for i in range(n_in)]
                 cls = getattr(fn, "_forward_cls", None)
                 if cls is not None:  # a torch.autograd.Function node (ops.py): backward returns one value per forward ARGUMENT
+                    # (one cotangent slot per forward OUTPUT: outputs after the last one reached -- LinearPair's log_var of the
+                    # cycle branch -- arrive as None)
+                    args += [None] * (len(getattr(fn, "_input_metadata", ())) - len(args))
                     if hasattr(cls, "backward_batched"):
                         outs = cls.backward_batched(fn, G, *args)
                     else:
@@ -488,5 +491,50 @@ def backward(tensors, aggregator, inputs=None, retain_graph=False, parallel_chun
     for i, t in enumerate(tensors):
         js = torch.autograd.grad(t, inputs, retain_graph=True, allow_unused=True)
         jb.write_row(i, js)
+    ops.join_wgrad()
+    _aggregate_into_grads(jb, aggregator)
+
+
+#: MOVAE_BATCHED_FULL_JACOBIAN=1: backward_through pulls the K rows back in one traversal; default: one autograd pass per loss, which
+#: measured faster for rc_vae at the C2 shape
+BATCHED_FULL_JACOBIAN = os.environ.get("MOVAE_BATCHED_FULL_JACOBIAN", "0") == "1"
+
+
+def backward_through(tensors, aggregator, inputs=None):
+    """torchjd's backward(tensors, aggregator) -- the Jacobian of every loss w.r.t. ALL parameters it reaches, aggregated into .grad
+    -- for losses that are the outputs of ONE op exposing `input_cotangents` (ops.RecursiveLosses, the loss kernel of the multi-pass
+    VAEs).  Batched form (BATCHED_FULL_JACOBIAN and BATCHED_VJP): the op's backward gives each loss's cotangents of the op's own
+    inputs (recons, mu_hat, log_var_hat, mu_gen -- only the direct edges: the path from recons through the second encoder pass
+    is the walker's), and the K rows are pulled back through the whole network together (_batched_pullback: every node once, on
+    [K, ...] stacked cotangents, BatchNorm statistics per group).  A root may also sit under another root's graph (recons under
+    mu_hat): the walker's dependency count holds the shared node until every path into it has delivered.  A parameter reached
+    several times (the encoder runs three times) gets the sum: its first use writes the Jacobian slice in place, the walker adds
+    the later uses before the leaf's copy; no weight-gradient reduce is parked on this path.  Otherwise, or when the graph is not
+    of that shape, one torch.autograd pass per loss over all parameters (backward()'s arithmetic)."""
+    tensors = list(tensors)
+    if len(tensors) == 0:
+        raise ValueError("`tensors` cannot be empty")
+    if inputs is None:
+        inputs = _leaf_tensors(tensors)
+    inputs = list(inputs)
+    if not inputs:
+        return
+    K = len(tensors)
+    jb = JacobianBuffer(inputs, K, tensors[0].device)
+    node = tensors[0].grad_fn
+    cls = getattr(node, "_forward_cls", None)
+    done = False
+    if (BATCHED_FULL_JACOBIAN and BATCHED_VJP and K > 1 and hasattr(cls, "input_cotangents")
+            and all(t.grad_fn is node for t in tensors)):
+        roots, cots = cls.input_cotangents(node, [t.output_nr for t in tensors])
+        try:
+            _batched_pullback(roots, cots, list(range(K)), jb)
+            done = True
+        except NotImplementedError:
+            jb.buf.zero_()  # a node the walker cannot align: the sequential form below rewrites every row
+    if not done:
+        for i, t in enumerate(tensors):
+            js = torch.autograd.grad(t, inputs, retain_graph=True, allow_unused=True)
+            jb.write_row(i, js)
     ops.join_wgrad()
     _aggregate_into_grads(jb, aggregator)

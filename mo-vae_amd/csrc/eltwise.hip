@@ -287,29 +287,44 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
 
 __device__ __forceinline__ float unit_open(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.f / 16777216.f); }  // (0, 1), 24 bits
 
+// four standard normals of counter block (quad q, draw number): the Philox words through Box-Muller
+__device__ __forceinline__ void normal4(long q, unsigned long long draw, unsigned long long seed, float e[4]) {
+    unsigned w[4];
+    philox4x32_10((unsigned)q, (unsigned)((unsigned long long)q >> 32), (unsigned)draw, (unsigned)(draw >> 32), (unsigned)seed,
+                  (unsigned)(seed >> 32), w);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float r = sqrtf(-2.f * logf(unit_open(w[2 * h]))), t = 6.28318530717958647692f * unit_open(w[2 * h + 1]);
+        float sn, cs;
+        sincosf(t, &sn, &cs);
+        e[2 * h] = r * cs, e[2 * h + 1] = r * sn;
+    }
+}
+
+// quads [0, ceil(n / 4)) draw eps (and z); with `prior`, the quads that follow draw prior[0 .. n_prior) -- the cycle branch's
+// z_prior of the recursive-cyclic VAEs -- from the same draw number: one launch and one counter advance for both
 __global__ __launch_bounds__(256) void reparam_rng_fwd_k(const float* __restrict__ mu, const float* __restrict__ lv, float* __restrict__ eps,
-                                                         float* __restrict__ z, long n, unsigned long long* __restrict__ state,
-                                                         int advance) {
+                                                         float* __restrict__ z, long n, float* __restrict__ prior, long n_prior,
+                                                         unsigned long long* __restrict__ state, int advance) {
     const unsigned long long seed = state[0], draw = state[1];
-    const long nq = (n + 3) / 4, stride = (long)gridDim.x * blockDim.x;
-    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride) {
-        unsigned w[4];
-        philox4x32_10((unsigned)q, (unsigned)((unsigned long long)q >> 32), (unsigned)draw, (unsigned)(draw >> 32), (unsigned)seed,
-                      (unsigned)(seed >> 32), w);
+    const long nq = (n + 3) / 4, nq_all = nq + (prior ? (n_prior + 3) / 4 : 0), stride = (long)gridDim.x * blockDim.x;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq_all; q += stride) {
         float e[4];
+        normal4(q, draw, seed, e);
+        if (q < nq) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float r = sqrtf(-2.f * logf(unit_open(w[2 * h]))), t = 6.28318530717958647692f * unit_open(w[2 * h + 1]);
-            float sn, cs;
-            sincosf(t, &sn, &cs);
-            e[2 * h] = r * cs, e[2 * h + 1] = r * sn;
-        }
+            for (int j = 0; j < 4; ++j) {
+                const long i = q * 4 + j;
+                if (i < n) {
+                    eps[i] = e[j];
+                    z[i] = mu[i] + e[j] * expf(0.5f * lv[i]);
+                }
+            }
+        } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long i = q * 4 + j;
-            if (i < n) {
-                eps[i] = e[j];
-                z[i] = mu[i] + e[j] * expf(0.5f * lv[i]);
+            for (int j = 0; j < 4; ++j) {
+                const long i = (q - nq) * 4 + j;
+                if (i < n_prior) prior[i] = e[j];
             }
         }
     }
@@ -491,9 +506,18 @@ int movae_reparam_fwd(const float* mu, const float* log_var, const float* eps, f
 int movae_reparam_rng_fwd(const float* mu, const float* log_var, float* eps, float* z, size_t n, unsigned long long* state, int advance,
                           movae_stream_t stream) {
     MOVAE_CHECK_ARG(mu && log_var && eps && z && state && n > 0, "movae_reparam_rng_fwd: bad argument");
-    hipLaunchKernelGGL(reparam_rng_fwd_k, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mu, log_var, eps, z, (long)n, state,
-                       advance);
+    hipLaunchKernelGGL(reparam_rng_fwd_k, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mu, log_var, eps, z, (long)n,
+                       (float*)nullptr, 0L, state, advance);
     MOVAE_CHECK_LAUNCH("reparam_rng_fwd");
+    return MOVAE_OK;
+}
+
+int movae_reparam_prior_rng_fwd(const float* mu, const float* log_var, float* eps, float* z, size_t n, float* prior, size_t n_prior,
+                                unsigned long long* state, int advance, movae_stream_t stream) {
+    MOVAE_CHECK_ARG(mu && log_var && eps && z && prior && state && n > 0 && n_prior > 0, "movae_reparam_prior_rng_fwd: bad argument");
+    hipLaunchKernelGGL(reparam_rng_fwd_k, dim3(grid_for((n + 3) / 4 + (n_prior + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mu, log_var,
+                       eps, z, (long)n, prior, (long)n_prior, state, advance);
+    MOVAE_CHECK_LAUNCH("reparam_prior_rng_fwd");
     return MOVAE_OK;
 }
 

@@ -355,6 +355,107 @@ inline int grid_for(long total) {
     return (int)(gq > 4096 ? 4096 : (gq < 1 ? 1 : gq));
 }
 
+
+// ---- the recursive-KL / cycle / recursive-cyclic VAEs (models/recursive_vaes.py) --------------------------------------------------
+// Partial sums of the three terms in one launch: blocks [0, nb1) the reconstruction objective over n elements, [nb1, nb1 + nb2) the KL
+// sum of (mu_hat, lv_hat), [nb1 + nb2, nb1 + nb2 + nb3) the cycle sum of squares (z_prior - mu_gen)^2, the last two over nk elements.
+__global__ __launch_bounds__(256) void rvae_partial(const float* __restrict__ r, const float* __restrict__ x, long n, int kind,
+                                                    const float* __restrict__ mh, const float* __restrict__ lh,
+                                                    const float* __restrict__ zp, const float* __restrict__ mg, long nk, int nb1,
+                                                    int nb2, int nb3, double* __restrict__ part) {
+    __shared__ double sh[4];
+    double s = 0.0;
+    const int blk = (int)blockIdx.x;
+    if (blk < nb1) {
+        const long stride = (long)nb1 * 256;
+        for (long i = (long)blk * 256 + threadIdx.x; i < n; i += stride) s += recon_term(r[i], x[i], kind);
+    } else if (blk < nb1 + nb2) {
+        const long stride = (long)nb2 * 256;
+        for (long i = (long)(blk - nb1) * 256 + threadIdx.x; i < nk; i += stride) {
+            const float m = mh[i], l = lh[i];
+            s += 1.f + l - m * m - expf(l);
+        }
+    } else {
+        const long stride = (long)nb3 * 256;
+        for (long i = (long)(blk - nb1 - nb2) * 256 + threadIdx.x; i < nk; i += stride) {
+            const float dd = zp[i] - mg[i];
+            s += dd * dd;
+        }
+    }
+    s = block_sum_256(s, sh);
+    if (threadIdx.x == 0) part[blk] = s;
+}
+
+// The final kernel: the three means, the weights, the annealing factor of the recursive KL and the total, in the reference's order
+// of operations (objective -> fp32 mean, then weight * mean; the recursive KL's (anneal * weight) is a product of host doubles there).
+// out = [reconstruction, (recursive_kld), (cycle), total].  The annealing factor: 1 in eval mode; in training mode `anneal_host`, or,
+// with iter_dev, min(++iter / anneal_steps, 1) from the device counter (advanced here, so a replayed hipGraph anneals).
+__global__ __launch_bounds__(256) void rvae_final(const double* __restrict__ part, int nb1, int nb2, int nb3, long n, int b,
+                                                  float w_rec, float w_kl, float w_cyc, float* __restrict__ iter_dev, float anneal_host,
+                                                  float anneal_steps, int training, float* __restrict__ out, float* __restrict__ anneal_out) {
+    __shared__ double sh[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb1; i += 256) s += part[i];
+    s = block_sum_256(s, sh);
+    const float rec = w_rec * (float)(s / (double)n);
+    double q = 0.0;
+    for (int i = threadIdx.x; i < nb2; i += 256) q += part[nb1 + i];
+    q = block_sum_256(q, sh);
+    double c = 0.0;
+    for (int i = threadIdx.x; i < nb3; i += 256) c += part[nb1 + nb2 + i];
+    c = block_sum_256(c, sh);
+    if (threadIdx.x != 0) return;
+    int k = 0;
+    out[k++] = rec;
+    float total = rec;
+    if (nb2 > 0) {
+        float anneal = 1.f;
+        if (training) {
+            if (iter_dev) {
+                const float it = iter_dev[0] + 1.f;
+                iter_dev[0] = it;
+                anneal = fminf(it / anneal_steps, 1.f);
+            } else {
+                anneal = anneal_host;
+            }
+        }
+        if (anneal_out) anneal_out[0] = anneal;
+        const float kl = (float)(q * (-0.5 / (double)b));
+        const float v = (float)((double)anneal * (double)w_kl) * kl;
+        out[k++] = v;
+        total += v;
+    }
+    if (nb3 > 0) {
+        const float v = w_cyc * (float)(c / (double)b);
+        out[k++] = v;
+        total += v;
+    }
+    out[k] = total;
+}
+
+__device__ __forceinline__ float cot_sum(const float* a, const float* t) { return (a ? a[0] : 0.f) + (t ? t[0] : 0.f); }
+
+// Cotangents of the loss inputs for whichever outputs' cotangents are present (g_* nullable; g_tot feeds every term).
+__global__ void rvae_bwd_k(const float* __restrict__ r, const float* __restrict__ x, long n, int kind, const float* __restrict__ mh,
+                           const float* __restrict__ lh, const float* __restrict__ zp, const float* __restrict__ mg, long nk, int b,
+                           float w_rec, float w_kl, float w_cyc, const float* __restrict__ anneal_dev, const float* __restrict__ g_rec,
+                           const float* __restrict__ g_kl, const float* __restrict__ g_cyc, const float* __restrict__ g_tot,
+                           float* __restrict__ dr, float* __restrict__ dmh, float* __restrict__ dlh, float* __restrict__ dmg) {
+    const float fr = w_rec / (float)n * cot_sum(g_rec, g_tot);
+    const float fk = (anneal_dev ? anneal_dev[0] : 1.f) * w_kl / (float)b * cot_sum(g_kl, g_tot);
+    const float fc = w_cyc / (float)b * cot_sum(g_cyc, g_tot);
+    const long stride = (long)gridDim.x * blockDim.x, m = n > nk ? n : nk;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
+        if (dr && i < n) dr[i] = fr * recon_dterm(r[i], x[i], kind);
+        if (i < nk) {
+            if (dmh) {
+                dmh[i] = fk * mh[i];
+                dlh[i] = fk * 0.5f * (expf(lh[i]) - 1.f);
+            }
+            if (dmg) dmg[i] = fc * (2.f * (mg[i] - zp[i]));
+        }
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -531,6 +632,46 @@ int movae_combine_losses_bwd(int nterms, int nout, const float* const* g, const 
     for (int i = 0; i < nout * nterms; ++i) cc.c[i] = coef[i];
     hipLaunchKernelGGL(combine_losses_bwd_k, dim3(1), dim3(64), 0, (hipStream_t)stream, gp, cc, nterms, nout, anneal_dev, anneal_row, gterms);
     MOVAE_CHECK_LAUNCH("combine_losses_bwd");
+    return MOVAE_OK;
+}
+
+// models/recursive_vaes.py loss_function in two launches (partials, final); mu_hat / log_var_hat and z_prior / mu_gen are each
+// nullable (RecursiveKLVAE has no cycle term, CycleVAE no recursive KL).  ws >= movae_reduce_ws_bytes(n) + 2 * movae_reduce_ws_bytes(b * d).
+int movae_recursive_losses_fwd(const float* recons, const float* inputs, size_t n, int kind, const float* mu_hat, const float* log_var_hat,
+                               const float* z_prior, const float* mu_gen, int b, int d, float w_rec, float w_kl, float w_cyc,
+                               float* iter_dev, float anneal_host, float anneal_steps, int training, float* out, float* anneal_out,
+                               void* ws, size_t ws_bytes, movae_stream_t stream) {
+    MOVAE_WS_SCRATCH(ws, ws_bytes);
+    MOVAE_CHECK_ARG(recons && inputs && out && n > 0 && b > 0 && d > 0, "movae_recursive_losses_fwd: bad argument");
+    MOVAE_CHECK_ARG(kind >= 0 && kind <= 3, "movae_recursive_losses_fwd: unknown objective %d", kind);
+    MOVAE_CHECK_ARG((mu_hat == nullptr) == (log_var_hat == nullptr) && (z_prior == nullptr) == (mu_gen == nullptr),
+                    "movae_recursive_losses_fwd: a term needs both of its operands");
+    const size_t nk = (size_t)b * d;
+    MOVAE_CHECK_ARG(ws && ws_bytes >= movae_reduce_ws_bytes(n) + 2 * movae_reduce_ws_bytes(nk), "movae_recursive_losses_fwd: workspace too small");
+    const int nb1 = red_blocks(n), nb2 = mu_hat ? red_blocks(nk) : 0, nb3 = z_prior ? red_blocks(nk) : 0;
+    double* part = static_cast<double*>(ws);
+    hipLaunchKernelGGL(rvae_partial, dim3(nb1 + nb2 + nb3), dim3(256), 0, (hipStream_t)stream, recons, inputs, (long)n, kind, mu_hat,
+                       log_var_hat, z_prior, mu_gen, (long)nk, nb1, nb2, nb3, part);
+    MOVAE_CHECK_LAUNCH("rvae_partial");
+    hipLaunchKernelGGL(rvae_final, dim3(1), dim3(256), 0, (hipStream_t)stream, part, nb1, nb2, nb3, (long)n, b, w_rec, w_kl, w_cyc,
+                       iter_dev, anneal_host, anneal_steps, training, out, anneal_out);
+    MOVAE_CHECK_LAUNCH("rvae_final");
+    return MOVAE_OK;
+}
+
+int movae_recursive_losses_bwd(const float* recons, const float* inputs, size_t n, int kind, const float* mu_hat, const float* log_var_hat,
+                               const float* z_prior, const float* mu_gen, int b, int d, float w_rec, float w_kl, float w_cyc,
+                               const float* anneal_dev, const float* g_rec, const float* g_kl, const float* g_cyc, const float* g_tot,
+                               float* drecons, float* dmu_hat, float* dlog_var_hat, float* dmu_gen, movae_stream_t stream) {
+    MOVAE_CHECK_ARG(recons && inputs && n > 0 && b > 0 && d > 0, "movae_recursive_losses_bwd: bad argument");
+    MOVAE_CHECK_ARG(kind >= 0 && kind <= 3, "movae_recursive_losses_bwd: unknown objective %d", kind);
+    MOVAE_CHECK_ARG(!dmu_hat || (mu_hat && log_var_hat && dlog_var_hat), "movae_recursive_losses_bwd: recursive KL operands missing");
+    MOVAE_CHECK_ARG(!dmu_gen || (z_prior && mu_gen), "movae_recursive_losses_bwd: cycle operands missing");
+    const long nk = (long)b * d, m = (long)n > nk ? (long)n : nk;
+    hipLaunchKernelGGL(rvae_bwd_k, dim3(grid_for(m)), dim3(256), 0, (hipStream_t)stream, recons, inputs, (long)n, kind, mu_hat, log_var_hat,
+                       z_prior, mu_gen, nk, b, w_rec, w_kl, w_cyc, anneal_dev, g_rec, g_kl, g_cyc, g_tot, drecons, dmu_hat, dlog_var_hat,
+                       dmu_gen);
+    MOVAE_CHECK_LAUNCH("rvae_bwd");
     return MOVAE_OK;
 }
 

@@ -1,16 +1,16 @@
 """Model factory -- drop-in for the reference's models/__init__.py:18-211 for the four hot-path
-architectures (vae, vq_vae, vq_vae2, betatc_vae / btc_vae) and the SURVEY 8f.3 widening gg_vae[_v2|_v3|_v5] / gg_vq_vae[_v1.._v7] / gg_vq_vae2."""
+architectures (vae, vq_vae, vq_vae2, betatc_vae / btc_vae), the SURVEY 8f.3 widening gg_vae[_v2|_v3|_v5] / gg_vq_vae[_v1.._v7] / gg_vq_vae2
+and the multi-objective VAEs recursive_kl_vae / cycle_vae / recursive_cyclic_vae (rc_vae)."""
 from .betatc_vae import BetaTCVAE
 from .gg_vae import GGVAE
 from .gg_vq_vae import GGVQVAE
 from .gg_vq_vae2 import GGVQVAE2
+from .recursive_vaes import CycleVAE, RecursiveCyclicVAE, RecursiveKLVAE
 from .vae import VAE
 from .vq_vae import VQVAE, VectorQuantizer
 from .vq_vae2 import VQVAE2
 
-OUT_OF_SCOPE_ARCHS = {
-    "recursive_kl_vae", "cycle_vae", "recursive_cyclic_vae", "rc_vae", "sphere_encoder", "sphere_encoder_vit",
-}
+OUT_OF_SCOPE_ARCHS = {"sphere_encoder", "sphere_encoder_vit"}
 
 
 def _recons_objective(args):
@@ -90,11 +90,34 @@ def get_network(input_size, num_channels=3, args=None, device=None):
             lambda_weights = [lambda_weights[0], lambda_weights[1], lambda_weights[2], ratio]
         return BetaTCVAE(latent_dim=latent_dim, hidden_dims=hidden_dims, anneal_steps=getattr(args, "anneal_steps", 200),
                          dataset_size=getattr(args, "dataset_size", 50000), lambda_weights=lambda_weights, **common)
+    if arch in ("recursive_kl_vae", "cycle_vae", "recursive_cyclic_vae", "rc_vae"):  # models/__init__.py:57-79
+        # the reference's dictionaries: the None forms fail the VAE base's key check (ValueError), as does every dict form of
+        # recursive_kl_vae / rc_vae (the factory adds recursive_kld_loss); the list forms are what the models accept
+        steps = getattr(args, "recursive_kld_anneal_steps", 25000)
+        kw = dict(latent_dim=latent_dim, hidden_dims=hidden_dims, **common)
+        if arch == "recursive_kl_vae":
+            if lambda_weights is None:
+                lambda_weights = {"reconstruction_loss": 1.0, "recursive_kld_loss": args.batch_size / args.dataset_size}
+            elif isinstance(lambda_weights, dict):
+                lambda_weights = dict(lambda_weights, recursive_kld_loss=args.batch_size / args.dataset_size)
+            return RecursiveKLVAE(lambda_weights=lambda_weights, recursive_kld_anneal_steps=steps, **kw)
+        if arch == "cycle_vae":
+            if lambda_weights is None:
+                lambda_weights = {"reconstruction_loss": 1.0, "cycle_loss": args.batch_size / args.dataset_size}
+            return CycleVAE(lambda_weights=lambda_weights, **kw)
+        ratio = None if isinstance(lambda_weights, list) else args.batch_size / args.dataset_size
+        if lambda_weights is None:
+            lambda_weights = {"reconstruction_loss": 1.0, "recursive_kld_loss": ratio, "cycle_loss": ratio}
+        elif isinstance(lambda_weights, dict):
+            lambda_weights = dict(lambda_weights)
+            lambda_weights.setdefault("recursive_kld_loss", ratio)
+        return RecursiveCyclicVAE(lambda_weights=lambda_weights, recursive_kld_anneal_steps=steps, **kw)
     if arch in OUT_OF_SCOPE_ARCHS:
         raise NotImplementedError(
             f"Network architecture {arch} exists in the reference but is outside this build's hot-path scope "
-            "(vae, vq_vae, vq_vae2, betatc_vae); see DESIGN.md")
+            "(the sphere encoders need pretrained VGG weights or a ViT stack); see DESIGN.md")
     raise ValueError(f"Network architecture {arch} not supported")
 
 
-__all__ = ["VAE", "VQVAE", "VQVAE2", "BetaTCVAE", "GGVAE", "GGVQVAE", "GGVQVAE2", "VectorQuantizer", "get_network"]
+__all__ = ["VAE", "VQVAE", "VQVAE2", "BetaTCVAE", "GGVAE", "GGVQVAE", "GGVQVAE2", "VectorQuantizer", "RecursiveKLVAE", "CycleVAE",
+           "RecursiveCyclicVAE", "get_network"]

@@ -1430,6 +1430,43 @@ def reparameterize_rng(mu, log_var, state):
     return ReparameterizeRNG.apply(mu, log_var, state)
 
 
+class ReparameterizePriorRNG(Function):
+    """ReparameterizeRNG that also draws z_prior ~ N(0, I) [n_prior rows, latent] in the same launch, from the same generator state
+    and draw number (movae_reparam_prior_rng_fwd): the cycle branch's prior sample of the cycle / recursive-cyclic VAEs costs no
+    launch and no counter advance of its own.  z's noise is exactly ReparameterizeRNG's.  Returns (z, z_prior); z_prior is a
+    constant of the tape."""
+
+    @staticmethod
+    def forward(ctx, mu, log_var, state, n_prior):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(mu)
+        mu, log_var = _c(mu), _c(log_var)
+        assert state.dtype == torch.int64 and state.numel() == 2 and state.device == mu.device and mu.dim() == 2
+        z, eps = torch.empty_like(mu), torch.empty_like(mu)
+        prior = torch.empty((int(n_prior), mu.shape[1]), dtype=mu.dtype, device=mu.device)
+        _call("movae_reparam_prior_rng_fwd", mu.data_ptr(), log_var.data_ptr(), eps.data_ptr(), z.data_ptr(), mu.numel(), prior.data_ptr(),
+              prior.numel(), state.data_ptr(), 1, _st(mu))
+        ctx.mark_non_differentiable(prior)
+        ctx.save_for_backward(log_var, eps)
+        ctx.in_ptrs = (mu.data_ptr(), log_var.data_ptr())
+        return z, prior
+
+    @staticmethod
+    def backward(ctx, dz, _dprior):
+        if dz is None:
+            return (None,) * 4
+        log_var, eps = ctx.saved_tensors
+        dz = _c(dz)
+        dmu, dlv = _cot(ctx.in_ptrs[0], dz), _cot(ctx.in_ptrs[1], dz)
+        _call("movae_reparam_bwd", dz.data_ptr(), log_var.data_ptr(), eps.data_ptr(), dmu.data_ptr(), dlv.data_ptr(), dz.numel(), _st(dz))
+        return dmu, dlv, None, None
+
+
+def reparameterize_prior_rng(mu, log_var, state, n_prior):
+    """-> (z, z_prior)"""
+    return ReparameterizePriorRNG.apply(mu, log_var, state, n_prior)
+
+
 # ---------------------------------------------------------------------------------------------
 class ReconLoss(Function):
     """scale * mean(objective(recons, inputs)); both tensors must share one memory order."""
@@ -1633,6 +1670,93 @@ class VAELosses(Function):
 
 def vae_losses(recons, inputs, kind, scale_r, mu, log_var, scale_k, act_link=None):
     return VAELosses.apply(recons, inputs, kind, scale_r, mu, log_var, scale_k, act_link)
+
+
+class RecursiveLosses(Function):
+    """loss_function of the recursive-KL / cycle / recursive-cyclic VAEs (models/recursive_vaes.py) in two launches forward and
+    one backward: w_rec * mean(objective(recons, inputs)); anneal * w_kl * kl(mu_hat, log_var_hat) when mu_hat is given; w_cyc *
+    mean_b sum_d (z_prior - mu_gen)^2 when z_prior is given; and their fp32 sum.  Returns those K + 1 scalars (adjacent in one
+    buffer).  `anneal`: (iter_dev or None, host factor, steps, training) -- with iter_dev the counter is advanced and the factor
+    formed inside the final kernel (graph mode), else the host factor is used; eval mode (training False) uses 1.  The backward
+    serves whichever cotangents arrive and writes only the cotangents they reach."""
+
+    @staticmethod
+    def forward(ctx, recons, inputs, kind, w_rec, mu_hat, log_var_hat, w_kl, anneal, z_prior, mu_gen, w_cyc):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(recons)
+        recons, inputs = _c(recons), _c(inputs)
+        assert recons.shape == inputs.shape, (recons.shape, inputs.shape)
+        has_kl, has_cyc = mu_hat is not None, z_prior is not None
+        lat = mu_hat if has_kl else mu_gen
+        b, d = lat.shape
+        mu_hat, log_var_hat = (_c(mu_hat), _c(log_var_hat)) if has_kl else (None, None)
+        z_prior, mu_gen = (_c(z_prior), _c(mu_gen)) if has_cyc else (None, None)
+        K = 1 + int(has_kl) + int(has_cyc)
+        out = torch.empty(K + 1, dtype=torch.float32, device=recons.device)
+        it_dev, host, steps, training = anneal if anneal is not None else (None, 1.0, 1.0, False)
+        fac = torch.empty(1, dtype=torch.float32, device=out.device) if has_kl else None
+        wsp, wsb = _ws(recons)
+        p = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        _call("movae_recursive_losses_fwd", recons.data_ptr(), inputs.data_ptr(), recons.numel(), L.RECON[kind], p(mu_hat), p(log_var_hat),
+              p(z_prior), p(mu_gen), b, d, float(w_rec), float(w_kl), float(w_cyc), p(it_dev), float(host), float(steps), int(bool(training)),
+              out.data_ptr(), p(fac), wsp, wsb, _st(recons))
+        ctx.kind, ctx.w = kind, (float(w_rec), float(w_kl), float(w_cyc))
+        ctx.has, ctx.fac, ctx.bd = (has_kl, has_cyc), fac, (b, d)
+        ctx.save_for_backward(recons, inputs, mu_hat, log_var_hat, z_prior, mu_gen)
+        return tuple(out[k] for k in range(K + 1))
+
+    @staticmethod
+    def backward(ctx, *g):
+        recons, inputs, mu_hat, log_var_hat, z_prior, mu_gen = ctx.saved_tensors
+        has_kl, has_cyc = ctx.has
+        g = [None if x is None else _c(x) for x in g]
+        g_rec, g_tot = g[0], g[-1]
+        g_kl = g[1] if has_kl else None
+        g_cyc = g[1 + int(has_kl)] if has_cyc else None
+        reach = lambda t: t is not None or g_tot is not None  # noqa: E731
+        dr = dmh = dlh = dmg = None
+        if reach(g_rec) and ctx.needs_input_grad[0]:
+            dr = torch.empty_like(recons)
+        if has_kl and reach(g_kl) and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
+            dmh, dlh = _cot(mu_hat.data_ptr(), mu_hat), _cot(log_var_hat.data_ptr(), mu_hat)
+        if has_cyc and reach(g_cyc) and ctx.needs_input_grad[9]:
+            dmg = _cot(mu_gen.data_ptr(), mu_gen)
+        if dr is None and dmh is None and dmg is None:
+            return (None,) * 11
+        p = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        b, d = ctx.bd
+        _call("movae_recursive_losses_bwd", recons.data_ptr(), inputs.data_ptr(), recons.numel(), L.RECON[ctx.kind], p(mu_hat), p(log_var_hat),
+              p(z_prior), p(mu_gen), b, d, ctx.w[0], ctx.w[1], ctx.w[2], p(ctx.fac), p(g_rec), p(g_kl), p(g_cyc), p(g_tot), p(dr), p(dmh),
+              p(dlh), p(dmg), _st(recons))
+        return dr, None, None, None, dmh, dlh, None, None, None, dmg, None
+
+    #: forward-argument positions of the differentiable inputs: recons, mu_hat, log_var_hat, mu_gen
+    _DIFF_ARGS = (0, 4, 5, 9)
+
+    @staticmethod
+    @torch.no_grad()
+    def input_cotangents(node, outputs):
+        """For the Jacobian pull-back (autojac.backward_through): the op's differentiable input tensors that need a gradient and,
+        per loss output index in `outputs`, its cotangents of those inputs (a unit cotangent on that output alone) -- the direct
+        edges of the loss op only."""
+        saved = node.saved_tensors
+        by_pos = dict(zip(RecursiveLosses._DIFF_ARGS, (saved[0], saved[2], saved[3], saved[5])))
+        live = [p for p in RecursiveLosses._DIFF_ARGS if by_pos[p] is not None and node.needs_input_grad[p]]
+        roots = [by_pos[p] for p in live]
+        n_out = len(node._input_metadata)
+        one = torch.ones((), dtype=torch.float32, device=roots[0].device)
+        cots = []
+        for k in outputs:
+            g = [None] * n_out
+            g[k] = one
+            res = RecursiveLosses.backward(node, *g)
+            cots.append([res[p] for p in live])
+        return roots, cots
+
+
+def recursive_losses(recons, inputs, kind, w_rec, mu_hat=None, log_var_hat=None, w_kl=0.0, anneal=None, z_prior=None, mu_gen=None,
+                     w_cyc=0.0):
+    return RecursiveLosses.apply(recons, inputs, kind, w_rec, mu_hat, log_var_hat, w_kl, anneal, z_prior, mu_gen, w_cyc)
 
 
 class CombineLosses(Function):

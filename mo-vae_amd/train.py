@@ -84,8 +84,11 @@ def forward_backward_begin(net, images, optimizer, aggregator):
     optimizer.zero_grad()
     outputs = net(images)
     loss_dict = net.loss_function(images, args=outputs)
-    # weight gradients leave the backward's critical path (ops.wgrad_side_stream); the block's exit is the one join
-    with ops.wgrad_side_stream(images.device, enabled=L.DEFER_WGRAD_DEFAULT):
+    # weight gradients leave the backward's critical path (ops.wgrad_side_stream); the block's exit is the one join.  Not for a
+    # Jacobian over all parameters (features is None): those models reuse parameters, whose per-use gradients are summed on the
+    # compute stream while the side stream may still be writing them
+    side = L.DEFER_WGRAD_DEFAULT and net.features is not None
+    with ops.wgrad_side_stream(images.device, enabled=side):
         if aggregator is None or aggregator == "sum":
             loss_dict["total_loss"].backward()
             return loss_dict, outputs, None
@@ -94,7 +97,10 @@ def forward_backward_begin(net, images, optimizer, aggregator):
         if isinstance(aggregator, (MGDA, COMFORT)):  # main.py:185
             aggregator.set_losses(_stacked(component_losses))
         if features is None:
-            autojac.backward(component_losses, aggregator=aggregator)
+            if getattr(net, "_jacobian_from_loss_op", False):  # (internal: the K rows can be pulled back from the loss op's inputs)
+                autojac.backward_through(component_losses, aggregator)
+            else:
+                autojac.backward(component_losses, aggregator=aggregator)
             return loss_dict, outputs, None
         pending = autojac.mtl_backward_begin(component_losses, features, aggregator)
     pending.device = images.device
@@ -177,6 +183,9 @@ class GraphedTrainStep:
     def __init__(self, net, optimizer, aggregator, args, example, warmup=3, dp=None, record_calls=False, preserve_state=False):
         if not getattr(net, "graph_safe", False):
             raise NotImplementedError(f"{type(net).__name__}: forward syncs with the host; use the eager train_step")
+        if dp is not None and getattr(net, "features", ()) is None:
+            raise NotImplementedError(f"{type(net).__name__}: the data-parallel graphed step is not supported for models whose Jacobian "
+                                      "spans all parameters (features is None); use the eager step")
         net.prepare_for_graph()
         # preserve_state: the warm-up steps a capture needs are real optimisation steps; with this flag everything they
         # touched (parameters, buffers, optimizer state, RNG streams) is rewound afterwards, so the first replay is step 1
@@ -416,7 +425,8 @@ def train_epoch(net, train_loader, optimizer, aggregator, step, device, args, dp
         if "codebook_usage_percentage" in outputs:
             usage.update(float(outputs["codebook_usage_percentage"]), n=images.size(0))  # LazyScalar: one device read
         for k in meters:
-            meters[k].update(host[k])
+            if k in host:  # (an objective outside the loss dict -- the cycle VAEs' kld_loss -- keeps an un-updated meter: main.py:217-218)
+                meters[k].update(host[k])
         step += 1
         if log is not None:
             rec = {f"train/{k}": m.avg for k, m in meters.items()}
@@ -553,7 +563,6 @@ def get_dataset(name, data_dir="./data", normalize=False, max_items=None):
 # ---- CLI -----------------------------------------------------------------------------------------
 #: main.py:1603-1623,1636-1640 -- options that only the out-of-scope architectures read
 IGNORED_FLAGS = {
-    "--recursive_kld_anneal_steps": dict(type=int, default=25000),
     "--sigma_max_angle_deg": dict(type=float, default=80.0),
     "--sigma_mix_prob": dict(type=float, default=0.0),
     "--sigma_mix_angle_min_deg": dict(type=float, default=None),
@@ -619,6 +628,7 @@ def build_parser():
     p.add_argument("--embedding_dim", type=int, default=None)
     p.add_argument("--num_embeddings", type=int, default=None)
     p.add_argument("--anneal_steps", type=int, default=None)
+    p.add_argument("--recursive_kld_anneal_steps", type=int, default=25000)  # recursive_kl_vae / rc_vae (main.py:1603)
     p.add_argument("--hv_ref", type=str, nargs="*", default=None)
     p.add_argument("--num_vis_samples", type=int, default=4, dest="num_vis_samples")
     p.add_argument("--save_freq", type=int, default=10)
@@ -742,7 +752,9 @@ def main(args):
     if getattr(args, "graph", "off") in ("on", "auto"):
         # PNUPGrad / PCGrad draw torch's CPU generator per call, COMFORT's blend factor is a host scalar that changes per epoch
         host_rng = isinstance(aggregator, (aggregation.PNUPGrad, aggregation.PCGrad, aggregation.COMFORT))
-        if getattr(net, "graph_safe", False) and not host_rng and args.optimizer.lower() in ("adam", "adamw"):
+        # (data parallel with a Jacobian over all parameters -- features is None -- has no graphed form: GraphedTrainStep)
+        dp_full_jacobian = dp is not None and getattr(net, "features", ()) is None
+        if getattr(net, "graph_safe", False) and not host_rng and not dp_full_jacobian and args.optimizer.lower() in ("adam", "adamw"):
             graphed = {"batch": per_rank_bs, "step": None}
         elif args.graph == "on":
             print("--graph on: this model / aggregator / optimizer combination is not replayable; running the eager step")
