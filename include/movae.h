@@ -526,6 +526,28 @@ int movae_cross_entropy_fwd(const float* logits, const int64_t* target, float* l
 int movae_cross_entropy_bwd(const float* logits, const int64_t* target, const float* lse, const float* gscale_dev, float* dlogits,
                             size_t rows, int k, movae_stream_t stream);
 
+/* ---- PixelSNAIL's causal self-attention (models/pixelcnn_prior.py:95-135 CausalAttention2d.forward; :16-22 the mask) ------
+ * Replaces  attn = matmul(q, k^T) / sqrt(hd); masked_fill(tril == 0, -inf); softmax(-1); dropout; out = matmul(attn, v) and the
+ * permute(0, 2, 3, 1).reshape of `out` (:118-131) -- fused, FlashAttention-2 style: no [L, L] matrix is ever stored.
+ *   q, k, v     [B, L, ld] row-major (the NHWC 1x1-conv outputs); head h reads channels h*hd .. h*hd+hd-1 in place
+ *   out, dout   [B, L, heads*hd], element (h, d) at channel d*heads + h: the reference's channel order after its permute
+ *   lse         [B*heads, L] natural log-sum-exp of the scaled, masked scores (written by the forward, read by the backward)
+ *   dq, dk, dv  written in the q / k / v layout (same ld)
+ *   1 <= hd <= 64 (larger is refused), any L >= 1.  Key j is visible from query i iff j <= i.
+ *   p in [0, 1): dropout on the probabilities, P' = P * Z / (1 - p); p == 0 takes the no-dropout kernels.  Z(bh, i, j) is a pure
+ *   function of (seed, draw, bh, i, j) -- Philox4x32-10 -- so the backward regenerates it; movae_causal_attn_dropout_mask writes
+ *   it out (keep [BH][L][L] uint8, 1 = kept) as a test and measurement hook.
+ *   ws >= movae_causal_attn_ws_bytes(B, heads, L) (the 4096-byte header included).  No float atomics: the gradients are
+ *   bit-identical from run to run. */
+int movae_causal_attn_fwd(const float* q, const float* k, const float* v, long ld, float* out, float* lse, int B, int heads, int L,
+                          int hd, float p, unsigned long long seed, unsigned long long draw, movae_stream_t stream);
+size_t movae_causal_attn_ws_bytes(int B, int heads, int L);
+int movae_causal_attn_bwd(const float* q, const float* k, const float* v, long ld, const float* out, const float* dout, const float* lse,
+                          float* dq, float* dk, float* dv, int B, int heads, int L, int hd, float p, unsigned long long seed,
+                          unsigned long long draw, void* ws, size_t ws_bytes, movae_stream_t stream);
+int movae_causal_attn_dropout_mask(uint8_t* keep, int BH, int L, float p, unsigned long long seed, unsigned long long draw,
+                                   movae_stream_t stream);
+
 /* ---- reconstruction metrics of the final evaluation (main.py:335-373 over utils/metrics.py ssim :14-80, ssnr :108-154,
  * psnr :157-203) ----------------------------------------------------------------------------------------------------------
  * One chunk of n (real, recon) image pairs of c x h x w, each operand given by its element strides (n, c, h, w) -- e.g. NCHW

@@ -1,0 +1,438 @@
+// Fused causal multi-head self-attention of PixelSNAIL's CausalAttention2d (reference models/pixelcnn_prior.py:95-135):
+// S = Q K^T / sqrt(hd), causal mask j <= i (diagonal included, :16-22), softmax, dropout on the probabilities, O = P' V.
+// FlashAttention-2 form: the [L, L] matrix never exists.  The forward keeps an online softmax over 16-key tiles and saves the
+// log-sum-exp; the backward recomputes P from it in two passes without float atomics -- one per 16-key tile (dK, dV) and one per
+// 16-query tile (dQ) -- so every gradient is bit-identical from run to run.
+//
+// Layout.  q / k / v are the 1x1-conv outputs [B, L, ld] (NHWC, ld >= heads * hd); head h is channels h*hd .. h*hd+hd-1, read in
+// place.  O and dO are [B, L, heads * hd] in the reference's channel order d*heads + h (out.permute(0, 2, 3, 1).reshape, :130).
+// dq / dk / dv are written in the q / k / v layout (same ld).
+//
+// Math.  fp32 in, fp32 accumulate on v_mfma_f32_16x16x4_f32 (gfx950 has no xf32).  One wave owns a 16-row tile; lane l holds
+// column c = l & 15 and row group g = l >> 4 of every 16x16 fragment (C/D: col = c, row = 4g + reg).  The products are oriented so
+// that the softmax row of a query lives on the 4 lanes {c, c+16, c+32, c+48}:
+//   forward / dQ:  S^T = K Q^T  (lane c: query i0+c; reg r: key j0+4g+r),  O^T += V^T P^T,  dQ^T += K^T dS^T
+//   dK / dV:       S   = Q K^T  (lane c: key j0+c;   reg r: query i0+4g+r), dV^T += dO^T P', dK^T += Q^T dS
+// and the second product of each pair takes the first one's accumulator registers as its B operand directly: its k-step r uses the
+// key (query) set {4g + r}, which is the same set on both operands.  The head dim is padded to HDP in {8, 16, 32, 64} with masked
+// loads; the QK^T k-steps use d = g * HDP/4 + s, so each lane group reads a contiguous run of a row.
+//
+// Dropout.  keep(bh, i, j) = word (j & 3) of Philox4x32-10 at counter (j >> 2, i, bh, draw_lo), key (seed_lo, seed_hi ^ draw_hi),
+// kept iff the word < thr = (1 - p) * 2^32.  A pure function of (seed, draw, bh, i, j): the forward, both backward passes and
+// movae_causal_attn_dropout_mask regenerate the same mask whatever their tiling.
+#include "common.h"
+
+namespace {
+
+constexpr float LOG2E = 1.4426950408889634f;
+constexpr float LN2 = 0.6931471805599453f;
+
+struct AttnArgs {
+    const float* q;
+    const float* k;
+    const float* v;
+    const float* dout;
+    const float* lse;
+    const float* delta;
+    float* out;
+    float* lse_out;
+    float* dq;
+    float* dk;
+    float* dv;
+    long ld;       // row stride of q / k / v / dq / dk / dv (floats)
+    int heads, L, hd, ntiles, nbh;
+    float scale;   // 1 / sqrt(hd)
+    unsigned thr;  // keep iff Philox word < thr (and p > 0)
+    int drop;
+    float inv_keep;
+    unsigned s0, s1, d0;  // Philox key (seed lo, seed hi ^ draw hi) and counter word 3 (draw lo)
+};
+
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+__device__ __forceinline__ void keep4(const AttnArgs& a, int bh, int i, int jq, unsigned w[4]) {
+    philox4x32_10((unsigned)jq, (unsigned)i, (unsigned)bh, a.d0, a.s0, a.s1, w);
+}
+
+__device__ __forceinline__ float ld_guard(const float* base, long row, int d, bool ok, long ld) { return ok ? base[row * ld + d] : 0.f; }
+
+// wave-level tile order: work group t of the grid handles 4 consecutive 16-row tiles of one (b, h); `rev` maps the earliest
+// dispatched groups to the LAST tiles (the longest causal rows) -- forward and dQ -- and the key passes keep t (key tile 0 sees
+// every query)
+__device__ __forceinline__ bool wave_tile(const AttnArgs& a, bool rev, int& tile, int& bh) {
+    const int ngrp = (a.ntiles + 3) >> 2;
+    const int t = blockIdx.x / a.nbh;
+    bh = blockIdx.x - t * a.nbh;
+    const int grp = rev ? ngrp - 1 - t : t;
+    tile = grp * 4 + (threadIdx.x >> 6);
+    return tile < a.ntiles;
+}
+
+template <int HDP, bool DROP>
+__global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
+    constexpr int NS = HDP / 4, NC = HDP >= 16 ? HDP / 16 : 1;
+    int qt, bh;
+    if (!wave_tile(a, true, qt, bh)) return;  // (no block-level barrier below: whole waves may leave)
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd;
+    const long row0 = (long)b * L;
+    const float *qb = a.q + row0 * a.ld + h * hd, *kb = a.k + row0 * a.ld + h * hd, *vb = a.v + row0 * a.ld + h * hd;
+    const int i0 = qt * 16, i = i0 + c;
+    const float sl2 = a.scale * LOG2E;
+    float qf[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) qf[s] = ld_guard(qb, i, g * NS + s, i < L && g * NS + s < hd, a.ld);
+    f32x4 acc[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) acc[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+    for (int kt = 0; kt <= qt; ++kt) {
+        const int j0 = kt * 16, jr = j0 + c;
+        f32x4 st = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) st = mfma4(ld_guard(kb, jr, g * NS + s, jr < L && g * NS + s < hd, a.ld), qf[s], st);
+        float p[4], mx = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + 4 * g + r;
+            p[r] = (j <= i && j < L) ? st[r] * sl2 : -INFINITY;
+            mx = fmaxf(mx, p[r]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mn = fmaxf(m, mx), alpha = exp2f(m - mn);  // key 0 is in the first tile: mn is finite from there on
+        float rs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            p[r] = exp2f(p[r] - mn);
+            rs += p[r];
+        }
+        rs += __shfl_xor(rs, 16, 64);
+        rs += __shfl_xor(rs, 32, 64);
+        l = l * alpha + rs;
+        m = mn;
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc) acc[cc] *= alpha;
+        if (DROP) {
+            unsigned w[4];
+            keep4(a, bh, i, (j0 >> 2) + g, w);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = w[r] < a.thr ? p[r] * a.inv_keep : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + 4 * g + r;
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc)
+                acc[cc] = mfma4(ld_guard(vb, j, cc * 16 + c, j < L && cc * 16 + c < hd, a.ld), p[r], acc[cc]);
+        }
+    }
+    if (i >= L) return;
+    const float inv_l = 1.f / l;
+    const int proj = a.heads * hd;
+    float* ob = a.out + (row0 + i) * proj + h;
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = cc * 16 + 4 * g + r;
+            if (d < hd) ob[(long)d * a.heads] = acc[cc][r] * inv_l;
+        }
+    if (g == 0) a.lse_out[(long)bh * L + i] = (m + log2f(l)) * LN2;
+}
+
+// delta[bh][i] = sum_d dO[b][i][d*heads+h] * O[b][i][d*heads+h]  (D_i of the FlashAttention-2 backward; holds with dropout too)
+__global__ __launch_bounds__(256) void attn_delta_k(const float* __restrict__ o, const float* __restrict__ dout, float* __restrict__ delta,
+                                                    long rows, int heads, int L, int hd) {
+    const long n = rows * heads;  // (b, i, h)
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
+        const long r = t / heads;
+        const int h = (int)(t - r * heads);
+        const float *ob = o + r * heads * hd + h, *gb = dout + r * heads * hd + h;
+        float s = 0.f;
+        for (int d = 0; d < hd; ++d) s += ob[(long)d * heads] * gb[(long)d * heads];
+        const long b = r / L;
+        delta[(b * heads + h) * L + (r - b * L)] = s;
+    }
+}
+
+// dK, dV: one wave per 16-key tile, over the query tiles at and below the diagonal
+template <int HDP, bool DROP>
+__global__ __launch_bounds__(256) void attn_bwd_dkdv_k(AttnArgs a) {
+    constexpr int NS = HDP / 4, NC = HDP >= 16 ? HDP / 16 : 1;
+    int kt, bh;
+    if (!wave_tile(a, false, kt, bh)) return;
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd, heads = a.heads;
+    const long row0 = (long)b * L, ldo = (long)heads * hd;
+    const float *qb = a.q + row0 * a.ld + h * hd, *kb = a.k + row0 * a.ld + h * hd, *vb = a.v + row0 * a.ld + h * hd;
+    const float* gb = a.dout + row0 * ldo + h;  // dO[i][d] at gb[i * ldo + d * heads]
+    const float *lseb = a.lse + (long)bh * L, *delb = a.delta + (long)bh * L;
+    const int j0 = kt * 16, j = j0 + c;
+    const float sl2 = a.scale * LOG2E;
+    float kf[NS], vf[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const bool ok = j < L && g * NS + s < hd;
+        kf[s] = ld_guard(kb, j, g * NS + s, ok, a.ld);
+        vf[s] = ld_guard(vb, j, g * NS + s, ok, a.ld);
+    }
+    f32x4 adk[NC], adv[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) adk[cc] = adv[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int qt = kt; qt < a.ntiles; ++qt) {
+        const int i0 = qt * 16, ir = i0 + c;
+        f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int d = g * NS + s;
+            const bool ok = ir < L && d < hd;
+            st = mfma4(ld_guard(qb, ir, d, ok, a.ld), kf[s], st);
+            dpt = mfma4(ok ? gb[ir * ldo + (long)d * heads] : 0.f, vf[s], dpt);
+        }
+        // keep bits of (query i0+4g+r, key j): lane (c, g) draws the Philox block of query i0+4g+(c&3), keys j0+4(c>>2) .. +3
+        // -- the 4 x 4 patch its quad needs -- and the quad transposes it in 4 rotations: in rotation t lane k = c&3 takes from
+        // quad lane (k+t)&3 the bit of word k, so each source sends one word (no lane reads a register index of its own choosing)
+        unsigned kmask = 0xFu;
+        if (DROP) {
+            unsigned w[4];
+            keep4(a, bh, i0 + 4 * g + (c & 3), (j0 >> 2) + (c >> 2), w);
+            const int k = c & 3;
+            kmask = 0u;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int sw = (k - t) & 3;  // the word this lane sends in rotation t
+                const unsigned x = sw == 0 ? w[0] : sw == 1 ? w[1] : sw == 2 ? w[2] : w[3];
+                const int src = (lane & ~3) | ((k + t) & 3);
+                const int bit = __shfl((int)(x < a.thr), src, 64);
+                kmask |= (unsigned)bit << ((k + t) & 3);
+            }
+        }
+        float pk[4], ds[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i0 + 4 * g + r;
+            const bool ok = i < L && j <= i;
+            const float p = ok ? exp2f(st[r] * sl2 - lseb[i] * LOG2E) : 0.f;
+            float dp = dpt[r], pd = p;
+            if (DROP) {
+                const bool kp = (kmask >> r) & 1u;
+                dp = kp ? dp * a.inv_keep : 0.f;
+                pd = kp ? p * a.inv_keep : 0.f;
+            }
+            pk[r] = pd;
+            ds[r] = ok ? p * (dp - delb[i]) : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i0 + 4 * g + r;
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc) {
+                const int d = cc * 16 + c;
+                const bool ok = i < L && d < hd;
+                adv[cc] = mfma4(ok ? gb[i * ldo + (long)d * heads] : 0.f, pk[r], adv[cc]);
+                adk[cc] = mfma4(ld_guard(qb, i, d, ok, a.ld), ds[r], adk[cc]);
+            }
+        }
+    }
+    if (j >= L) return;
+    float *dkb = a.dk + (row0 + j) * a.ld + h * hd, *dvb = a.dv + (row0 + j) * a.ld + h * hd;
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = cc * 16 + 4 * g + r;
+            if (d < hd) {
+                dkb[d] = adk[cc][r] * a.scale;
+                dvb[d] = adv[cc][r];
+            }
+        }
+}
+
+// dQ: one wave per 16-query tile, over the key tiles at and left of the diagonal (the forward's orientation)
+template <int HDP, bool DROP>
+__global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
+    constexpr int NS = HDP / 4, NC = HDP >= 16 ? HDP / 16 : 1;
+    int qt, bh;
+    if (!wave_tile(a, true, qt, bh)) return;
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd, heads = a.heads;
+    const long row0 = (long)b * L, ldo = (long)heads * hd;
+    const float *qb = a.q + row0 * a.ld + h * hd, *kb = a.k + row0 * a.ld + h * hd, *vb = a.v + row0 * a.ld + h * hd;
+    const float* gb = a.dout + row0 * ldo + h;
+    const int i0 = qt * 16, i = i0 + c;
+    const float sl2 = a.scale * LOG2E;
+    float qf[NS], gf[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int d = g * NS + s;
+        const bool ok = i < L && d < hd;
+        qf[s] = ld_guard(qb, i, d, ok, a.ld);
+        gf[s] = ok ? gb[i * ldo + (long)d * heads] : 0.f;
+    }
+    const float lse2 = i < L ? a.lse[(long)bh * L + i] * LOG2E : 0.f, di = i < L ? a.delta[(long)bh * L + i] : 0.f;
+    f32x4 acc[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) acc[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt <= qt; ++kt) {
+        const int j0 = kt * 16, jr = j0 + c;
+        f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int d = g * NS + s;
+            const bool ok = jr < L && d < hd;
+            st = mfma4(ld_guard(kb, jr, d, ok, a.ld), qf[s], st);
+            dpt = mfma4(ld_guard(vb, jr, d, ok, a.ld), gf[s], dpt);
+        }
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+        if (DROP) keep4(a, bh, i, (j0 >> 2) + g, w);
+        float ds[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + 4 * g + r;
+            const bool ok = i < L && j <= i;
+            const float p = ok ? exp2f(st[r] * sl2 - lse2) : 0.f;
+            float dp = dpt[r];
+            if (DROP) dp = w[r] < a.thr ? dp * a.inv_keep : 0.f;
+            ds[r] = p * (dp - di);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + 4 * g + r;
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc)
+                acc[cc] = mfma4(ld_guard(kb, j, cc * 16 + c, j < L && cc * 16 + c < hd, a.ld), ds[r], acc[cc]);
+        }
+    }
+    if (i >= L) return;
+    float* dqb = a.dq + (row0 + i) * a.ld + h * hd;
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = cc * 16 + 4 * g + r;
+            if (d < hd) dqb[d] = acc[cc][r] * a.scale;
+        }
+}
+
+// keep[bh][i][j] in {0, 1} for every (i, j) < L (test / measurement hook; the kernels above never store the mask)
+__global__ __launch_bounds__(256) void attn_mask_k(AttnArgs a, uint8_t* __restrict__ keep, long n4) {
+    const int L = a.L, LQ = (L + 3) >> 2;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += (long)gridDim.x * blockDim.x) {
+        const long row = t / LQ;  // bh * L + i
+        const int jq = (int)(t - row * LQ);
+        const int bh = (int)(row / L), i = (int)(row - (long)bh * L);
+        unsigned w[4];
+        keep4(a, bh, i, jq, w);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (jq * 4 + r < L) keep[row * L + jq * 4 + r] = (!a.drop || w[r] < a.thr) ? 1 : 0;
+    }
+}
+
+int hdp_of(int hd) { return hd <= 8 ? 8 : hd <= 16 ? 16 : hd <= 32 ? 32 : 64; }
+
+// common argument checks and the per-call constants; rc != MOVAE_OK: error already set
+int setup(AttnArgs& a, const char* what, long ld, int B, int heads, int L, int hd, float p, unsigned long long seed, unsigned long long draw) {
+    MOVAE_CHECK_ARG(B > 0 && heads > 0 && L > 0 && hd > 0, "%s: bad sizes B=%d heads=%d L=%d head_dim=%d", what, B, heads, L, hd);
+    MOVAE_CHECK_ARG(hd <= 64, "%s: head_dim %d exceeds the supported maximum of 64", what, hd);
+    MOVAE_CHECK_ARG(ld >= (long)heads * hd, "%s: row stride %ld < heads * head_dim", what, ld);
+    MOVAE_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout p must be in [0, 1), got %g", what, (double)p);
+    MOVAE_CHECK_ARG((long)B * heads <= (1L << 30) && L <= (1 << 28), "%s: sizes out of range", what);
+    a = AttnArgs{};
+    a.ld = ld;
+    a.heads = heads, a.L = L, a.hd = hd;
+    a.ntiles = (L + 15) / 16;
+    a.nbh = B * heads;
+    a.scale = 1.f / sqrtf((float)hd);
+    const double t = (1.0 - (double)p) * 4294967296.0;
+    a.thr = p > 0.f ? (unsigned)(t >= 4294967295.0 ? 4294967295.0 : t) : 0xFFFFFFFFu;
+    a.drop = p > 0.f;
+    a.inv_keep = p > 0.f ? (float)(1.0 / (1.0 - (double)p)) : 1.f;
+    a.s0 = (unsigned)seed, a.s1 = (unsigned)(seed >> 32) ^ (unsigned)(draw >> 32), a.d0 = (unsigned)draw;
+    return MOVAE_OK;
+}
+
+dim3 tile_grid(const AttnArgs& a) { return dim3((unsigned)(((a.ntiles + 3) / 4) * a.nbh)); }
+
+// one template instance per padded head dim (8 / 16 / 32 / 64) and dropout on / off
+#define ATTN_LAUNCH(KERNEL, a, drop, stream)                                                              \
+    do {                                                                                                  \
+        const dim3 grid_ = tile_grid(a);                                                                  \
+        const int hdp_ = hdp_of((a).hd);                                                                  \
+        if (hdp_ == 8) {                                                                                  \
+            if (drop) hipLaunchKernelGGL((KERNEL<8, true>), grid_, dim3(256), 0, stream, a);              \
+            else hipLaunchKernelGGL((KERNEL<8, false>), grid_, dim3(256), 0, stream, a);                  \
+        } else if (hdp_ == 16) {                                                                          \
+            if (drop) hipLaunchKernelGGL((KERNEL<16, true>), grid_, dim3(256), 0, stream, a);             \
+            else hipLaunchKernelGGL((KERNEL<16, false>), grid_, dim3(256), 0, stream, a);                 \
+        } else if (hdp_ == 32) {                                                                          \
+            if (drop) hipLaunchKernelGGL((KERNEL<32, true>), grid_, dim3(256), 0, stream, a);             \
+            else hipLaunchKernelGGL((KERNEL<32, false>), grid_, dim3(256), 0, stream, a);                 \
+        } else {                                                                                          \
+            if (drop) hipLaunchKernelGGL((KERNEL<64, true>), grid_, dim3(256), 0, stream, a);             \
+            else hipLaunchKernelGGL((KERNEL<64, false>), grid_, dim3(256), 0, stream, a);                 \
+        }                                                                                                 \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int movae_causal_attn_fwd(const float* q, const float* k, const float* v, long ld, float* out, float* lse, int B, int heads, int L,
+                          int hd, float p, unsigned long long seed, unsigned long long draw, movae_stream_t stream) {
+    MOVAE_CHECK_ARG(q && k && v && out && lse, "movae_causal_attn_fwd: null pointer");
+    AttnArgs a;
+    const int rc = setup(a, "movae_causal_attn_fwd", ld, B, heads, L, hd, p, seed, draw);
+    if (rc != MOVAE_OK) return rc;
+    a.q = q, a.k = k, a.v = v, a.out = out, a.lse_out = lse;
+    const bool drop = p > 0.f;
+    ATTN_LAUNCH(attn_fwd_k, a, drop, (hipStream_t)stream);
+    MOVAE_CHECK_LAUNCH("causal_attn_fwd");
+    return MOVAE_OK;
+}
+
+size_t movae_causal_attn_ws_bytes(int B, int heads, int L) {
+    return MOVAE_WS_HEADER_BYTES + (size_t)B * heads * L * sizeof(float);
+}
+
+int movae_causal_attn_bwd(const float* q, const float* k, const float* v, long ld, const float* out, const float* dout, const float* lse,
+                          float* dq, float* dk, float* dv, int B, int heads, int L, int hd, float p, unsigned long long seed,
+                          unsigned long long draw, void* ws, size_t ws_bytes, movae_stream_t stream) {
+    MOVAE_WS_SCRATCH(ws, ws_bytes);
+    MOVAE_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv, "movae_causal_attn_bwd: null pointer");
+    AttnArgs a;
+    const int rc = setup(a, "movae_causal_attn_bwd", ld, B, heads, L, hd, p, seed, draw);
+    if (rc != MOVAE_OK) return rc;
+    MOVAE_CHECK_ARG(ws && ws_bytes >= (size_t)B * heads * L * sizeof(float), "movae_causal_attn_bwd: workspace too small");
+    float* delta = static_cast<float*>(ws);
+    const long rows = (long)B * L;
+    const long n = rows * heads;
+    long g = (n + 255) / 256;
+    g = g > 8192 ? 8192 : g;
+    hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, out, dout, delta, rows, heads, L, hd);
+    MOVAE_CHECK_LAUNCH("causal_attn_delta");
+    a.q = q, a.k = k, a.v = v, a.dout = dout, a.lse = lse, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
+    const bool drop = p > 0.f;
+    ATTN_LAUNCH(attn_bwd_dkdv_k, a, drop, (hipStream_t)stream);
+    MOVAE_CHECK_LAUNCH("causal_attn_bwd_dkdv");
+    ATTN_LAUNCH(attn_bwd_dq_k, a, drop, (hipStream_t)stream);
+    MOVAE_CHECK_LAUNCH("causal_attn_bwd_dq");
+    return MOVAE_OK;
+}
+
+int movae_causal_attn_dropout_mask(uint8_t* keep, int BH, int L, float p, unsigned long long seed, unsigned long long draw,
+                                   movae_stream_t stream) {
+    MOVAE_CHECK_ARG(keep && BH > 0 && L > 0 && p >= 0.f && p < 1.f, "movae_causal_attn_dropout_mask: bad argument");
+    AttnArgs a = AttnArgs{};
+    const int rc = setup(a, "movae_causal_attn_dropout_mask", 1, 1, 1, L, 1, p, seed, draw);
+    if (rc != MOVAE_OK) return rc;
+    const long n4 = (long)BH * L * ((L + 3) / 4);
+    long g = (n4 + 255) / 256;
+    g = g > 16384 ? 16384 : g;
+    hipLaunchKernelGGL(attn_mask_k, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, a, keep, n4);
+    MOVAE_CHECK_LAUNCH("causal_attn_dropout_mask");
+    return MOVAE_OK;
+}
+
+}  // extern "C"

@@ -109,6 +109,21 @@ __device__ __forceinline__ bool arrive_last(unsigned* counter, unsigned nblk) {
     return s_last != 0;
 }
 
+
+// Philox4x32-10 (Salmon et al., SC'11; the counter-based generator family torch / cuRAND / rocRAND use): four 32-bit words of
+// counter (c0..c3) under key (k0, k1).  Shared by the reparameterisation draws (eltwise.hip) and the attention dropout mask
+// (attention.hip).
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
 // block-wide sum for 256-thread blocks; result valid in every thread
 // Column fold of a 256-thread block whose thread t owns column cl = t % CQB of row group rg = t / CQB (CQB a power of two):
 // on return the threads with rg == 0 hold, in v[], the sums over all row groups of their column.  Row groups that share a

@@ -5,6 +5,7 @@ from .betatc_vae import BetaTCVAE
 from .gg_vae import GGVAE
 from .gg_vq_vae import GGVQVAE
 from .gg_vq_vae2 import GGVQVAE2
+from .pixelcnn_prior import HierarchicalPixelCNN, HierarchicalPixelSNAIL, PixelCNN, PixelSNAIL
 from .recursive_vaes import CycleVAE, RecursiveCyclicVAE, RecursiveKLVAE
 from .vae import VAE
 from .vq_vae import VQVAE, VectorQuantizer
@@ -120,4 +121,4 @@ def get_network(input_size, num_channels=3, args=None, device=None):
 
 
 __all__ = ["VAE", "VQVAE", "VQVAE2", "BetaTCVAE", "GGVAE", "GGVQVAE", "GGVQVAE2", "VectorQuantizer", "RecursiveKLVAE", "CycleVAE",
-           "RecursiveCyclicVAE", "get_network"]
+           "RecursiveCyclicVAE", "PixelCNN", "HierarchicalPixelCNN", "PixelSNAIL", "HierarchicalPixelSNAIL", "get_network"]

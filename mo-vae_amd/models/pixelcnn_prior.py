@@ -1,8 +1,9 @@
 """PixelCNN priors over the discrete VQ code grids on the HIP kernels -- drop-in for the reference's
 models/pixelcnn_prior.py:25-54 (MaskedConv2d), :57-92 (GatedResBlock), :262-349 (PixelCNN) and :352-421 (HierarchicalPixelCNN):
 same constructor signatures, state_dict keys (incl. the `mask` buffers) and init sequence, forward(x[B,H,W] int64) -> logits
-[B, K, H, W] (a zero-copy NCHW view of the NHWC logits the kernels write).  PixelSNAIL (:95-259, :424+) adds causal
-self-attention and is outside SURVEY 8f.4's row: the training stage refuses `--prior_type pixelsnail` by name.
+[B, K, H, W] (a zero-copy NCHW view of the NHWC logits the kernels write).  PixelSNAIL (:95-259) and HierarchicalPixelSNAIL
+(:434-555) add causal self-attention, which runs on the fused kernels of csrc/attention.hip (ops.causal_attention); prior.py builds
+them with build_pixelsnail_prior, while `--prior_type pixelsnail` on the command line is still refused by name.
 
 Every convolution runs on the implicit-GEMM kernels; the embedding gather, the gated combine, the weight mask and the
 cross-entropy are csrc/prior.hip.  Activations stay NHWC: nn.Embedding of a [B,H,W] grid IS the NHWC activation, and the
@@ -162,3 +163,109 @@ class HierarchicalPixelCNN(tnn.Module):
 
     def total_trainable_params(self):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+
+class CausalAttention2d(tnn.Module):
+    """pixelcnn_prior.py:95-135 on NHWC activations: three 1x1 projections, the fused causal attention (ops.causal_attention: no
+    [L, L] matrix) and out_proj, which reads the attention output in the reference's channel order d * heads + h.
+
+    Dropout (the reference's nn.Dropout on the probabilities) is drawn inside the kernels from (seed, draw): seed is
+    torch.cuda.initial_seed(), draw combines the module's index in its model (`stream`) with a host counter that advances once per
+    training-mode forward, so the same torch.manual_seed gives the same masks and nothing is drawn from torch's generators."""
+
+    def __init__(self, channels, num_heads=8, head_dim=None, dropout=0.1):
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = head_dim or (channels // num_heads)
+        assert channels % num_heads == 0 or head_dim is not None, "channels must be divisible by num_heads"
+        self.proj_dim = self.head_dim * num_heads
+        self.q_proj = mnn.Conv2d(channels, self.proj_dim, 1)
+        self.k_proj = mnn.Conv2d(channels, self.proj_dim, 1)
+        self.v_proj = mnn.Conv2d(channels, self.proj_dim, 1)
+        self.out_proj = mnn.Conv2d(self.proj_dim, channels, 1)
+        self.dropout = tnn.Dropout(dropout)  # holds p; never called (the kernels apply it)
+        self.stream = 0  # set by PixelSNAIL: distinct dropout streams per block
+        self.draws = 0
+
+    def forward(self, x):
+        p = self.dropout.p if self.training else 0.0
+        seed = draw = 0
+        if p > 0.0:
+            seed, draw = torch.cuda.initial_seed(), (self.stream << 40) | self.draws
+            self.draws += 1
+        o = ops.causal_attention(self.q_proj(x), self.k_proj(x), self.v_proj(x), self.num_heads, p, seed, draw)
+        return self.out_proj(o)
+
+
+class PixelSNAILBlock(tnn.Module):
+    """pixelcnn_prior.py:138-156: gated residual blocks, causal attention, out_conv(cat([x, attn])) + x."""
+
+    def __init__(self, channels, num_res_blocks=2, num_heads=8, dropout=0.1):
+        super().__init__()
+        self.res_blocks = tnn.ModuleList([GatedResBlock(channels) for _ in range(num_res_blocks)])
+        self.attention = CausalAttention2d(channels, num_heads=num_heads, dropout=dropout)
+        self.out_conv = mnn.Conv2d(channels * 2, channels, 1)
+
+    def forward(self, x):
+        for blk in self.res_blocks:
+            x = blk(x)
+        return ops.add(self.out_conv(ops.concat_channels(x, self.attention(x))), x)
+
+
+class PixelSNAIL(tnn.Module):
+    """pixelcnn_prior.py:159-259."""
+
+    def __init__(self, num_embeddings, embedding_dim=64, hidden_channels=128, num_blocks=8, num_res_blocks_per_layer=2, num_heads=8,
+                 kernel_size=7, conditional_channels=0, dropout=0.1):
+        super().__init__()
+        self.num_embeddings, self.embedding_dim = num_embeddings, embedding_dim
+        self.embedding = Embedding(num_embeddings, embedding_dim)
+        self.conv_in = MaskedConv2d("A", embedding_dim + conditional_channels + 2, hidden_channels, kernel_size, padding=kernel_size // 2)
+        self.blocks = tnn.ModuleList([PixelSNAILBlock(hidden_channels, num_res_blocks=num_res_blocks_per_layer, num_heads=num_heads,
+                                                      dropout=dropout) for _ in range(num_blocks)])
+        self.conv_out = _OutHead(hidden_channels, num_embeddings)
+        for i, blk in enumerate(self.blocks):
+            blk.attention.stream = i
+        self._pos = {}
+
+    def _pos_encoding(self, batch, height, width, device):
+        """NHWC [B, H, W, 2] of the reference's row / column coordinates (:195-203), built once per shape."""
+        key = (batch, height, width, str(device))
+        pos = self._pos.get(key)
+        if pos is None:
+            coord_h = (torch.arange(height, dtype=torch.float32) - height / 2) / max(height, 1)
+            coord_w = (torch.arange(width, dtype=torch.float32) - width / 2) / max(width, 1)
+            pos = torch.stack([coord_h.view(height, 1).expand(height, width), coord_w.view(1, width).expand(height, width)], dim=-1)
+            pos = self._pos[key] = pos.expand(batch, height, width, 2).contiguous().to(device)
+        return pos
+
+    def forward_nhwc(self, x, condition=None):
+        """x [B, H, W] int64, condition NHWC [B, H, W, C] or None -> NHWC logits [B, H, W, K]."""
+        B, H, W = x.shape
+        h = ops.concat_channels(self.embedding(x), self._pos_encoding(B, H, W, x.device))
+        if condition is not None:
+            h = ops.concat_channels(h, condition)
+        h = self.conv_in(h)
+        for blk in self.blocks:
+            h = ops.add(h, blk(h))
+        return self.conv_out(h)
+
+    forward = PixelCNN.forward
+    loss = PixelCNN.loss
+    sample = PixelCNN.sample
+    total_trainable_params = PixelCNN.total_trainable_params
+
+
+class HierarchicalPixelSNAIL(HierarchicalPixelCNN):
+    """pixelcnn_prior.py:434-555: PixelSNAIL over the top codes, the conditional PixelCNN over the bottom codes."""
+
+    def __init__(self, num_embeddings, embedding_dim=64, hidden_channels=128, num_blocks_top=8, num_res_blocks_per_layer=2, num_heads=8,
+                 num_layers_bottom=15, dropout=0.1):
+        tnn.Module.__init__(self)
+        self.num_embeddings, self.embedding_dim = num_embeddings, embedding_dim
+        self.prior_top = PixelSNAIL(num_embeddings=num_embeddings, embedding_dim=embedding_dim, hidden_channels=hidden_channels,
+                                    num_blocks=num_blocks_top, num_res_blocks_per_layer=num_res_blocks_per_layer, num_heads=num_heads,
+                                    dropout=dropout)
+        self.embedding_top = Embedding(num_embeddings, embedding_dim)
+        self.upsample_top = mnn.ConvTranspose2d(embedding_dim, embedding_dim, 4, stride=2, padding=1)
+        self.prior_bottom = PixelCNN(num_embeddings, embedding_dim, hidden_channels, num_layers_bottom, conditional_channels=embedding_dim)

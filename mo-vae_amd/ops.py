@@ -2011,3 +2011,65 @@ class CrossEntropy(Function):
 
 def cross_entropy(logits, target):
     return CrossEntropy.apply(logits, target)
+
+
+# ---------------------------------------------------------------------------------------------
+# PixelSNAIL's causal self-attention (models/pixelcnn_prior.py:95-135; csrc/attention.hip)
+def _attn_ws(device, nbytes):
+    """The shared workspace when it is large enough, else a buffer of this call's own (the first 4 KiB header stays zero)."""
+    w = L.workspace(device)
+    if w.numel() >= nbytes:
+        return w
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+class CausalAttention(Function):
+    """softmax(mask(Q K^T / sqrt(hd))) with dropout, times V, over the [..., proj] NHWC outputs of the three 1x1 projections; the
+    result is [..., proj] in the reference's channel order d * heads + h (pixelcnn_prior.py:130).  The backward regenerates the
+    dropout mask from (seed, draw) instead of storing it."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, p, seed, draw):
+        ctx.set_materialize_grads(False)  # an absent cotangent arrives as None: no zero-fill, no kernels on zeros
+        L.require_gpu(q)
+        q, k, v = _c(q), _c(k), _c(v)
+        assert q.shape == k.shape == v.shape and q.dtype == torch.float32
+        proj = q.shape[-1]
+        if proj % heads:
+            raise ValueError(f"causal_attention: {proj} channels do not split into {heads} heads")
+        B = q.shape[0]
+        n = q.numel() // (B * proj)
+        o = torch.empty_like(q)
+        lse = torch.empty((B * heads, n), dtype=q.dtype, device=q.device)
+        p = float(p)
+        _call("movae_causal_attn_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), proj, o.data_ptr(), lse.data_ptr(), B, heads, n,
+              proj // heads, p, seed, draw, _st(q))
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.cfg = (B, heads, n, proj // heads, p, seed, draw)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        if do is None:
+            return (None,) * 7
+        q, k, v, o, lse = ctx.saved_tensors
+        B, heads, n, hd, p, seed, draw = ctx.cfg
+        do = _c(do)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        ws = _attn_ws(q.device, L.load().movae_causal_attn_ws_bytes(B, heads, n))
+        _call("movae_causal_attn_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), heads * hd, o.data_ptr(), do.data_ptr(), lse.data_ptr(),
+              dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, heads, n, hd, p, seed, draw, ws.data_ptr(), ws.numel(), _st(q))
+        return dq, dk, dv, None, None, None, None
+
+
+def causal_attention(q, k, v, heads, p=0.0, seed=0, draw=0):
+    """q, k, v: [B, ..., heads * hd] (NHWC; head h at channels h*hd ..), causal over the flattened positions; p = 0 (or eval mode
+    in the caller) takes the no-dropout kernels.  (seed, draw) select the dropout mask (causal_attention_dropout_mask)."""
+    return CausalAttention.apply(q, k, v, int(heads), float(p), int(seed), int(draw))
+
+
+def causal_attention_dropout_mask(bh, n, p, seed, draw, device):
+    """The keep mask [bh, n, n] (uint8, 1 = kept) that causal_attention(p, seed, draw) applies (test / measurement hook)."""
+    keep = torch.empty((bh, n, n), dtype=torch.uint8, device=device)
+    _call("movae_causal_attn_dropout_mask", keep.data_ptr(), bh, n, float(p), int(seed), int(draw), L.stream_ptr(keep.device))
+    return keep

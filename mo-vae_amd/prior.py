@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from .models.pixelcnn_prior import HierarchicalPixelCNN, PixelCNN
+from .models.pixelcnn_prior import HierarchicalPixelCNN, HierarchicalPixelSNAIL, PixelCNN, PixelSNAIL
 from .optim import FusedAdam, clip_grad_norm_
 
 #: what the last train_pixelcnn_prior call did (tests and callers that want the numbers; the reference only prints them)
@@ -82,17 +82,33 @@ def build_prior(net, args, device):
     return cls(**kw).to(device)
 
 
-def train_pixelcnn_prior(net, train_loader, device, args, save_root):
-    """main.py:890-1043.  Returns the trained prior (eval mode)."""
+def build_pixelsnail_prior(net, args, device):
+    """main.py:917-944 (the `use_pixelsnail` branches): PixelSNAIL, or HierarchicalPixelSNAIL for the two-level VQ models."""
+    hidden = getattr(args, "pixelcnn_hidden_channels", 128)
+    common = dict(num_embeddings=net.num_embeddings, embedding_dim=net.embedding_dim, hidden_channels=hidden,
+                  num_res_blocks_per_layer=getattr(args, "pixelsnail_num_res_blocks", 2), num_heads=getattr(args, "pixelsnail_num_heads", 8),
+                  dropout=getattr(args, "pixelsnail_dropout", 0.1))
+    if is_hierarchical_arch(getattr(args, "arch", "vae")):
+        return HierarchicalPixelSNAIL(num_blocks_top=getattr(args, "pixelsnail_num_blocks", 8),
+                                      num_layers_bottom=getattr(args, "pixelcnn_num_layers", 15), **common).to(device)
+    return PixelSNAIL(num_blocks=getattr(args, "pixelsnail_num_blocks", 8), **common).to(device)
+
+
+def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None):
+    """main.py:890-1043.  Returns the trained prior (eval mode).  `prior`: an already built prior to train instead of the one
+    build_prior makes (e.g. build_pixelsnail_prior's; a PixelSNAIL prior writes under pixelsnail_prior/, main.py:913)."""
     hier = is_hierarchical_arch(getattr(args, "arch", "vae"))
     epochs = getattr(args, "pixelcnn_epochs", 100)
     lr = getattr(args, "pixelcnn_lr", 3e-4)
     net.eval()
     for p in net.parameters():
         p.requires_grad = False
-    prior_dir = os.path.join(save_root, "pixelcnn_prior")
+    snail = isinstance(prior, (PixelSNAIL, HierarchicalPixelSNAIL))
+    name = "PixelSNAIL" if snail else "PixelCNN"
+    prior_dir = os.path.join(save_root, "pixelsnail_prior" if snail else "pixelcnn_prior")
     os.makedirs(os.path.join(prior_dir, "checkpoints"), exist_ok=True)
-    prior = build_prior(net, args, device)
+    if prior is None:
+        prior = build_prior(net, args, device)
     opt = FusedAdam(prior.parameters(), lr=lr, weight_decay=0.0)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=epochs, eta_min=1e-6)
     use_cache = getattr(args, "prior_use_lmdb_codes", True)
@@ -101,7 +117,7 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root):
         ds = extract_codes(net, train_loader, device, hier)
         n_codes = len(ds)
         codes_loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True, num_workers=0, drop_last=False)
-    print(f"Training PixelCNN prior for {epochs} epochs..." + (" (codes extracted once, held in memory)" if use_cache
+    print(f"Training {name} prior for {epochs} epochs..." + (" (codes extracted once, held in memory)" if use_cache
                                                              else " (extracting codes on-the-fly)"))
     K = net.num_embeddings
     best, epoch_losses = float("inf"), []
@@ -148,7 +164,7 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root):
                        os.path.join(prior_dir, "checkpoints", "best_prior.pth"))
     torch.save({"model_state_dict": {k: v.contiguous() for k, v in prior.state_dict().items()}, "epoch": epochs},
                os.path.join(prior_dir, "checkpoints", "final_prior.pth"))
-    print(f"PixelCNN prior training complete. Best loss: {best:.4f}. Saved to {prior_dir}")
+    print(f"{name} prior training complete. Best loss: {best:.4f}. Saved to {prior_dir}")
     prior.eval()
     samples = generate_samples_vq_with_prior(net, prior, getattr(args, "num_vis_samples", 4), device,
                                              getattr(args, "pixelcnn_temperature", 1.0))
