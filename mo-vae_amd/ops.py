@@ -17,6 +17,13 @@ from . import _lib as L
 
 _call = L.call
 
+
+def _knob(name, default="1"):
+    """The A/B switch MOVAE_<name> of the environment: on unless set to "0" -- with default "0", off unless set to "1"."""
+    v = os.environ.get("MOVAE_" + name, default)
+    return v == "1" if default == "0" else v != "0"
+
+
 #: data_ptr of a parameter -> 1-D destination tensor for its gradient.  autojac.mtl_backward points this at
 #: the current row of the Jacobian arena so wgrad / BN-backward kernels write their results in place
 #: (consumed on first use; a second use of the same parameter falls back to a fresh buffer).
@@ -30,12 +37,19 @@ SINK_LOG = []
 SINK_ZERO_LOG = []
 
 
-def _sink(param, shape):
-    dst = GRAD_SINK.pop(param.data_ptr(), None) if GRAD_SINK else None
+def _registered(sinks, param, shape, log):
+    """The sink registered for `param` in the dict `sinks` (consumed, and its data_ptr logged), or None."""
+    dst = sinks.pop(param.data_ptr(), None) if sinks else None
     if dst is not None and dst.numel() == param.numel():
-        SINK_LOG.append(dst.data_ptr())
+        log.append(dst.data_ptr())
         return dst.view(shape)
-    return torch.empty(shape, dtype=param.dtype, device=param.device)
+    return None
+
+
+def _sink(g, param, shape):
+    """Destination of the gradient of `param` for the engine's single cotangent (g is 0)."""
+    dst = _registered(GRAD_SINK, param, shape, SINK_LOG)
+    return dst if dst is not None else torch.empty(shape, dtype=param.dtype, device=param.device)
 
 
 #: data_ptr of a parameter -> its EXISTING gradient tensor: the weight-gradient kernels add into it (split-K reduce with
@@ -95,11 +109,8 @@ GRAD_SINK_ROWS = None
 def _sink_row(g, param, shape, zeros=False):
     """Destination of group g's gradient of `param` in a batched backward (J row of that group when registered)."""
     rows = GRAD_SINK_ROWS
-    dst = rows[g].pop(param.data_ptr(), None) if rows else None
-    if dst is not None and dst.numel() == param.numel():
-        (SINK_ZERO_LOG if zeros else SINK_LOG).append(dst.data_ptr())  # (zeros: the slice is handed out untouched)
-        return dst.view(shape)
-    return (torch.zeros if zeros else torch.empty)(shape, dtype=param.dtype, device=param.device)
+    dst = _registered(rows[g] if rows else None, param, shape, SINK_ZERO_LOG if zeros else SINK_LOG)  # (zeros: handed out untouched)
+    return dst if dst is not None else (torch.zeros if zeros else torch.empty)(shape, dtype=param.dtype, device=param.device)
 
 
 def _stacked(t, G):
@@ -112,20 +123,44 @@ def _stacked(t, G):
 _ZERO_GRADS = {}
 
 
-def _sink_zeros(param, shape):
+def _sink_zeros(g, param, shape):
     """An all-zero gradient: sinks are zero-initialised by their owner (autojac.JacobianBuffer) and written at most
     once, so a registered sink is returned untouched -- no fill launch.  Without a sink the parameter gets ONE persistent
     zero tensor for life (a bias in front of a training-mode BatchNorm: its gradient is identically zero, so whatever is
     accumulated into this tensor later is zero as well); nothing here launches a fill per step."""
-    dst = GRAD_SINK.pop(param.data_ptr(), None) if GRAD_SINK else None
-    if dst is not None and dst.numel() == param.numel():
-        SINK_ZERO_LOG.append(dst.data_ptr())
-        return dst.view(shape)
+    dst = _registered(GRAD_SINK, param, shape, SINK_ZERO_LOG)
+    if dst is not None:
+        return dst
     key = (param.data_ptr(), param.numel(), param.dtype)
     z = _ZERO_GRADS.get(key)
     if z is None or z.device != param.device:
         z = _ZERO_GRADS[key] = torch.zeros(param.numel(), dtype=param.dtype, device=param.device)
     return z.view(shape)
+
+
+class _Dest:
+    """Where a backward body (`_run`) puts group g's gradient of a parameter, and with it what only one of its two callers does.
+    Two instances, no subclasses: _ENGINE serves Function.backward (torch's engine: one cotangent, stacked as [1, ...]), _WALKER
+    serves backward_batched (autojac._batched_pullback: G cotangents, G = 1 included).
+      sink(g, param, shape)   the destination -- a registered sink (logged in SINK_LOG) or a fresh buffer
+      zeros(g, param, shape)  an identically zero gradient, handed out untouched (SINK_ZERO_LOG); the engine's form keeps ONE
+                              persistent zero tensor per parameter that has no sink
+      accum(w, b, need_b)     in-place accumulation targets (GRAD_ACCUM), the engine's alone; else (None, None)
+      engine                  the engine's launch choices: the per-layer fork (MOVAE_SIDE_STREAM=fork), and the entry points of
+                              one cotangent (movae_act_bwd, movae_bn_act_bwd) where the walker takes the grouped ones"""
+    __slots__ = ("sink", "zeros", "accum", "engine")
+
+    def __init__(self, sink, zeros, accum, engine):
+        self.sink, self.zeros, self.accum, self.engine = sink, zeros, accum, engine
+
+
+_ENGINE = _Dest(_sink, _sink_zeros, _accum_targets, True)
+_WALKER = _Dest(_sink_row, lambda g, p, shape: _sink_row(g, p, shape, zeros=True), lambda w, b, need_b: (None, None), False)
+
+
+def _first(t):
+    """Group 0 of a backward body's result (stacked tensor or per-group list), None staying None."""
+    return t[0] if t is not None else None
 
 
 def _ws(t):
@@ -172,22 +207,21 @@ class NchwToNhwc(Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        if dy is None:
-            return (None,) * 1
-        dy = _c(dy)
-        n, h, w, c = dy.shape
-        dx = torch.empty((n, c, h, w), dtype=dy.dtype, device=dy.device)
-        _call("movae_nhwc_to_nchw", dy.data_ptr(), dx.data_ptr(), n, c, h, w, _st(dy))
-        return dx
-
-    @staticmethod
-    def backward_batched(ctx, G, dy):
-        dy = _stacked(dy, G)
+    def _run(G, dy):
         _, n, h, w, c = dy.shape
         dx = torch.empty((G, n, c, h, w), dtype=dy.dtype, device=dy.device)
         _call("movae_nhwc_to_nchw", dy.data_ptr(), dx.data_ptr(), G * n, c, h, w, _st(dy))
-        return (dx,)
+        return dx
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return None
+        return NchwToNhwc._run(1, _c(dy).unsqueeze(0))[0]
+
+    @staticmethod
+    def backward_batched(ctx, G, dy):
+        return (NchwToNhwc._run(G, _stacked(dy, G)),)
 
 
 class NhwcToNchw(Function):
@@ -202,22 +236,21 @@ class NhwcToNchw(Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        if dy is None:
-            return (None,) * 1
-        dy = _c(dy)
-        n, c, h, w = dy.shape
-        dx = torch.empty((n, h, w, c), dtype=dy.dtype, device=dy.device)
-        _call("movae_nchw_to_nhwc", dy.data_ptr(), dx.data_ptr(), n, c, h, w, _st(dy))
-        return dx
-
-    @staticmethod
-    def backward_batched(ctx, G, dy):
-        dy = _stacked(dy, G)
+    def _run(G, dy):
         _, n, c, h, w = dy.shape
         dx = torch.empty((G, n, h, w, c), dtype=dy.dtype, device=dy.device)
         _call("movae_nchw_to_nhwc", dy.data_ptr(), dx.data_ptr(), G * n, c, h, w, _st(dy))
-        return (dx,)
+        return dx
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return None
+        return NhwcToNchw._run(1, _c(dy).unsqueeze(0))[0]
+
+    @staticmethod
+    def backward_batched(ctx, G, dy):
+        return (NhwcToNchw._run(G, _stacked(dy, G)),)
 
 
 _LAST_NHWC = [None]  # (weakref to the NCHW source, its version counter, data_ptr, capturing?, the NHWC copy)
@@ -227,7 +260,6 @@ def forget_nhwc():
     """Drop the remembered conversion (train.GraphedTrainStep calls this around every capture: a result produced eagerly
     must not stand in for a launch the graph has to contain, and graph-pool memory must not leak into eager code)."""
     _LAST_NHWC[0] = None
-
 
 
 def to_nhwc(x):
@@ -303,7 +335,7 @@ def join_wgrad():
 
 
 #: MOVAE_DEFER_REDUCE=0: every weight-gradient reduce is a launch of its own (A/B knob)
-DEFER_REDUCE = os.environ.get("MOVAE_DEFER_REDUCE", "1") != "0"
+DEFER_REDUCE = _knob("DEFER_REDUCE")
 
 
 class deferred_reduces:
@@ -389,7 +421,7 @@ def _res_take(carrier):
 
 
 #: MOVAE_FUSE_ACT=0: every conv runs its own activation-backward pass (A/B knob)
-FUSE_ACT = __import__("os").environ.get("MOVAE_FUSE_ACT", "1") != "0"
+FUSE_ACT = _knob("FUSE_ACT")
 
 
 class ConvFusion:
@@ -422,12 +454,12 @@ class ConvFusion:
 #: (entry point, geometry) for which the library answered "unsupported" to a fused input transform: not asked again
 _NO_FUSE = set()
 #: A/B knobs of the fusion's three parts (development): the normalise-on-load of consumers, the statistics from producer epilogues
-FUSE_NORM = __import__("os").environ.get("MOVAE_FUSE_NORM", "1") != "0"
-FUSE_STATS = __import__("os").environ.get("MOVAE_FUSE_STATS", "1") != "0"
+FUSE_NORM = _knob("FUSE_NORM")
+FUSE_STATS = _knob("FUSE_STATS")
 
 
 #: MOVAE_BN_FIN=0: never ask a producer to finish the BatchNorm that follows (A/B knob; the kernels' own switch is MOVAE_KGEMM_BN_FIN)
-BN_FIN = os.environ.get("MOVAE_BN_FIN", "1") != "0"
+BN_FIN = _knob("BN_FIN")
 
 
 def _fuse_fin(f, bn_fin, out):
@@ -458,7 +490,7 @@ def _fuse_struct(in_norm, stats=None, bn=None, ep=None):
 
 
 #: MOVAE_FUSE_BN_BWD=0: the BatchNorm backward runs its own reduction pass (the sums are not taken from the dgrad epilogue)
-FUSE_BN_BWD = __import__("os").environ.get("MOVAE_FUSE_BN_BWD", "1") != "0"
+FUSE_BN_BWD = _knob("FUSE_BN_BWD")
 
 
 def _bn_request(ctx, x, in_norm, G):
@@ -537,6 +569,39 @@ def scale_shift_act(y, scale, shift, slope):
     return out
 
 
+def _act_bwd(dest, G, dy, y, dx, act, slope):
+    """dx[g] = dy[g] * act'(y) for the G stacked cotangents.  Which entry point is the CALLER's choice (dest.engine), never G == 1: the
+    engine's single cotangent takes movae_act_bwd; the walker -- a single-row pull-back included -- takes the grouped kernel (all
+    groups in one launch, no bias sums) where the operands are aligned, and movae_act_bwd once per group where they are not."""
+    c = y.shape[-1]
+    if not dest.engine and c % 4 == 0 and dy.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:
+        wsp, wsb = _ws(dy)
+        _call("movae_act_bwd_bias_grouped", G, dy.data_ptr(), y.data_ptr(), dx.data_ptr(), None, y.numel() // c, c, L.ACT[act], float(slope), 0,
+              wsp, wsb, _st(dy))
+        return
+    step = y.numel() * dy.element_size()
+    for g in range(G):
+        _call("movae_act_bwd", dy.data_ptr() + g * step, y.data_ptr(), dx.data_ptr() + g * step, y.numel(), L.ACT[act], float(slope), _st(dy))
+
+
+def _call_f(name, geom, x, in_norm, args, fuse):
+    """The *_f form of entry point `name` on the operand x with the virtual transform in_norm (or None): args(x) -> the plain argument
+    list, fuse(in_norm, retry) -> the movae_fuse_t.  Where the dispatched kernel cannot apply the transform (L.Unsupported) the shape is
+    remembered in _NO_FUSE, the transformed operand is materialised and the call repeated without it (retry=True).
+    -> (x as used, in_norm as used, the fuse struct of the call that ran)."""
+    f = fuse(in_norm, False)
+    try:
+        _call(name + "_f", *args(x), C.byref(f))
+    except L.Unsupported:
+        if in_norm is None:
+            raise
+        _NO_FUSE.add((name, geom))
+        x, in_norm = scale_shift_act(x, *in_norm), None
+        f = fuse(None, True)
+        _call(name + "_f", *args(x), C.byref(f))
+    return x, in_norm, f
+
+
 class Conv(Function):
     """conv2d / conv_transpose2d / linear (+bias, + fused activation).  `fusion` (ConvFusion or None): BatchNorm fused into the
     conv -- the producer's normalisation + activation applied to the input while it is loaded, and / or the statistics of the
@@ -578,24 +643,18 @@ class Conv(Function):
         if in_norm is None and stats is None and ep_fwd is None:
             _call(fn, x.data_ptr(), wm.data_ptr(), L.ptr(b), y.data_ptr(), *geom, L.ACT[act], float(slope), wsp, wsb, _st(x))
         else:
-            f = _fuse_struct(in_norm, stats, None, ep_fwd)
             fin_out = None
             if stats is not None and fusion.bn_fin is not None and BN_FIN:
                 fin_out = torch.empty((4, co), dtype=torch.float32, device=x.device)
-                _fuse_fin(f, fusion.bn_fin, fin_out)
-            try:
-                _call(fn + "_f", x.data_ptr(), wm.data_ptr(), L.ptr(b), y.data_ptr(), *geom, L.ACT[act], float(slope), wsp, wsb, _st(x),
-                      C.byref(f))
-            except L.Unsupported:  # nothing was launched: materialise the normalised input, then the same call without it
-                if in_norm is None:
-                    raise
-                _NO_FUSE.add((fn, geom))
-                x, in_norm = scale_shift_act(x, *in_norm), None
-                f = _fuse_struct(None, stats, None, ep_fwd)
+
+            def fuse(nrm, retry):
+                f = _fuse_struct(nrm, stats, None, ep_fwd)
                 if fin_out is not None:
                     _fuse_fin(f, fusion.bn_fin, fin_out)
-                _call(fn + "_f", x.data_ptr(), wm.data_ptr(), L.ptr(b), y.data_ptr(), *geom, L.ACT[act], float(slope), wsp, wsb, _st(x),
-                      C.byref(f))
+                return f
+
+            x, in_norm, f = _call_f(fn, geom, x, in_norm, lambda x: (x.data_ptr(), wm.data_ptr(), L.ptr(b), y.data_ptr(), *geom, L.ACT[act],
+                                                                     float(slope), wsp, wsb, _st(x)), fuse)
             if fusion is not None:
                 fusion.stats, fusion.parts = stats, int(f.stats_parts)
                 fusion.fin = fin_out if (fin_out is not None and int(f.fin_done)) else None
@@ -634,155 +693,61 @@ class Conv(Function):
         to a materialised activation where the dispatched kernel cannot apply the transform.  args: (head, x_index, tail).
         bn: BatchNorm-backward request for the paired call's dgrad (_bn_request).  Returns (x as used, fuse struct or None)."""
         head, xi, tail = args
+        x = head[xi]
         if in_norm is not None and (name, geom) in _NO_FUSE:
-            head = list(head)
-            head[xi] = scale_shift_act(head[xi], *in_norm)
-            in_norm = None
-        ptrs = lambda h: [t.data_ptr() if isinstance(t, torch.Tensor) else t for t in h]  # noqa: E731
+            x, in_norm = scale_shift_act(x, *in_norm), None
+        argv = lambda x: [t.data_ptr() if isinstance(t, torch.Tensor) else t for t in head[:xi] + (x,) + head[xi + 1:]] + list(tail)  # noqa: E731
         if in_norm is None and bn is None and ep is None:
-            _call(name, *ptrs(head), *tail)
-            return head[xi], None
-        f = _fuse_struct(in_norm, None, bn, ep)
-        try:
-            _call(name + "_f", *ptrs(head), *tail, C.byref(f))
-            return head[xi], f
-        except L.Unsupported:
-            if in_norm is None:
-                raise
-            _NO_FUSE.add((name, geom))
-            head = list(head)
-            head[xi] = scale_shift_act(head[xi], *in_norm)
-            f = _fuse_struct(None, None, bn)
-            _call(name + "_f", *ptrs(head), *tail, C.byref(f))
-            return head[xi], f
+            _call(name, *argv(x))
+            return x, None
+        # The repeated call asks for no `ep`.  Only a paired call gets here with one (its input a virtual activation, MOVAE_LAZY_ACT=1,
+        # on a shape whose weight gradient takes a kernel without the operand transform), and its first attempt has by then run the
+        # dgrad WITH the epilogue (the library issues the pair's dgrad before it asks the wgrad
+        # dispatch).  Harmless: the repeat overwrites dx with the plain input gradient and reports ep_act_done == 0, so _act_publish
+        # publishes nothing -- the producer runs its own activation backward, the carrier keeps its cotangent for _res_finish.  From
+        # the next step on _NO_FUSE materialises up front and the epilogue is asked for again.
+        x, _, f = _call_f(name, geom, x, in_norm, argv, lambda nrm, retry: _fuse_struct(nrm, None, bn, None if retry else ep))
+        return x, f
 
     @staticmethod
-    def backward(ctx, dy):
-        if dy is None:
-            return (None,) * 11
+    def _run(ctx, G, dy, dest):
+        """The backward of the G stacked cotangents dy [G, n, ho, wo, co] -> (dx [G, ...], [dW per group], [dbias per group]).
+        dgrad runs as ONE launch over G*n images -- the pull-back is linear and per-sample, and the deep layers' grids are far
+        too small to fill the chip one cotangent at a time; wgrad is one grouped launch (each group reduces over its own
+        pixels, x is shared) writing straight into the groups' destinations (`dest`: _ENGINE / _WALKER)."""
         x, w, y, b, in_norm = Conv._saved(ctx)
-        dy = _c(dy)
         if ctx.res_out is not None:  # this conv's output is branch + block input: dy is the identity branch's cotangent too
             ctx.res_out.res = dy
         n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad = ctx.geom
         st = _st(dy)
         wsp, wsb = _ws(dy)
+        arr = C.c_void_p * G
         db_done = None
         if L.ACT[ctx.act] and not _act_take(ctx, dy):
             dpre = torch.empty_like(dy)
             if _fuse_bias_grad(ctx, dy, y, co):
                 # activation backward and the bias gradient (column sums of dpre) in one pass over dy
-                db_done = _sink(b, (co,))
-                _call("movae_act_bwd_bias_grouped", 1, dy.data_ptr(), y.data_ptr(), dpre.data_ptr(), (C.c_void_p * 1)(db_done.data_ptr()),
-                      dy.numel() // co, co, L.ACT[ctx.act], float(ctx.slope), 0, wsp, wsb, st)
+                db_done = [dest.sink(g, b, (co,)) for g in range(G)]
+                _call("movae_act_bwd_bias_grouped", G, dy.data_ptr(), y.data_ptr(), dpre.data_ptr(), arr(*[t.data_ptr() for t in db_done]),
+                      y.numel() // co, co, L.ACT[ctx.act], float(ctx.slope), 0, wsp, wsb, st)
             else:
-                _call("movae_act_bwd", dy.data_ptr(), y.data_ptr(), dpre.data_ptr(), dy.numel(), L.ACT[ctx.act], float(ctx.slope), st)
-            dy = dpre
-        pre = "movae_convT2d_" if ctx.transposed else "movae_conv2d_"
-        dx = dw = db = None
-        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-        # dgrad and wgrad only share read-only operands: when both are needed the wgrad (+ its reduce / bias sum)
-        # is issued on a forked side stream with its own scratch arena and joined afterwards, so the two short,
-        # latency-bound launches overlap on the device (also inside a captured hipGraph, as parallel branches)
-        defer = L.DEFER
-        fork = need_w and (defer is not None or (L.SIDE_STREAM_WGRAD and ctx.needs_input_grad[0]))
-        if fork:
-            main, side = torch.cuda.current_stream(dy.device), L.side_stream(dy.device)
-            side.wait_stream(main)
-        pair = need_w and ctx.needs_input_grad[0] and not fork  # both gradients, one stream: one call, one main launch
-        bn = _bn_request(ctx, x, in_norm, 1)
-        ep = _act_request(ctx, x, bn, x.shape)
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            wm = weight_mem(w)
-            if not pair:
-                if bn is None and ep is None:
-                    _call(pre + "dgrad", dy.data_ptr(), wm.data_ptr(), dx.data_ptr(), n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad,
-                          wsp, wsb, st)
-                else:
-                    f = _fuse_struct(None, None, bn, ep)
-                    _call(pre + "dgrad_f", dy.data_ptr(), wm.data_ptr(), dx.data_ptr(), n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad,
-                          wsp, wsb, st, C.byref(f), 1)
-                    _bn_publish(ctx, f, bn, dx, 1)
-                    _act_publish(ep, f, dx)
-        if fork:
-            ws2 = L.workspace(dy.device, slot=1)
-            wsp, wsb, st = ws2.data_ptr(), ws2.numel(), side.cuda_stream
-        if need_w:
-            wm_shape = (ci, kh, kw, co) if ctx.transposed else (co, kh, kw, ci)
-            # a task-side parameter that an earlier loss already reached: add into its gradient inside the kernels' reduce
-            plain_bias = ctx.has_bias and ctx.needs_input_grad[2] and db_done is None and not ctx.bias_grad_is_zero
-            acc_w, acc_b = _accum_targets(w, b, plain_bias) if (db_done is None and not (ctx.has_bias and ctx.bias_grad_is_zero)) else (None, None)
-            acc = 1 if acc_w is not None else 0
-            nlog = len(SINK_LOG)
-            dwm = acc_w.view(wm_shape) if acc else _sink(w, wm_shape)
-            db_k = None
-            if db_done is not None:
-                db = db_done
-            elif ctx.has_bias and ctx.needs_input_grad[2]:
-                if ctx.bias_grad_is_zero:
-                    # the bias feeds a training-mode BatchNorm, which subtracts the batch mean: d(loss)/d(bias) == 0
-                    # identically (the reference's value is rounding noise of order 1e-9); no column-sum pass
-                    db = _sink_zeros(b, (co,))
-                else:
-                    db = db_k = (acc_b if acc else _sink(b, (co,)))
-            dbp = (C.c_void_p * 1)(db_k.data_ptr()) if db_k is not None else None
-            # every destination a sink (or an in-place accumulation target): the split-K reduce may ride on a later launch
-            armed = _defer_ws(dy, not fork and (acc or len(SINK_LOG) - nlog == 1 + (db_k is not None)))
-            if armed is not None:
-                wsp, wsb = armed
-            tail = (n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, acc, wsp, wsb, st)
-            if pair:
-                x, f = Conv._wgrad_call(pre + "dgrad_wgrad_grouped", in_norm, ctx.geom,
-                                        ((1, dy, wm, x, dx, (C.c_void_p * 1)(dwm.data_ptr()), dbp), 3, tail), bn, ep)
-                _bn_publish(ctx, f, bn, dx, 1)
-                _act_publish(ep, f, dx)
-            else:
-                x, _ = Conv._wgrad_call(pre + "wgrad_grouped", in_norm, ctx.geom, ((1, dy, x, (C.c_void_p * 1)(dwm.data_ptr()), dbp), 2, tail))
-            dw = dwm.permute(0, 3, 1, 2)
-        if fork and defer is not None:
-            defer.keep.append((dy, x, dwm, db))  # joined once, by wgrad_side_stream
-            defer.used = True
-        elif fork:
-            main.wait_stream(side)
-        dx = _res_finish(ctx, dx)
-        return dx, dw, db, None, None, None, None, None, None, None, None
-
-    @staticmethod
-    def backward_batched(ctx, G, dy):
-        """The backward of G cotangents at once (autojac._batched_pullback): dy is [G, n, ho, wo, co] (or a list of
-        G tensors).  dgrad runs as ONE launch over G*n images -- the pull-back is linear and per-sample, and the deep
-        layers' grids are far too small to fill the chip one cotangent at a time; wgrad is one grouped launch (each
-        group reduces over its own pixels, x is shared) writing straight into the groups' Jacobian rows."""
-        x, w, y, b, in_norm = Conv._saved(ctx)
-        dy = _stacked(dy, G)
-        if ctx.res_out is not None:
-            ctx.res_out.res = dy
-        n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad = ctx.geom
-        st = _st(dy)
-        wsp, wsb = _ws(dy)
-        db_done = None
-        if L.ACT[ctx.act] and not _act_take(ctx, dy):
-            dpre = torch.empty_like(dy)
-            if _fuse_bias_grad(ctx, dy, y, co):
-                db_done = [_sink_row(g, b, (co,)) for g in range(G)]
-                _call("movae_act_bwd_bias_grouped", G, dy.data_ptr(), y.data_ptr(), dpre.data_ptr(),
-                      (C.c_void_p * G)(*[t.data_ptr() for t in db_done]), y.numel() // co, co, L.ACT[ctx.act], float(ctx.slope), 0,
-                      wsp, wsb, st)
-            elif co % 4 == 0 and dy.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:  # all groups in one launch, no bias sums
-                _call("movae_act_bwd_bias_grouped", G, dy.data_ptr(), y.data_ptr(), dpre.data_ptr(), None, y.numel() // co, co,
-                      L.ACT[ctx.act], float(ctx.slope), 0, wsp, wsb, st)
-            else:
-                for g in range(G):
-                    _call("movae_act_bwd", dy[g].data_ptr(), y.data_ptr(), dpre[g].data_ptr(), y.numel(), L.ACT[ctx.act],
-                          float(ctx.slope), st)
+                _act_bwd(dest, G, dy, y, dpre, ctx.act, ctx.slope)
             dy = dpre
         pre = "movae_convT2d_" if ctx.transposed else "movae_conv2d_"
         dx = dw = db = None
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         need_w = ctx.needs_input_grad[1] or need_b
-        defer = L.DEFER if need_w else None
-        pair = need_w and ctx.needs_input_grad[0] and defer is None
+        # dgrad and wgrad only share read-only operands: inside wgrad_side_stream (L.DEFER) the wgrad (+ its reduce / bias sum) is
+        # issued on a forked side stream with its own scratch arena, so the two short, latency-bound launches overlap on the
+        # device (also inside a captured hipGraph, as parallel branches).  The per-layer fork with its own join
+        # (MOVAE_SIDE_STREAM=fork) is the engine's alone.
+        defer = L.DEFER
+        fork = need_w and (defer is not None or (dest.engine and L.SIDE_STREAM_WGRAD and ctx.needs_input_grad[0]))
+        pair = need_w and ctx.needs_input_grad[0] and not fork  # both gradients, one stream: one call, one main launch
+        if fork:
+            main, side = torch.cuda.current_stream(dy.device), L.side_stream(dy.device)
+            if dest.engine:  # (the engine's form forks in front of the dgrad, the walker's behind it: kept as they were)
+                side.wait_stream(main)
         bn = _bn_request(ctx, x, in_norm, G)
         ep = _act_request(ctx, x, bn, (G,) + tuple(x.shape))
         if ctx.needs_input_grad[0]:
@@ -798,41 +763,62 @@ class Conv(Function):
                           wsp, wsb, st, C.byref(f), G)
                     _bn_publish(ctx, f, bn, dx, G)
                     _act_publish(ep, f, dx)
-        if defer is not None:  # the grouped wgrad goes to the side stream (see wgrad_side_stream)
-            side = L.side_stream(dy.device)
-            side.wait_stream(torch.cuda.current_stream(dy.device))
+        if fork:
+            if not dest.engine:
+                side.wait_stream(main)
             ws2 = L.workspace(dy.device, slot=1)
             wsp, wsb, st = ws2.data_ptr(), ws2.numel(), side.cuda_stream
         if need_w:
             wm_shape = (ci, kh, kw, co) if ctx.transposed else (co, kh, kw, ci)
+            # a task-side parameter that an earlier loss already reached: add into its gradient inside the kernels' reduce
+            plain_bias = need_b and db_done is None and not ctx.bias_grad_is_zero
+            acc_w, acc_b = dest.accum(w, b, plain_bias) if (db_done is None and not (ctx.has_bias and ctx.bias_grad_is_zero)) else (None, None)
+            acc = 1 if acc_w is not None else 0
             nlog = len(SINK_LOG)
-            dwm = [_sink_row(g, w, wm_shape) for g in range(G)]
-            arr = C.c_void_p * G
+            dwm = [acc_w.view(wm_shape)] if acc else [dest.sink(g, w, wm_shape) for g in range(G)]
+            db_k = None
             if db_done is not None:
-                db, dbp = db_done, None  # already produced by the fused activation-backward pass
-            else:
-                db = [_sink_row(g, b, (co,), zeros=ctx.bias_grad_is_zero) for g in range(G)] if need_b else None
-                dbp = arr(*[t.data_ptr() for t in db]) if (need_b and not ctx.bias_grad_is_zero) else None
+                db = db_done  # already produced by the fused activation-backward pass
+            elif need_b and ctx.bias_grad_is_zero:
+                # the bias feeds a training-mode BatchNorm, which subtracts the batch mean: d(loss)/d(bias) == 0
+                # identically (the reference's value is rounding noise of order 1e-9); no column-sum pass
+                db = [dest.zeros(g, b, (co,)) for g in range(G)]
+            elif need_b:
+                db = db_k = [acc_b] if acc else [dest.sink(g, b, (co,)) for g in range(G)]
+            dbp = arr(*[t.data_ptr() for t in db_k]) if db_k is not None else None
             # one grouped launch: blockIdx.z = group * splits + split, x is read by every group, dy by its own; with the
-            # input gradient wanted too, dgrad and wgrad share the launch (igemm2_pair)
-            # every destination a Jacobian row: the split-K reduce may ride on a later launch (deferred_reduces)
-            armed = _defer_ws(dy, defer is None and len(SINK_LOG) - nlog == G * (1 + (dbp is not None)))
+            # input gradient wanted too, dgrad and wgrad share the launch (igemm2_pair).  Every destination a sink (or an
+            # in-place accumulation target): the split-K reduce may ride on a later launch (deferred_reduces)
+            armed = _defer_ws(dy, not fork and (acc or len(SINK_LOG) - nlog == G * (1 + (db_k is not None))))
             if armed is not None:
                 wsp, wsb = armed
-            tail = (n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, 0, wsp, wsb, st)
+            tail = (n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, acc, wsp, wsb, st)
+            dwp = arr(*[t.data_ptr() for t in dwm])
             if pair:
-                x, f = Conv._wgrad_call(pre + "dgrad_wgrad_grouped", in_norm, ctx.geom,
-                                        ((G, dy, wm, x, dx, arr(*[t.data_ptr() for t in dwm]), dbp), 3, tail), bn, ep)
+                x, f = Conv._wgrad_call(pre + "dgrad_wgrad_grouped", in_norm, ctx.geom, ((G, dy, wm, x, dx, dwp, dbp), 3, tail), bn, ep)
                 _bn_publish(ctx, f, bn, dx, G)
                 _act_publish(ep, f, dx)
             else:
-                x, _ = Conv._wgrad_call(pre + "wgrad_grouped", in_norm, ctx.geom, ((G, dy, x, arr(*[t.data_ptr() for t in dwm]), dbp), 2, tail))
+                x, _ = Conv._wgrad_call(pre + "wgrad_grouped", in_norm, ctx.geom, ((G, dy, x, dwp, dbp), 2, tail))
             dw = [t.permute(0, 3, 1, 2) for t in dwm]
-            if defer is not None:
-                defer.keep.append((dy, x, dwm, db))
-                defer.used = True
-        dx = _res_finish(ctx, dx)
-        return dx, dw, db, None, None, None, None, None, None, None, None
+        if fork and defer is not None:
+            defer.keep.append((dy, x, dwm, db))  # joined once, by wgrad_side_stream
+            defer.used = True
+        elif fork:
+            main.wait_stream(side)
+        return _res_finish(ctx, dx), dw, db
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 11
+        dx, dw, db = Conv._run(ctx, 1, _c(dy).unsqueeze(0), _ENGINE)
+        return (_first(dx), _first(dw), _first(db)) + (None,) * 8
+
+    @staticmethod
+    def backward_batched(ctx, G, dy):
+        """autojac._batched_pullback: dy is [G, n, ho, wo, co] (or a list of G tensors)."""
+        return Conv._run(ctx, G, _stacked(dy, G), _WALKER) + (None,) * 8
 
 
 def _fuse_bias_grad(ctx, dy, y, co):
@@ -862,7 +848,7 @@ def linear(x, w, b=None, act=None, slope=0.01):
 
 
 #: MOVAE_LINEAR_PAIR=0: fc_mu / fc_var as two ordinary linear calls
-LINEAR_PAIR = __import__("os").environ.get("MOVAE_LINEAR_PAIR", "1") != "0"
+LINEAR_PAIR = _knob("LINEAR_PAIR")
 
 
 def linear_pair_ok(x, w1, b1, w2, b2, groups=1):
@@ -895,8 +881,8 @@ class LinearPair(Function):
         return y1, y2
 
     @staticmethod
-    def _run(ctx, G, dy1, dy2, sink):
-        """dy_i: [G, m, n] stacked (or None: that output had no cotangent).  sink(g, param, shape) -> gradient destination."""
+    def _run(ctx, G, dy1, dy2, dest):
+        """dy_i: [G, m, n] stacked (or None: that output had no cotangent).  dest: _ENGINE / _WALKER."""
         x, w1, b1, w2, b2 = ctx.saved_tensors
         m, k = x.shape
         n = w1.shape[0]
@@ -910,8 +896,8 @@ class LinearPair(Function):
         dx = torch.empty((G, m, k), dtype=x.dtype, device=x.device) if need_x else None
         dw1 = dw2 = db1 = db2 = None
         if need_w:
-            dw1, dw2 = [sink(g, w1, (n, k)) for g in range(G)], [sink(g, w2, (n, k)) for g in range(G)]
-            db1, db2 = [sink(g, b1, (n,)) for g in range(G)], [sink(g, b2, (n,)) for g in range(G)]
+            dw1, dw2 = [dest.sink(g, w1, (n, k)) for g in range(G)], [dest.sink(g, w2, (n, k)) for g in range(G)]
+            db1, db2 = [dest.sink(g, b1, (n,)) for g in range(G)], [dest.sink(g, b2, (n,)) for g in range(G)]
         for g0 in range(0, G, 4):  # (the entry point takes up to four cotangent groups)
             g1 = min(G, g0 + 4)
             ptrs = lambda ts: (C.c_void_p * (g1 - g0))(*[t.data_ptr() for t in ts[g0:g1]]) if ts is not None else None  # noqa: E731
@@ -924,16 +910,14 @@ class LinearPair(Function):
         if dy1 is None and dy2 is None:
             return None, None, None, None, None
         one = lambda t: _c(t).unsqueeze(0) if t is not None else None  # noqa: E731
-        dx, dw1, db1, dw2, db2 = LinearPair._run(ctx, 1, one(dy1), one(dy2), lambda g, p, shape: _sink(p, shape))
-        first = lambda ts: ts[0] if ts is not None else None  # noqa: E731
-        return (dx[0] if dx is not None else None), first(dw1), first(db1), first(dw2), first(db2)
+        return tuple(_first(t) for t in LinearPair._run(ctx, 1, one(dy1), one(dy2), _ENGINE))
 
     @staticmethod
     def backward_batched(ctx, G, dy1, dy2):
         if dy1 is None and dy2 is None:
             return None, None, None, None, None
         st = lambda t: _stacked(t, G) if t is not None else None  # noqa: E731
-        return LinearPair._run(ctx, G, st(dy1), st(dy2), _sink_row)
+        return LinearPair._run(ctx, G, st(dy1), st(dy2), _WALKER)
 
 
 def linear_pair(x, w1, b1, w2, b2):
@@ -965,42 +949,39 @@ class BatchNormAct(Function):
         return out
 
     @staticmethod
+    def _run(ctx, G, dout, dest):
+        if not ctx.training:
+            raise RuntimeError("BatchNormAct backward is implemented for training-mode statistics only")
+        gamma, beta = ctx.saved_tensors[1:3]
+        dgs = [dest.sink(g, gamma, gamma.shape) for g in range(G)]
+        dbs = [dest.sink(g, beta, beta.shape) for g in range(G)]
+        return _bn_act_bwd(dest, G, dout, ctx.saved_tensors, dgs, dbs, ctx.act, ctx.slope), dgs, dbs
+
+    @staticmethod
     def backward(ctx, dout):
         if dout is None:
             return (None,) * 11
-        y, gamma, beta, mean, rstd = ctx.saved_tensors
-        if not ctx.training:
-            raise RuntimeError("BatchNormAct backward is implemented for training-mode statistics only")
-        dout = _c(dout)
-        c = y.shape[-1]
-        rows = y.numel() // c
-        dy = torch.empty_like(y)
-        dg = _sink(gamma, gamma.shape)
-        db = _sink(beta, beta.shape)
-        wsp, wsb = _ws(y)
-        _call("movae_bn_act_bwd", dout.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-              rstd.data_ptr(), dy.data_ptr(), dg.data_ptr(), db.data_ptr(), rows, c, L.ACT[ctx.act], float(ctx.slope), 0,
-              wsp, wsb, _st(y))
-        return dy, dg, db, None, None, None, None, None, None, None, None
+        return tuple(t[0] for t in BatchNormAct._run(ctx, 1, _c(dout).unsqueeze(0), _ENGINE)) + (None,) * 8
 
     @staticmethod
     def backward_batched(ctx, G, dout):
-        y, gamma, beta, mean, rstd = ctx.saved_tensors
-        if not ctx.training:
-            raise RuntimeError("BatchNormAct backward is implemented for training-mode statistics only")
-        dout = _stacked(dout, G)
-        c = y.shape[-1]
-        rows = y.numel() // c
-        dy = torch.empty_like(dout)
-        wsp, wsb = _ws(y)
-        dgs = [_sink_row(g, gamma, gamma.shape) for g in range(G)]
-        dbs = [_sink_row(g, beta, beta.shape) for g in range(G)]
-        arr = C.c_void_p * G
-        # one grouped call: the batch statistics of the cotangent are taken per group inside the kernels (blockIdx.y)
-        _call("movae_bn_act_bwd_grouped", G, dout.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-              rstd.data_ptr(), dy.data_ptr(), arr(*[t.data_ptr() for t in dgs]), arr(*[t.data_ptr() for t in dbs]), rows, c,
-              L.ACT[ctx.act], float(ctx.slope), 0, wsp, wsb, _st(y))
-        return dy, dgs, dbs, None, None, None, None, None, None, None, None
+        return BatchNormAct._run(ctx, G, _stacked(dout, G), _WALKER) + (None,) * 8
+
+
+def _bn_act_bwd(dest, G, dout, saved, dgs, dbs, act, slope):
+    """-> dy [G, ...]: the training-mode BatchNorm (+ activation) backward of the G stacked cotangents dout on the saved raw y, the
+    parameter gradients written to dgs[g] / dbs[g].  The batch statistics of the cotangent are taken per group inside the kernels
+    (blockIdx.y).  As in _act_bwd the entry point is the caller's choice, not G == 1's."""
+    y, gamma, beta, mean, rstd = saved[:5]
+    c = y.shape[-1]
+    dy = torch.empty_like(dout)
+    wsp, wsb = _ws(y)
+    arr = C.c_void_p * G
+    name, head, dg, db = ("movae_bn_act_bwd", (), dgs[0].data_ptr(), dbs[0].data_ptr()) if dest.engine else \
+        ("movae_bn_act_bwd_grouped", (G,), arr(*[t.data_ptr() for t in dgs]), arr(*[t.data_ptr() for t in dbs]))
+    _call(name, *head, dout.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dy.data_ptr(),
+          dg, db, y.numel() // c, c, L.ACT[act], float(slope), 0, wsp, wsb, _st(y))
+    return dy
 
 
 # ---- BatchNorm fused into its neighbours (DESIGN.md section 3.5) ---------------------------------------------------------------
@@ -1024,7 +1005,7 @@ class LazyBN:
 #: MOVAE_LAZY_ACT=1: a stand-alone ReLU / LeakyReLU in front of a conv is not written to memory -- the conv applies it while loading
 #: (LazyAct).  OFF by default: measured SLOWER (C4 4.56 vs 4.44 ms, C3 10.61 vs 10.56): the operand transform in the consumer's
 #: forward and weight-gradient kernels costs more than the twelve 6 us activation launches it removes.
-LAZY_ACT = os.environ.get("MOVAE_LAZY_ACT", "0") == "1"
+LAZY_ACT = _knob("LAZY_ACT", "0")
 _UNIT_MAP = {}
 
 
@@ -1096,22 +1077,17 @@ class BatchNormLazy(Function):
         st = _st(y)
         if fin is not None:  # the producer conv finished this BatchNorm inside its own launch (movae_fuse_t::fin_*)
             mean, rstd, scale, shift = fin[0], fin[1], fin[2], fin[3]
-            ctx.act, ctx.slope = ("lrelu" if slope not in _ACT_OF_SLOPE else _ACT_OF_SLOPE[slope]), slope
-            ctx.link = link
-            ctx.save_for_backward(y, gamma, beta, mean, rstd, scale, shift)
-            ctx.mark_non_differentiable(scale, shift)
-            ctx.set_materialize_grads(False)
-            return y.view_as(y), scale, shift
-        if not parts:
-            stats = torch.empty(1100 * 2 * c, dtype=torch.float32, device=y.device)  # movae_bn_stats: at most 1024 partials (+ room to fold them)
-            pout = C.c_int(0)
-            _call("movae_bn_stats", y.data_ptr(), rows, c, stats.data_ptr(), stats.numel(), C.byref(pout), st)
-            parts = pout.value
-        mean = torch.empty(c, dtype=y.dtype, device=y.device)
-        rstd, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-        _call("movae_bn_finalize", stats.data_ptr(), stats.numel(), int(parts), rows, c, gamma.data_ptr(), beta.data_ptr(), float(eps), float(momentum),
-              mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), L.ptr(running_mean), L.ptr(running_var),
-              L.ptr(num_batches_tracked), st)
+        else:
+            if not parts:
+                stats = torch.empty(1100 * 2 * c, dtype=torch.float32, device=y.device)  # movae_bn_stats: at most 1024 partials (+ room to fold them)
+                pout = C.c_int(0)
+                _call("movae_bn_stats", y.data_ptr(), rows, c, stats.data_ptr(), stats.numel(), C.byref(pout), st)
+                parts = pout.value
+            mean = torch.empty(c, dtype=y.dtype, device=y.device)
+            rstd, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
+            _call("movae_bn_finalize", stats.data_ptr(), stats.numel(), int(parts), rows, c, gamma.data_ptr(), beta.data_ptr(), float(eps),
+                  float(momentum), mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), L.ptr(running_mean),
+                  L.ptr(running_var), L.ptr(num_batches_tracked), st)
         ctx.act, ctx.slope = ("lrelu" if slope not in _ACT_OF_SLOPE else _ACT_OF_SLOPE[slope]), slope
         ctx.link = link
         ctx.save_for_backward(y, gamma, beta, mean, rstd, scale, shift)
@@ -1142,43 +1118,24 @@ class BatchNormLazy(Function):
         return dy
 
     @staticmethod
+    def _run(ctx, G, dout, dest):
+        gamma, beta = ctx.saved_tensors[1:3]
+        dgs = [dest.sink(g, gamma, gamma.shape) for g in range(G)]
+        dbs = [dest.sink(g, beta, beta.shape) for g in range(G)]
+        dy = BatchNormLazy._from_sums(ctx, G, dout, dgs, dbs)
+        if dy is None:
+            dy = _bn_act_bwd(dest, G, dout, ctx.saved_tensors, dgs, dbs, ctx.act, ctx.slope)
+        return dy, dgs, dbs
+
+    @staticmethod
     def backward(ctx, dout, _ds, _dh):
         if dout is None:
             return (None,) * 13
-        y, gamma, beta, mean, rstd = ctx.saved_tensors[:5]
-        dout = _c(dout)
-        c = y.shape[-1]
-        rows = y.numel() // c
-        dg = _sink(gamma, gamma.shape)
-        db = _sink(beta, beta.shape)
-        dy = BatchNormLazy._from_sums(ctx, 1, dout, [dg], [db])
-        if dy is not None:
-            return dy, dg, db, None, None, None, None, None, None, None, None, None, None
-        dy = torch.empty_like(y)
-        wsp, wsb = _ws(y)
-        _call("movae_bn_act_bwd", dout.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-              rstd.data_ptr(), dy.data_ptr(), dg.data_ptr(), db.data_ptr(), rows, c, L.ACT[ctx.act], float(ctx.slope), 0,
-              wsp, wsb, _st(y))
-        return dy, dg, db, None, None, None, None, None, None, None, None, None, None
+        return tuple(t[0] for t in BatchNormLazy._run(ctx, 1, _c(dout).unsqueeze(0), _ENGINE)) + (None,) * 10
 
     @staticmethod
     def backward_batched(ctx, G, dout, _ds=None, _dh=None):
-        y, gamma, beta, mean, rstd = ctx.saved_tensors[:5]
-        dout = _stacked(dout, G)
-        c = y.shape[-1]
-        rows = y.numel() // c
-        dgs = [_sink_row(g, gamma, gamma.shape) for g in range(G)]
-        dbs = [_sink_row(g, beta, beta.shape) for g in range(G)]
-        dy = BatchNormLazy._from_sums(ctx, G, dout, dgs, dbs)
-        if dy is not None:
-            return dy, dgs, dbs, None, None, None, None, None, None, None, None, None, None
-        dy = torch.empty_like(dout)
-        wsp, wsb = _ws(y)
-        arr = C.c_void_p * G
-        _call("movae_bn_act_bwd_grouped", G, dout.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-              rstd.data_ptr(), dy.data_ptr(), arr(*[t.data_ptr() for t in dgs]), arr(*[t.data_ptr() for t in dbs]), rows, c,
-              L.ACT[ctx.act], float(ctx.slope), 0, wsp, wsb, _st(y))
-        return dy, dgs, dbs, None, None, None, None, None, None, None, None, None, None
+        return BatchNormLazy._run(ctx, G, _stacked(dout, G), _WALKER) + (None,) * 10
 
 
 def batch_norm_lazy(y, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, act, slope, fusion):
@@ -1227,16 +1184,13 @@ class Activation(Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        if dy is None:
-            return (None,) * 6
+    def _run(ctx, G, dy, dest):
         (y,) = ctx.saved_tensors
-        dy = _c(dy)
         if _act_take(ctx, dy):
-            return Activation._add_res(ctx, dy, ctx.act_out.res_done), None, None, None, None, None
+            return Activation._add_res(ctx, dy, ctx.act_out.res_done)
         dx = torch.empty_like(dy)
-        _call("movae_act_bwd", dy.data_ptr(), y.data_ptr(), dx.data_ptr(), dy.numel(), L.ACT[ctx.act], float(ctx.slope), _st(dy))
-        return Activation._add_res(ctx, dx, False), None, None, None, None, None
+        _act_bwd(dest, G, dy, y, dx, ctx.act, ctx.slope)
+        return Activation._add_res(ctx, dx, False)
 
     @staticmethod
     def _add_res(ctx, dx, already):
@@ -1248,22 +1202,14 @@ class Activation(Function):
         return dx
 
     @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 6
+        return (Activation._run(ctx, 1, _c(dy).unsqueeze(0), _ENGINE)[0],) + (None,) * 5
+
+    @staticmethod
     def backward_batched(ctx, G, dy):
-        (y,) = ctx.saved_tensors
-        dy = _stacked(dy, G)
-        if _act_take(ctx, dy):
-            return Activation._add_res(ctx, dy, ctx.act_out.res_done), None, None, None, None, None
-        dx = torch.empty_like(dy)
-        c = y.shape[-1]
-        if c % 4 == 0 and dy.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:  # all groups in one launch
-            wsp, wsb = _ws(dy)
-            _call("movae_act_bwd_bias_grouped", G, dy.data_ptr(), y.data_ptr(), dx.data_ptr(), None, y.numel() // c, c, L.ACT[ctx.act],
-                  float(ctx.slope), 0, wsp, wsb, _st(dy))
-        else:
-            for g in range(G):
-                _call("movae_act_bwd", dy[g].data_ptr(), y.data_ptr(), dx[g].data_ptr(), y.numel(), L.ACT[ctx.act], float(ctx.slope),
-                      _st(dy))
-        return Activation._add_res(ctx, dx, False), None, None, None, None, None
+        return (Activation._run(ctx, G, _stacked(dy, G), _WALKER),) + (None,) * 5
 
 
 def activation(x, act, slope=0.01, act_out=None, res_in=None):
@@ -1307,20 +1253,22 @@ class ResidualAdd(Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        if dy is None:
-            return (None,) * 3
+    def _run(ctx, dy, stacked):
+        """dy passes through as it came (tensor or per-group list); the carrier gets it stacked ([G, ...]: stacked(dy))."""
         if ctx.carrier is None or not ctx.needs_input_grad[1]:
             return dy, dy, None
-        ctx.carrier.res = _c(dy)
+        ctx.carrier.res = stacked(dy)
         return dy, None, None
 
     @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 3
+        return ResidualAdd._run(ctx, dy, lambda t: _c(t).unsqueeze(0))
+
+    @staticmethod
     def backward_batched(ctx, G, dy):
-        if ctx.carrier is None or not ctx.needs_input_grad[1]:
-            return dy, dy, None
-        ctx.carrier.res = _stacked(dy, G)
-        return dy, None, None
+        return ResidualAdd._run(ctx, dy, lambda t: _stacked(t, G))
 
 
 def residual_add(branch, x, carrier):
