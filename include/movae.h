@@ -12,9 +12,10 @@
  *     and transposed-conv weights [Ci][KH][KW][Co] in memory (the channels_last image of the
  *     reference's OIHW / IOHW parameter shapes), Linear weights [out][in];
  *   - `ws`/`ws_bytes`: scratch for split-K partials / reduction partials; may be NULL/0 where stated (then no
- *     split-K).  The FIRST 4096 BYTES of the workspace are the library's hand-off counters: they must be zero
- *     before the first call (hipMemset once), are left zero by every call, and one workspace must only be used
- *     by one stream at a time; everything after the header is plain scratch with no state between calls;
+ *     split-K).  The FIRST 4096 BYTES of the workspace are the library's header: they must be zero before the
+ *     first call (hipMemset once), are left zero by every call, and one workspace must only be used by one stream
+ *     at a time.  Words 64 .. 127 of the header are the arrival counters of the in-launch BatchNorm finish
+ *     (movae_fuse_t: fin_*); everything after the header is plain scratch with no state between calls;
  *   - return 0 on success, <0 on invalid argument (-1), unsupported shape (-2) or launch
  *     failure (-3); movae_last_error() gives the text for the calling thread.
  */

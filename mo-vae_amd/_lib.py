@@ -278,34 +278,14 @@ _workspaces = {}
 WS_BYTES = 96 << 20
 
 
-# Forking conv wgrad onto a second stream measured SLOWER on MI355X (C2 graph replay 2.42 ms vs 2.24 ms: the tiny
-# layers are launch/latency bound and the fork/join events cost more than the overlap wins) -> opt-in only.
-SIDE_STREAM_WGRAD = os.environ.get("MOVAE_SIDE_STREAM") == "fork"  # per-layer fork/join (measured slower; experiments)
-#: deferred weight gradients (ops.wgrad_side_stream) in the training loop: off by default -- eager streams overlap the two
-#: launches well (333 vs 462 us over the C2 layers) but a replayed hipGraph serialises its branches with extra cross-queue
-#: waits (C2 step 1.397 ms vs 1.357 ms); the paired launch (igemm2_pair) gets the overlap inside one kernel instead
-DEFER_WGRAD_DEFAULT = os.environ.get("MOVAE_SIDE_STREAM", "0") == "1"
-DEFER = None  # the active ops.wgrad_side_stream block, if any
-_side_streams = {}
-
-
-def side_stream(device):
-    """One forked HIP stream per device for launches that are independent of the main chain (conv wgrad)."""
-    key = (device.type, device.index)
-    s = _side_streams.get(key)
-    if s is None:
-        s = torch.cuda.Stream(device)
-        _side_streams[key] = s
-    return s
-
-
 def workspace(device, slot=0):
-    """Persistent per-device scratch (split-K slabs, reduction partials).  Stream-ordered reuse; `slot` 1 is the
-    side stream's own arena (a workspace serves one stream at a time)."""
+    """Persistent per-device scratch (split-K slabs, reduction partials).  Stream-ordered reuse; `slot` 2 and 3 are the
+    deferred reduces' arenas (defer_arm)."""
     key = (device.type, device.index, slot)
     ws = _workspaces.get(key)
     if ws is None:
-        # zero-filled: the first 4 KiB hold the in-launch hand-off counters (include/movae.h), which must start at zero
+        # zero-filled: the first 4 KiB are the workspace header (include/movae.h), which must start at zero; words 64 .. 127 of it
+        # are the arrival counters of the in-launch BatchNorm finish (fin_*)
         ws = torch.zeros(WS_BYTES, dtype=torch.uint8, device=device)
         _workspaces[key] = ws
     return ws

@@ -84,8 +84,7 @@ def _accumulate(p, g, taken=()):
                            "different tensor for it (the parameter feeds more than one node of this loss?): in-place accumulation "
                            "does not support shared weights")
     else:
-        ops.join_wgrad()  # both operands may still be in flight on the weight-gradient side stream
-        ops.flush_deferred()  # ... or wait in a parked split-K reduce (ops.deferred_reduces)
+        ops.flush_deferred()  # either operand may wait in a parked split-K reduce (ops.deferred_reduces)
         p.grad = p.grad + g
 
 
@@ -166,7 +165,6 @@ class JacobianBuffer:
                 dst = row[off: off + p.numel()]
                 self.copied.add(dst.data_ptr())
                 if g.data_ptr() != dst.data_ptr():  # already written in place through the sink
-                    ops.join_wgrad()
                     dst.copy_(_mem_flat(g))
 
 
@@ -384,7 +382,7 @@ def mtl_backward_begin(losses, features, aggregator, tasks_params=None, shared_p
         # task-side parameters an earlier loss already reached get this loss's gradient added inside the weight-gradient kernels
         ops.GRAD_ACCUM.clear()
         ops.GRAD_ACCUM_TAKEN.clear()
-        if i > 0 and ops.L.DEFER is None:
+        if i > 0:
             ops.GRAD_ACCUM.update({p.data_ptr(): p.grad for p in tp if p.grad is not None})
         ops.COT_SINK.clear()
         ops.COT_SINK.update({f.data_ptr(): c[i] for f, c in zip(st.feat_diff, cot) if c is not None})
@@ -392,11 +390,10 @@ def mtl_backward_begin(losses, features, aggregator, tasks_params=None, shared_p
         # and a destination the kernels know nobody reads before the optimizer: its split-K reduce may ride on a later launch)
         ops.GRAD_SINK.clear()
         owned = {}
-        if ops.L.DEFER is None:
-            for p in tp:
-                if p.grad is None:
-                    buf = ops.GRAD_SINK[p.data_ptr()] = _task_grad_buffer(p)
-                    owned[buf.data_ptr()] = p
+        for p in tp:
+            if p.grad is None:
+                buf = ops.GRAD_SINK[p.data_ptr()] = _task_grad_buffer(p)
+                owned[buf.data_ptr()] = p
         n_w, n_z = len(ops.SINK_LOG), len(ops.SINK_ZERO_LOG)
         try:
             with ops.deferred_reduces():
@@ -463,7 +460,6 @@ def _mtl_backward_finish(st):
             ops.GRAD_SINK.clear()
         jb.write_row(i, js)
     if shared_params:
-        ops.join_wgrad()  # the Jacobian rows are written by deferred weight-gradient launches
         jb.settle()
         _aggregate_into_grads(jb, st.aggregator)
 
@@ -491,7 +487,6 @@ def backward(tensors, aggregator, inputs=None, retain_graph=False, parallel_chun
     for i, t in enumerate(tensors):
         js = torch.autograd.grad(t, inputs, retain_graph=True, allow_unused=True)
         jb.write_row(i, js)
-    ops.join_wgrad()
     _aggregate_into_grads(jb, aggregator)
 
 
@@ -536,5 +531,4 @@ def backward_through(tensors, aggregator, inputs=None):
         for i, t in enumerate(tensors):
             js = torch.autograd.grad(t, inputs, retain_graph=True, allow_unused=True)
             jb.write_row(i, js)
-    ops.join_wgrad()
     _aggregate_into_grads(jb, aggregator)

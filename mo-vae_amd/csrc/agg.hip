@@ -11,7 +11,7 @@ namespace {
 constexpr int MAXK = MOVAE_MAX_K;
 // blocks of the streaming passes over J (gram_partial, combine, similarity): one per 2048 columns, at most MOVAE_GRAM_BLOCKS
 inline int gram_blocks(size_t m) {
-    static const size_t cap = getenv("MOVAE_GRAM_BLOCKS") ? (size_t)atol(getenv("MOVAE_GRAM_BLOCKS")) : 1024;
+    static const size_t cap = (size_t)env_long("MOVAE_GRAM_BLOCKS", 1024);
     size_t g = (m + 2047) / 2048;
     return (int)(g > cap ? cap : (g < 1 ? 1 : g));
 }

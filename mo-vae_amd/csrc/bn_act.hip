@@ -233,8 +233,8 @@ inline Split4 make_split4(int rows, int c, int parts = 256) {
     const int cq = c / 4;
     s.CQB = pow2_ge(cq) < 256 ? pow2_ge(cq) : 256;
     s.RG = 256 / s.CQB;
-    static const int env_parts = getenv("MOVAE_BN_PARTS") ? atoi(getenv("MOVAE_BN_PARTS")) : 0;
-    static const int min_iter = getenv("MOVAE_BN_MINITER") ? atoi(getenv("MOVAE_BN_MINITER")) : 4;
+    static const int env_parts = env_long("MOVAE_BN_PARTS", 0);
+    static const int min_iter = env_long("MOVAE_BN_MINITER", 4);
     const int max_parts = env_parts > 0 ? env_parts : parts;
     int rpb = ceil_div(rows, max_parts);  // up to 4 partial blocks per CU keep enough 16-byte loads in flight
     rpb = ceil_div(rpb, s.RG) * s.RG;
@@ -245,10 +245,7 @@ inline Split4 make_split4(int rows, int c, int parts = 256) {
 }
 
 __global__ __launch_bounds__(256) void bn_stats_partial4(const float* __restrict__ y, double* __restrict__ part, int rows,
-                                                         int C, int CQB, int rows_per_block, unsigned* __restrict__ counter,
-                                                         float eps, float momentum, float* __restrict__ save_mean,
-                                                         float* __restrict__ save_rstd, float* __restrict__ running_mean,
-                                                         float* __restrict__ running_var, long long* __restrict__ nbt) {
+                                                         int C, int CQB, int rows_per_block) {
     __shared__ double sh[8 * 256];
     const int t = threadIdx.x, RG = 256 / CQB, cl = t % CQB, rg = t / CQB, CQ = C / 4;
     const long r0 = (long)blockIdx.x * rows_per_block, r1 = min((long)rows, r0 + rows_per_block);
@@ -279,45 +276,16 @@ __global__ __launch_bounds__(256) void bn_stats_partial4(const float* __restrict
                 part[((long)blockIdx.x * C + cq * 4 + j) * 2 + 1] = v[4 + j];
             }
     }
-    if (counter == nullptr || !arrive_last(counter, gridDim.x)) return;
-    // last block: one wave per channel folds the block partials (fp64) and publishes mean / rstd / running stats
-    if (nbt && t == 0) nbt[0] += 1;
-    const int lane = t & 63, nblk = gridDim.x;
-    for (int c = t >> 6; c < C; c += 4) {
-        double s = 0.0, q = 0.0;
-        for (int b = lane; b < nblk; b += 64) {
-            s += part[((long)b * C + c) * 2 + 0];
-            q += part[((long)b * C + c) * 2 + 1];
-        }
-        s = wave_sum(s);
-        q = wave_sum(q);
-        if (lane == 0) {
-            const double mean = s / rows;
-            double var = q / rows - mean * mean;
-            if (var < 0.0) var = 0.0;
-            save_mean[c] = (float)mean;
-            save_rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-            if (running_mean) {
-                const double unb = rows > 1 ? var * ((double)rows / (rows - 1)) : var;
-                running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-                running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-            }
-        }
-    }
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_partial4(const float* __restrict__ dout, const float* __restrict__ y,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        double* __restrict__ part, int rows, int C, int CQB,
-                                                       int rows_per_block, int act, float slope,
-                                                       unsigned* __restrict__ counter, float* __restrict__ sums,
-                                                       BnOut tab, int accumulate, long gstride) {
+                                                       int rows_per_block, int act, float slope, long gstride) {
     __shared__ double sh[8 * 256];
     dout += (long)blockIdx.y * gstride;                  // cotangent group; y and the statistics are shared
-    part += (long)blockIdx.y * gridDim.x * C * 2;
-    float* __restrict__ dgamma = tab.dgamma[blockIdx.y];
-    float* __restrict__ dbeta = tab.dbeta[blockIdx.y];
+    part += ((long)blockIdx.y * gridDim.x + blockIdx.x) * C * 2;  // this block's row of partials
     const int t = threadIdx.x, RG = 256 / CQB, cl = t % CQB, rg = t / CQB, CQ = C / 4;
     const long r0 = (long)blockIdx.x * rows_per_block, r1 = min((long)rows, r0 + rows_per_block);
     for (int cb = 0; cb < CQ; cb += CQB) {
@@ -351,26 +319,9 @@ __global__ __launch_bounds__(256) void bn_bwd_partial4(const float* __restrict__
         if (rg == 0 && cq < CQ)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                part[((long)blockIdx.x * C + cq * 4 + j) * 2 + 0] = v[j];
-                part[((long)blockIdx.x * C + cq * 4 + j) * 2 + 1] = v[4 + j];
+                part[(cq * 4 + j) * 2 + 0] = v[j];
+                part[(cq * 4 + j) * 2 + 1] = v[4 + j];
             }
-    }
-    if (counter == nullptr || !arrive_last(counter, gridDim.x)) return;
-    const int lane = t & 63, nblk = gridDim.x;
-    for (int c = t >> 6; c < C; c += 4) {
-        double s = 0.0, q = 0.0;
-        for (int b = lane; b < nblk; b += 64) {
-            s += part[((long)b * C + c) * 2 + 0];
-            q += part[((long)b * C + c) * 2 + 1];
-        }
-        s = wave_sum(s);
-        q = wave_sum(q);
-        if (lane == 0) {
-            sums[2 * c + 0] = (float)(s / rows);
-            sums[2 * c + 1] = (float)(q / rows);
-            if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
-            if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s : (float)s;
-        }
     }
 }
 
@@ -634,7 +585,7 @@ inline const float* fold_partials(const float* part, size_t cap_floats, int* par
     const int nb = 64;
     // (the finalize kernels take a 256-thread block per channel: up to 2048 partials -- 8 strided pairs per thread -- cost less than
     // a fold launch and its dependent kernel boundary)
-    static const int fold_above = getenv("MOVAE_BN_FOLD_ABOVE") ? atoi(getenv("MOVAE_BN_FOLD_ABOVE")) : 2048;
+    static const int fold_above = env_long("MOVAE_BN_FOLD_ABOVE", 2048);
     if (P <= fold_above || (size_t)groups * P * E + (size_t)groups * nb * E > cap_floats) return part;
     float* dst = const_cast<float*>(part) + (size_t)groups * P * E;
     hipLaunchKernelGGL(bn_partials_fold_k, dim3(nb, groups), dim3(256), 0, st, part, P, E, dst);
@@ -778,21 +729,13 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_k(const float* __restrict__ 
 }
 
 inline int small_rows() {  // MOVAE_BN_SMALL_ROWS: largest row count served by the one-launch kernels (0 disables them)
-    static const int v = getenv("MOVAE_BN_SMALL_ROWS") ? atoi(getenv("MOVAE_BN_SMALL_ROWS")) : 1024;
+    static const int v = env_long("MOVAE_BN_SMALL_ROWS", 1024);
     return v < 1024 ? v : 1024;  // the kernels hold the whole column in registers: 4 rows per thread
 }
 
 inline int grid_for(long total) {
     long g = (total + 255) / 256;
     return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
-}
-
-// The "last block folds the partials" variant (arrive_last) is kept for experiments only: measured on MI355X
-// it is SLOWER than a second tiny launch for these kernels (C2 step 3.2 ms vs 2.25 ms) because every block pays
-// an agent-scope release (L2 write-back) while the conv outputs are still dirty in L2.  MOVAE_INLAUNCH=1 enables it.
-inline bool in_launch_final() {
-    static const bool v = getenv("MOVAE_INLAUNCH") != nullptr;
-    return v;
 }
 
 inline bool al16(const void* a, const void* b = nullptr, const void* c = nullptr) {
@@ -824,27 +767,21 @@ int movae_bn_act_fwd(const float* y, const float* gamma, const float* beta, floa
     }
     if (training) {
         MOVAE_CHECK_ARG(ws && ws_bytes >= movae_bn_ws_bytes(rows, c), "movae_bn_act_fwd: workspace too small");
-        unsigned* counter = static_cast<unsigned*>(ws);
         double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + MOVAE_WS_HEADER_BYTES);
         int nblk;
         if (c % 4 == 0 && al16(y)) {
             const Split4 s = make_split4(rows, c);
-            hipLaunchKernelGGL(bn_stats_partial4, dim3(s.nblk), dim3(256), 0, st, y, part, rows, c, s.CQB, s.rows_per_block,
-                               in_launch_final() ? counter : nullptr, eps, momentum, save_mean, save_rstd, running_mean,
-                               running_var, nbt);
-            MOVAE_CHECK_LAUNCH("bn_stats_partial4");
-            nblk = in_launch_final() ? 0 : s.nblk;  // 0: statistics finished in-launch by the last block
+            nblk = s.nblk;
+            hipLaunchKernelGGL(bn_stats_partial4, dim3(s.nblk), dim3(256), 0, st, y, part, rows, c, s.CQB, s.rows_per_block);
         } else {
             const Split s = make_split(rows, c);
             nblk = s.nblk;
             hipLaunchKernelGGL(bn_stats_partial, dim3(s.nblk), dim3(256), 0, st, y, part, rows, c, s.CB, s.rows_per_block);
         }
         MOVAE_CHECK_LAUNCH("bn_stats_partial");
-        if (nblk > 0) {
-            hipLaunchKernelGGL(bn_stats_final, dim3(c), dim3(64), 0, st, part, nblk, rows, c, eps, momentum, save_mean,
-                               save_rstd, running_mean, running_var, nbt);
-            MOVAE_CHECK_LAUNCH("bn_stats_final");
-        }
+        hipLaunchKernelGGL(bn_stats_final, dim3(c), dim3(64), 0, st, part, nblk, rows, c, eps, momentum, save_mean, save_rstd,
+                           running_mean, running_var, nbt);
+        MOVAE_CHECK_LAUNCH("bn_stats_final");
     } else {
         MOVAE_CHECK_ARG(running_mean && running_var, "movae_bn_act_fwd: eval mode needs running statistics");
         hipLaunchKernelGGL(bn_eval_prepare, dim3(ceil_div(c, 128)), dim3(128), 0, st, running_mean, running_var, eps,
@@ -886,19 +823,15 @@ int movae_bn_act_bwd_grouped(int groups, const float* dout, const float* y, cons
     }
     MOVAE_CHECK_ARG(ws && ws_bytes >= MOVAE_WS_HEADER_BYTES + (size_t)groups * (movae_bn_ws_bytes(rows, c) - MOVAE_WS_HEADER_BYTES),
                     "movae_bn_act_bwd: workspace too small");
-    unsigned* counter = static_cast<unsigned*>(ws);
     double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + MOVAE_WS_HEADER_BYTES);
     if (vec) {
         const Split4 s = make_split4(rows, c, groups == 1 ? 1024 : 512);
-        const bool fold = in_launch_final() && groups == 1;
         float* sums = reinterpret_cast<float*>(part + (size_t)groups * s.nblk * c * 2);
         hipLaunchKernelGGL(bn_bwd_partial4, dim3(s.nblk, groups), dim3(256), 0, st, dout, y, gamma, beta, save_mean, save_rstd, part,
-                           rows, c, s.CQB, s.rows_per_block, act, slope, fold ? counter : nullptr, sums, tab, accumulate, total);
+                           rows, c, s.CQB, s.rows_per_block, act, slope, total);
         MOVAE_CHECK_LAUNCH("bn_bwd_partial");
-        if (!fold) {
-            hipLaunchKernelGGL(bn_bwd_final, dim3(c, groups), dim3(64), 0, st, part, s.nblk, rows, c, sums, tab, accumulate);
-            MOVAE_CHECK_LAUNCH("bn_bwd_final");
-        }
+        hipLaunchKernelGGL(bn_bwd_final, dim3(c, groups), dim3(64), 0, st, part, s.nblk, rows, c, sums, tab, accumulate);
+        MOVAE_CHECK_LAUNCH("bn_bwd_final");
         hipLaunchKernelGGL(bn_bwd_apply4, dim3(grid_for(total / 16), groups), dim3(256), 0, st, dout, y, gamma, beta, save_mean,
                            save_rstd, sums, dy, total, c, act, slope);
         MOVAE_CHECK_LAUNCH("bn_bwd_apply");
@@ -991,7 +924,7 @@ int movae_bn_bwd_finalize_apply(const float* bn_part, size_t bn_cap, int ppg, in
     MOVAE_CHECK_ARG(ppg > 0 && rows > 0 && rows <= 0x7fffffffUL && c > 0 && groups >= 1 && groups <= MAX_GROUPS,
                     "movae_bn_bwd_finalize_apply: bad shape");
     MOVAE_CHECK_ARG(c % 4 == 0 && al16(dout, y, dy) && al16(scale, shift, coef), "movae_bn_bwd_finalize_apply: needs c %% 4 == 0 and aligned operands");
-    static const int fuse_below = getenv("MOVAE_BN_BWD_FUSE_PARTS") ? atoi(getenv("MOVAE_BN_BWD_FUSE_PARTS")) : 256;
+    static const int fuse_below = env_long("MOVAE_BN_BWD_FUSE_PARTS", 256);
     if (ppg > fuse_below) {  // many partials: every block folding them again costs more than the finalize launch
         if (int rc = movae_bn_bwd_finalize(bn_part, bn_cap, ppg, groups, (int)rows, c, gamma, save_mean, save_rstd, dgamma, dbeta, coef,
                                            accumulate, stream))

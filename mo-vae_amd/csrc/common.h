@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/movae.h"
 
@@ -35,6 +36,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// an environment switch / tuning threshold: its value where set, else the default (INTEGRATION.md lists every name)
+static inline long env_long(const char* name, long dflt) {
+    const char* v = getenv(name);
+    return v ? atol(v) : dflt;
+}
+static inline double env_double(const char* name, double dflt) {
+    const char* v = getenv(name);
+    return v ? atof(v) : dflt;
+}
 
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
     switch (act) {
@@ -68,16 +79,12 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// ---- in-launch "last block finishes" hand-off ---------------------------------------------------------
-// Two-stage reductions write per-block partials and let the LAST block to arrive fold them, instead of a
-// second launch (a dependent kernel boundary costs ~1.5-2 us plus the tiny kernel itself).  Placement
-// independent: every storing wave drains its stores, one lane publishes with an agent-scope release before
-// the ticket, the last arriver takes an agent-scope acquire before any wave of its block reads the partials
-// (cdna_hip_programming.md Guideline 16, counter form).  The counter word lives in the caller's workspace
-// header (MOVAE_WS_HEADER_BYTES, zero on first use) and is re-armed to zero by the last block.
+// ---- workspace header ----------------------------------------------------------------------------------
+// The first MOVAE_WS_HEADER_BYTES of a caller's workspace are reserved and zero on first use.  Words 64 .. 127 are the arrival
+// counters of the in-launch BatchNorm finish (kgemm.h: fin_*), one per column tile, re-armed to zero by the last block.
 #define MOVAE_WS_HEADER_BYTES 4096
 
-// plain-scratch users skip the counter header so it stays zero between the launches that use it
+// plain-scratch users skip the header so it stays zero between the launches that use it
 #define MOVAE_WS_SCRATCH(ws, ws_bytes)                                         \
     do {                                                                       \
         if ((ws) && (ws_bytes) > (size_t)MOVAE_WS_HEADER_BYTES) {              \
@@ -88,27 +95,6 @@ __device__ __forceinline__ float wave_sum(float v) {
             (ws_bytes) = 0;                                                    \
         }                                                                      \
     } while (0)
-
-__device__ __forceinline__ bool arrive_last(unsigned* counter, unsigned nblk) {
-    __shared__ unsigned s_last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned last = ticket == nblk - 1 ? 1u : 0u;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    return s_last != 0;
-}
-
 
 // Philox4x32-10 (Salmon et al., SC'11; the counter-based generator family torch / cuRAND / rocRAND use): four 32-bit words of
 // counter (c0..c3) under key (k0, k1).  Shared by the reparameterisation draws (eltwise.hip) and the attention dropout mask

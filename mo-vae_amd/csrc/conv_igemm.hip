@@ -898,7 +898,7 @@ int g_compute_bf16 = 0;          // movae_set_compute_dtype(): 1 = bf16 operands
 int g_force_kgemm = 0;           // movae_bench_force_kgemm(): 1 = every shape kgemm.h can serve takes it, -1 = none does (tests, A/B)
 
 inline long reduce_vec_min() {  // outputs from which the 16-byte reduce serves 8 <= S < 64 (tuning knob)
-    static const long v = getenv("MOVAE_REDUCE_VEC_MIN") ? atol(getenv("MOVAE_REDUCE_VEC_MIN")) : (1L << 19);
+    static const long v = env_long("MOVAE_REDUCE_VEC_MIN", 1L << 19);
     return v;
 }
 
@@ -949,8 +949,8 @@ inline int defer_flush() {
 // a parked reduce is a few blocks' work in a launch built for something else (its occupancy, not the reduce's): the size gates.
 // Paired launches (100-130 registers, 3-4 blocks per CU) carry more than the tiled 3-D ones (33 MB of slabs behind a 185 us
 // igemm2_bwd<128,64> cost it 49 us).  A reduce its next carrier refuses is launched stand-alone by that carrier's call.
-static size_t g_defer_max_bytes = getenv("MOVAE_DEFER_MAX_BYTES") ? (size_t)atol(getenv("MOVAE_DEFER_MAX_BYTES")) : (size_t)(12u << 20);
-static size_t g_defer_max_bytes_pair = getenv("MOVAE_DEFER_MAX_BYTES_PAIR") ? (size_t)atol(getenv("MOVAE_DEFER_MAX_BYTES_PAIR")) : (size_t)(12u << 20);
+static size_t g_defer_max_bytes = (size_t)env_long("MOVAE_DEFER_MAX_BYTES", 12L << 20);
+static size_t g_defer_max_bytes_pair = (size_t)env_long("MOVAE_DEFER_MAX_BYTES_PAIR", 12L << 20);
 inline size_t defer_max_bytes() { return g_defer_max_bytes; }
 inline size_t defer_max_bytes_pair() { return g_defer_max_bytes_pair; }
 
@@ -1089,8 +1089,6 @@ inline int choose_split(int form, int tile_area, int bk, long tiles, int nk, siz
     long smax = nk < 256 ? nk : 256;
     while (smax > 1 && per_slab_bytes * (size_t)smax > ws_bytes) --smax;
     if (g_force_split > 0) return (int)(g_force_split < smax ? g_force_split : smax);  // movae_bench_force_split()
-    static const int legacy_tiles = getenv("MOVAE_SPLIT_TILES") ? atoi(getenv("MOVAE_SPLIT_TILES")) : -1;
-    if (legacy_tiles >= 0 && tiles > legacy_tiles) return 1;
     const bool big = tile_area >= 128 * 128;
     const double form_tk = form == FORM_FWD ? 1.0 : (form == FORM_BWD ? 1.25 : 0.9);
     const double tk = form_tk * (tile_area / 4096.0) * (big ? 0.83 : 1.0) * (bk / 32.0);
@@ -1131,7 +1129,7 @@ inline bool is_linear(const Geom& g) {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline long big_tile_min() {  // minimum number of 128x128 work items before the big tile is preferred
-    static const long v = getenv("MOVAE_BIG_TILE_MIN") ? atol(getenv("MOVAE_BIG_TILE_MIN")) : 256;
+    static const long v = env_long("MOVAE_BIG_TILE_MIN", 256);
     return v;
 }
 
@@ -1721,7 +1719,6 @@ static int pair_calls(bool transposed, int groups, const float* dy, const float*
     v2::g_pending.active = false;
     kg::g_kpend.active = false;
     lin::g_lin_pend.active = false;
-    thin::g_thin_pend.active = false;
     v2::g_pair_collect = enabled;
     g_fuse = FuseCtx();
     fuse_bn_install(const_cast<movae_fuse_t*>(fuse), groups);  // (the dgrad's plan -- also a stashed one -- keeps what it claimed)
@@ -1734,8 +1731,7 @@ static int pair_calls(bool transposed, int groups, const float* dy, const float*
         v2::g_pending.active = false;
         kg::g_kpend.active = false;
         lin::g_lin_pend.active = false;
-        thin::g_thin_pend.active = false;
-        return rc;
+            return rc;
     }
     size_t used = v2::g_pending.active ? (v2::g_pending.ws_used + 255) / 256 * 256 : 0;
     if (v2::g_pending.active && (!ws || used + (32u << 20) > ws_bytes)) {  // no room left for the wgrad's slabs next to the dgrad's
@@ -1756,11 +1752,7 @@ static int pair_calls(bool transposed, int groups, const float* dy, const float*
         const int rc2 = lin::lin_flush((hipStream_t)stream);
         if (!rc) rc = rc2;
     }
-    if (thin::g_thin_pend.active) {  // likewise a thin-channel input gradient
-        const int rc2 = thin::thin_flush((hipStream_t)stream);
-        if (!rc) rc = rc2;
-    }
-    if (strncmp(g_last_kernel, "igemm2_pair", 11) != 0 && strncmp(g_last_kernel, "kpair_k", 7) != 0 && strncmp(g_last_kernel, "linear_bwd_k", 12) != 0 && strncmp(g_last_kernel, "thin_pair_k", 11) != 0) {  // two main launches: movae_bench_last_kernel() names both
+    if (strncmp(g_last_kernel, "igemm2_pair", 11) != 0 && strncmp(g_last_kernel, "kpair_k", 7) != 0 && strncmp(g_last_kernel, "linear_bwd_k", 12) != 0) {  // two main launches: movae_bench_last_kernel() names both
         static thread_local char both[128];
         snprintf(both, sizeof(both), "%s + %s", dgrad_kernel, g_last_kernel);
         g_last_kernel = both;

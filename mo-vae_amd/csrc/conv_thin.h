@@ -209,29 +209,12 @@ __global__ __launch_bounds__(256) void thin_in_k(const float* __restrict__ X, co
 // (3 floats per pixel: lanes are consecutive pixels, stride 3 or 6 floats): address = pixel corner + a lane-half constant per step.
 // ~30x less LDS traffic than the VALU form; K / 2 MFMAs per 32 pixels.  A block owns 256 consecutive output pixels of one image --
 // whole rows or a row segment (host) -- and leaves through thin_in_tile_out like thin_in_k.  BWD: stride 1 only.
-struct ThinInArgs {  // thin_in_mfma_k's arguments (a paired launch carries them as one struct)
-    const float* X;
-    const float* W;
-    const float* bias;
-    float* Y;
-    Geom g;
-    int M, act;
-    float slope;
-    float* stats;
-    BnBwd bb;
-    ActMul am;
-    int ncols, RH, RW;
-    FastDiv fd_row, fd3, fd_ncols, fd_hw, fd_wo;
-    int gx, gy;        // the launch's grid
-    unsigned lds_bytes;
-};
-
 template <int KH, int KW, bool BWD>
-__device__ __forceinline__ void thin_in_mfma_body(const float* __restrict__ X, const float* __restrict__ W,
-                                                  const float* __restrict__ bias, float* __restrict__ Y, const Geom& g, int M, int act,
-                                                  float slope, float* __restrict__ stats, const BnBwd& bb, const ActMul& am, int ncols, int RH,
-                                                  int RW, FastDiv fd_row, FastDiv fd3, FastDiv fd_ncols, FastDiv fd_hw, FastDiv fd_wo, int bx,
-                                                  int by) {
+__global__ __launch_bounds__(256) void thin_in_mfma_k(const float* __restrict__ X, const float* __restrict__ W,
+                                                      const float* __restrict__ bias, float* __restrict__ Y, Geom g, int M, int act,
+                                                      float slope, float* __restrict__ stats, BnBwd bb, ActMul am, int ncols, int RH,
+                                                      int RW, FastDiv fd_row, FastDiv fd3, FastDiv fd_ncols, FastDiv fd_hw, FastDiv fd_wo) {
+    const int bx = blockIdx.x, by = blockIdx.y;
     constexpr int TC = 3, TAPS = KH * KW, K = TAPS * TC, KS = (K + 1) / 2;
     extern __shared__ __attribute__((aligned(16))) float Wl[];  // input region [RH][RW * 3], then the output tile [256][33]
     const int t = threadIdx.x, lane = t & 63, half = lane >> 5, l31 = lane & 31, wave = t >> 6;
@@ -319,15 +302,6 @@ __device__ __forceinline__ void thin_in_mfma_body(const float* __restrict__ X, c
     // (Loading the ActMul factor's source ahead of the staging / MFMA phase was measured slower: 32 more registers, three waves per SIMD,
     // 211 vs 176 us on the C5 layer.)
     thin_in_tile_out(Wl, Y, M, t, stats, bb, am, N, n0, bx);
-}
-
-template <int KH, int KW, bool BWD>
-__global__ __launch_bounds__(256) void thin_in_mfma_k(const float* __restrict__ X, const float* __restrict__ W,
-                                                      const float* __restrict__ bias, float* __restrict__ Y, Geom g, int M, int act,
-                                                      float slope, float* __restrict__ stats, BnBwd bb, ActMul am, int ncols, int RH,
-                                                      int RW, FastDiv fd_row, FastDiv fd3, FastDiv fd_ncols, FastDiv fd_hw, FastDiv fd_wo) {
-    thin_in_mfma_body<KH, KW, BWD>(X, W, bias, Y, g, M, act, slope, stats, bb, am, ncols, RH, RW, fd_row, fd3, fd_ncols, fd_hw, fd_wo,
-                                   blockIdx.x, blockIdx.y);
 }
 
 // ---- thin output side (FWD gather) -----------------------------------------------------------------
@@ -1025,21 +999,6 @@ __global__ __launch_bounds__(256) void thin_wgrad_sweep_k(const float* __restric
 // MFMAs where the sweep kernel issued (1 + TAPS) reads per TAPS * TC FMAs and was bound by the LDS return bandwidth of its
 // broadcast ds_read_b128 (C5 first layer, 4x4 taps: 217 us for 92 MB of operands).  Same tiling, staging, slab row per block and
 // deterministic reduce as the sweep kernel; the four waves take every fourth pixel pair and fold through LDS.
-struct ThinWgArgs {  // thin_wgrad_mfma_k's arguments (a paired launch carries them as one struct)
-    const float* Wide;
-    const float* Thin;
-    float* slab;
-    int Hw, Ww, Cw, Ht, Wt, stride, pad, TH, TW, tiles_h, tiles_w, Cs, Cb;
-    long wide_gs, thin_gs, slab_gs;
-    Norm nrm;
-    int ntiles;
-    FastDiv fd_tw, fd_bw;
-    int cs_on;
-    long row_stride;
-    int gx, gy, gz;    // the launch's grid
-    unsigned lds_bytes;
-};
-
 template <int TC, int KH, int KW, bool REV>
 __device__ __forceinline__ void thin_wgrad_mfma_body(const float* __restrict__ Wide, const float* __restrict__ Thin,
                                                      float* __restrict__ slab, int Hw, int Ww, int Cw, int Ht, int Wt,
@@ -1221,6 +1180,7 @@ __device__ __forceinline__ void thin_wgrad_mfma_body(const float* __restrict__ W
     }
 }
 
+// (the body stays a function of its own: folded into the kernel it compiles to one more AGPR at <3, 4, 4, false>)
 template <int TC, int KH, int KW, bool REV>
 __global__ __launch_bounds__(256) void thin_wgrad_mfma_k(const float* __restrict__ Wide, const float* __restrict__ Thin,
                                                          float* __restrict__ slab, int Hw, int Ww, int Cw, int Ht, int Wt,
@@ -1232,58 +1192,8 @@ __global__ __launch_bounds__(256) void thin_wgrad_mfma_k(const float* __restrict
                                           blockIdx.z, gridDim.x);
 }
 
-// The last conv's backward in ONE launch (a 3-channel output: its input gradient is thin_in_mfma_k's BWD form, its weight gradient
-// thin_wgrad_mfma_k): blocks [0, nw) the weight gradient's persistent blocks (the longer ones: dispatched first), the rest the
-// input gradient's.  The two share read-only operands only; one dynamic LDS allocation, the larger of the two needs.
-template <int K, bool REVV>
-__global__ __launch_bounds__(256) void thin_pair_k(ThinInArgs d, ThinWgArgs w, int nw) {
-    int b = blockIdx.x;
-    if (b < nw) {
-        const int bx = b % w.gx, r = b / w.gx;
-        thin_wgrad_mfma_body<3, K, K, REVV>(w.Wide, w.Thin, w.slab, w.Hw, w.Ww, w.Cw, w.Ht, w.Wt, w.stride, w.pad, w.TH, w.TW, w.tiles_h,
-                                            w.tiles_w, w.Cs, w.Cb, w.wide_gs, w.thin_gs, w.slab_gs, w.nrm, w.ntiles, w.fd_tw, w.fd_bw,
-                                            w.cs_on, w.row_stride, bx, r % w.gy, r / w.gy, w.gx);
-    } else {
-        b -= nw;
-        thin_in_mfma_body<K, K, true>(d.X, d.W, d.bias, d.Y, d.g, d.M, d.act, d.slope, d.stats, d.bb, d.am, d.ncols, d.RH, d.RW, d.fd_row,
-                                      d.fd3, d.fd_ncols, d.fd_hw, d.fd_wo, b % d.gx, b / d.gx);
-    }
-}
-
-// an input gradient of the thin MFMA form planned inside a dgrad + wgrad call (v2::g_pair_collect), waiting for its weight gradient
-struct ThinPending {
-    bool active = false;
-    int k = 3;
-    ThinInArgs d;
-};
-static thread_local ThinPending g_thin_pend;
-
 // ---- host side ---------------------------------------------------------------------------------------
 inline bool thin_in_ok(const Geom& g) { return g.Cr <= 4 && g.Nn >= 8 && g.KH * g.KW * g.Cr * 64 * 4 <= 48 * 1024; }
-
-// MOVAE_THIN_PAIR=1: the last conv's input gradient and weight gradient in one launch (thin_pair_k).  OFF by default: measured level
-// at C1-C4 (C2 0.766 vs 0.762 ms, C1 0.576 vs 0.579) and 1.3 % slower at C5 (5.49 vs 5.42 ms: the pair takes the larger of the two
-// LDS needs for every block, and these two HBM-bound kernels do not overlap the way two latency-bound ones do).
-inline bool thin_pair_on() {
-    static const bool v = getenv("MOVAE_THIN_PAIR") && atoi(getenv("MOVAE_THIN_PAIR")) != 0;
-    return v;
-}
-
-inline int thin_flush(hipStream_t st) {  // the weight gradient took another kernel: the planned input gradient goes alone
-    ThinPending& p = g_thin_pend;
-    if (!p.active) return MOVAE_OK;
-    p.active = false;
-    const ThinInArgs& d = p.d;
-    const dim3 grid(d.gx, d.gy);
-    if (p.k == 3)
-        hipLaunchKernelGGL((thin_in_mfma_k<3, 3, true>), grid, dim3(256), d.lds_bytes, st, d.X, d.W, d.bias, d.Y, d.g, d.M, d.act, d.slope,
-                           d.stats, d.bb, d.am, d.ncols, d.RH, d.RW, d.fd_row, d.fd3, d.fd_ncols, d.fd_hw, d.fd_wo);
-    else
-        hipLaunchKernelGGL((thin_in_mfma_k<4, 4, true>), grid, dim3(256), d.lds_bytes, st, d.X, d.W, d.bias, d.Y, d.g, d.M, d.act, d.slope,
-                           d.stats, d.bb, d.am, d.ncols, d.RH, d.RW, d.fd_row, d.fd3, d.fd_ncols, d.fd_hw, d.fd_wo);
-    MOVAE_CHECK_LAUNCH("thin_in_mfma (unpaired input gradient)");
-    return MOVAE_OK;
-}
 
 template <bool BWD>
 int launch_thin_in(const float* X, const float* W, float* Y, const Geom& g, const Epilogue& ep, hipStream_t st) {
@@ -1322,14 +1232,6 @@ int launch_thin_in(const float* X, const float* W, float* Y, const Geom& g, cons
     }
     if (mfma) {
         grid.y = g.Nn / 32;
-        if (BWD && v2::g_pair_collect && thin_pair_on()) {  // inside a dgrad + wgrad call: planned, launched with the weight gradient (thin_pair_k)
-            ThinPending& p = g_thin_pend;
-            p.active = true, p.k = k33 ? 3 : 4;
-            p.d = ThinInArgs{X, W, ep.bias, Y, g, M, ep.act, ep.slope, stats, bb, am, ncols, RH, RW, fastdiv_make(RW * 3), fastdiv_make(3),
-                             fastdiv_make(ncols), fastdiv_make(hw), fastdiv_make(g.Wo), (int)grid.x, (int)grid.y,
-                             (unsigned)(lf * sizeof(float))};
-            return MOVAE_OK;
-        }
 #define MOVAE_TI(K)                                                                                                                \
     hipLaunchKernelGGL((thin_in_mfma_k<K, K, BWD>), grid, dim3(256), lf * sizeof(float), st, X, W, ep.bias, Y, g, M, ep.act, ep.slope,  \
                        stats, bb, am, ncols, RH, RW, fastdiv_make(RW * 3), fastdiv_make(3), fastdiv_make(ncols), fastdiv_make(hw),  \
@@ -1376,7 +1278,7 @@ inline bool thin_out_tile_plan(const Geom& g, const float* X, int& TH, int& TW, 
     if (TW < 1) return false;
     // two pixels per thread halve the weight reads per FMA but also the block count (measured: better from ~200k pixels)
     const long px_total = (long)g.Nimg * g.Ho * g.Wo;
-    static const int force_ppt = getenv("MOVAE_THIN_PPT") ? atoi(getenv("MOVAE_THIN_PPT")) : 0;  // tuning knob
+    static const int force_ppt = env_long("MOVAE_THIN_PPT", 0);  // tuning knob
     for (int ppt = force_ppt ? force_ppt : (px_total >= 200000L ? 2 : 1); ppt >= 1; --ppt) {
         int th = 256 * ppt / TW;
         if (BWD) th = th / 2 * 2;
@@ -1482,7 +1384,7 @@ int launch_thin_wgrad_impl(const float* S, const float* Bg, float* const* dW, in
             const int Hw = thin_small ? g.Hb : g.Hs, Ww = thin_small ? g.Wb : g.Ws;
             const int Ht = thin_small ? g.Hs : g.Hb, Wt = thin_small ? g.Ws : g.Wb;
             const int TW = Ww < 32 ? Ww : 32;
-            static const int tile_px = getenv("MOVAE_THIN_TILE_PX") ? atoi(getenv("MOVAE_THIN_TILE_PX")) : 256;
+            static const int tile_px = env_long("MOVAE_THIN_TILE_PX", 256);
             int TH = tile_px / TW;
             if (TH < 1) TH = 1;
             if (TH > Hw) TH = Hw;
@@ -1513,7 +1415,7 @@ int launch_thin_wgrad_impl(const float* S, const float* Bg, float* const* dW, in
             const long ntiles = (long)g.Nimg * tiles_h * tiles_w;
             // MFMA kernel: persistent blocks (one slab row each), about four per CU and (wide slice, group)
             // (three blocks of the MFMA kernel fit a CU -- 136 VGPRs + 16 accumulators per lane: 768 persistent blocks fill the chip once)
-            static const int persist = getenv("MOVAE_THIN_PERSIST") ? atoi(getenv("MOVAE_THIN_PERSIST")) : 768;
+            static const int persist = env_long("MOVAE_THIN_PERSIST", 768);
             long nblk = ntiles;
             if (use_mfma) {
                 const long cap = persist / ((long)(wide / 32) * G) > 64 ? persist / ((long)(wide / 32) * G) : 64;
@@ -1523,7 +1425,7 @@ int launch_thin_wgrad_impl(const float* S, const float* Bg, float* const* dW, in
             // (from 256 k pixels: the three extra floats per slab row take the reduce off its 16-byte path, +5 us at C2's last conv,
             // but the stand-alone column sum it saves is two launches there -- C2 0.822 -> 0.801 ms; C5's last conv: 34 us saved;
             // at C1's 128 k pixels the two are level)
-            static const long cs_min = getenv("MOVAE_THIN_CS_MIN") ? atol(getenv("MOVAE_THIN_CS_MIN")) : (1L << 18);
+            static const long cs_min = env_long("MOVAE_THIN_CS_MIN", 1L << 18);
             bool cs_on = use_mfma && thin_small && colsum && g.Hs == g.Hb && g.Ws == g.Wb && (long)K >= cs_min;
             for (int i = 0; cs_on && i < G; ++i) cs_on = colsum[i] != nullptr;
             const long row = (long)M * N + (cs_on ? M : 0);  // floats per slab row
@@ -1552,19 +1454,7 @@ int launch_thin_wgrad_impl(const float* S, const float* Bg, float* const* dW, in
     hipLaunchKernelGGL((thin_wgrad_mfma_k<3, K, K, REVV>), grid, dim3(256), shb, st, Wd, Tn, slab, Hw, Ww, wide, Ht, Wt, g.stride, \
                        g.pad, TH, TW, tiles_h, tiles_w, g.Cs, g.Cb, wide_gs, thin_gs, slab_gs, wide_nrm, (int)ntiles, fastdiv_make(TW),    \
                        fastdiv_make(thin_small ? TW + g.KW - 1 : (TW - 1) * g.stride + g.KW), cs_on ? 1 : 0, row)
-                if (use_mfma && thin_small && g_thin_pend.active && g_thin_pend.k == (k33 ? 3 : 4)) {
-                    // the layer's input gradient waits: one launch for both (thin_pair_k)
-                    g_thin_pend.active = false;
-                    const ThinInArgs& d = g_thin_pend.d;
-                    const ThinWgArgs w{Wd, Tn, slab, Hw, Ww, wide, Ht, Wt, g.stride, g.pad, TH, TW, tiles_h, tiles_w, g.Cs, g.Cb, wide_gs, thin_gs,
-                                       slab_gs, wide_nrm, (int)ntiles, fastdiv_make(TW), fastdiv_make(TW + g.KW - 1), cs_on ? 1 : 0, row,
-                                       (int)grid.x, (int)grid.y, (int)grid.z, (unsigned)shb};
-                    const int nw = (int)(grid.x * grid.y * grid.z), nd = d.gx * d.gy;
-                    const unsigned lds = d.lds_bytes > (unsigned)shb ? d.lds_bytes : (unsigned)shb;
-                    if (k33) hipLaunchKernelGGL((thin_pair_k<3, true>), dim3(nw + nd), dim3(256), lds, st, d, w, nw);
-                    else hipLaunchKernelGGL((thin_pair_k<4, true>), dim3(nw + nd), dim3(256), lds, st, d, w, nw);
-                    g_last_kernel = k33 ? "thin_pair_k<3,true>" : "thin_pair_k<4,true>";
-                } else if (use_mfma) {
+                if (use_mfma) {
                     if (thin_small) {
                         if (k33) MOVAE_MF(3, true); else MOVAE_MF(4, true);
                     } else {

@@ -150,8 +150,7 @@ __global__ __launch_bounds__(256) void colsum_partial(const float* __restrict__ 
 
 // 16-byte variant: a thread owns one 4-channel quad (C % 4 == 0), a wave reads 1 KiB contiguous
 __global__ __launch_bounds__(256) void colsum_partial4(const float* __restrict__ x, double* __restrict__ part, int rows,
-                                                       int C, int CQB, int rows_per_block, unsigned* __restrict__ counter,
-                                                       float* __restrict__ out, int accumulate) {
+                                                       int C, int CQB, int rows_per_block) {
     __shared__ double sh[4 * 256];
     const int t = threadIdx.x, RG = 256 / CQB, cl = t % CQB, rg = t / CQB, CQ = C / 4;
     const long r0 = (long)blockIdx.x * rows_per_block, r1 = min((long)rows, r0 + rows_per_block);
@@ -176,14 +175,6 @@ __global__ __launch_bounds__(256) void colsum_partial4(const float* __restrict__
 #pragma unroll
             for (int j = 0; j < 4; ++j) part[(long)blockIdx.x * C + cq * 4 + j] = v[j];
         }
-    }
-    if (counter == nullptr || !arrive_last(counter, gridDim.x)) return;
-    const int lane = t & 63, nblk = gridDim.x;  // last block: one wave per column folds the partials
-    for (int c = t >> 6; c < C; c += 4) {
-        double s = 0.0;
-        for (int b = lane; b < nblk; b += 64) s += part[(long)b * C + c];
-        s = wave_sum(s);
-        if (lane == 0) out[c] = accumulate ? out[c] + (float)s : (float)s;
     }
 }
 
@@ -449,7 +440,6 @@ int movae_act_bwd_bias_grouped(int groups, const float* dy, const float* out, fl
 }
 
 int movae_colsum(const float* x, float* out, int rows, int c, int accumulate, void* ws, size_t ws_bytes, movae_stream_t stream) {
-    unsigned* counter = static_cast<unsigned*>(ws);  // workspace header (see movae.h)
     MOVAE_WS_SCRATCH(ws, ws_bytes);
     MOVAE_CHECK_ARG(x && out && rows > 0 && c > 0, "movae_colsum: bad argument");
     if (c % 4 == 0 && al16(x) && ws) {
@@ -462,9 +452,7 @@ int movae_colsum(const float* x, float* out, int rows, int c, int accumulate, vo
         const int nblk4 = ceil_div(rows, rpb4);
         MOVAE_CHECK_ARG(ws && ws_bytes >= (size_t)nblk4 * c * sizeof(double), "movae_colsum: workspace too small");
         double* part4 = static_cast<double*>(ws);
-        (void)counter;  // in-launch fold measured slower than a second launch (see bn_act.hip::in_launch_final)
-        hipLaunchKernelGGL(colsum_partial4, dim3(nblk4), dim3(256), 0, (hipStream_t)stream, x, part4, rows, c, CQB, rpb4,
-                           (unsigned*)nullptr, out, accumulate);
+        hipLaunchKernelGGL(colsum_partial4, dim3(nblk4), dim3(256), 0, (hipStream_t)stream, x, part4, rows, c, CQB, rpb4);
         MOVAE_CHECK_LAUNCH("colsum_partial4");
         hipLaunchKernelGGL(colsum_final, dim3(c), dim3(64), 0, (hipStream_t)stream, part4, nblk4, c, out, accumulate);
         MOVAE_CHECK_LAUNCH("colsum_final");

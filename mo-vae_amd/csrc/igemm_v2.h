@@ -544,31 +544,15 @@ __device__ __forceinline__ void igemm2_fwd_body(const FwdArgs& a, float* __restr
     }
 }
 
-// XCD-aware block -> tile map.  The hardware deals consecutive workgroups to the 8 XCDs in turn (linear id % 8), each with an L2 of
-// its own: with tile = block id, the row tiles an XCD works on are every 8th one -- neighbours' halo rows and the column tiles that
-// re-read the same activation rows land in other XCDs' L2s, and every XCD streams (nearly) the whole activation (PMC: 541 MB per
-// launch of igemm2_bwd<128,128> at C3 for ~75 MB algorithmic).  Here XCD x takes a CONTIGUOUS run of tiles in (row tile, column
-// tile) order -- column tiles of one row tile adjacent -- so an activation row is fetched by one XCD.  A bijection on [0, gx * gy).
-__device__ __forceinline__ void xcd_tile(int xr, int& bx, int& by) {
-    if (!xr) return;
-    const int gx = (int)gridDim.x, gy = (int)gridDim.y, T = gx * gy;
-    const int lin = bx + gx * by, x = lin & 7, j = lin >> 3;
-    const int per = T >> 3, rem = T & 7;
-    const int t = x * per + (x < rem ? x : rem) + j;
-    bx = t / gy, by = t - bx * gy;
-}
-
 template <int BM, int BN, bool BF = false>
-__global__ __launch_bounds__(256) void igemm2_fwd(FwdArgs a, RSide sd, int gz, int xr) {
+__global__ __launch_bounds__(256) void igemm2_fwd(FwdArgs a, RSide sd, int gz) {
     __shared__ __attribute__((aligned(16))) float smem[FwdSmem<BM, BN>::FLOATS];
     if ((int)blockIdx.z >= gz) {  // a parked weight-gradient reduce rides BEHIND this launch's own blocks (conv_igemm.hip: RSide)
         const int bid = (((int)blockIdx.z - gz) * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
         if (bid < sd.nblk) side_reduce(sd, bid, smem);
         return;
     }
-    int bx = blockIdx.x, by = blockIdx.y;
-    xcd_tile(xr & 1, bx, by);
-    igemm2_fwd_body<BM, BN, BF>(a, smem, bx, by, blockIdx.z);
+    igemm2_fwd_body<BM, BN, BF>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1004,18 +988,14 @@ __device__ __forceinline__ void igemm2_bwd_body(const BwdArgs& a, float* __restr
 }
 
 template <int BM, int BN, bool BF = false>
-__global__ __launch_bounds__(256) void igemm2_bwd(BwdArgs a, RSide sd, int gz, int xr) {
+__global__ __launch_bounds__(256) void igemm2_bwd(BwdArgs a, RSide sd, int gz) {
     __shared__ __attribute__((aligned(16))) float smem[BwdSmem<BM, BN>::FLOATS];
     if ((int)blockIdx.z >= gz) {  // a parked weight-gradient reduce rides BEHIND this launch's own blocks (conv_igemm.hip: RSide)
         const int bid = (((int)blockIdx.z - gz) * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
         if (bid < sd.nblk) side_reduce(sd, bid, smem);
         return;
     }
-    int bx = blockIdx.x, by = blockIdx.y;
-    xcd_tile(xr & 1, bx, by);
-    // (xr & 2: the (class, split) pairs in REVERSE order -- the last output-parity class of a 3x3 stride-2 layer carries 4 of the 9
-    // taps, the first one 1: blocks are dispatched in index order, and the long ones should not be the tail; cls_order())
-    igemm2_bwd_body<BM, BN, BF>(a, smem, bx, by, (xr & 2) ? gz - 1 - (int)blockIdx.z : (int)blockIdx.z);
+    igemm2_bwd_body<BM, BN, BF>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1315,16 +1295,14 @@ __device__ __forceinline__ void igemm2_wgrad_body(const WgArgs& a, float* __rest
 }
 
 template <int BM, int BN, bool BF = false>
-__global__ __launch_bounds__(256) void igemm2_wgrad(WgArgs a, RSide sd, int gz, int xr) {
+__global__ __launch_bounds__(256) void igemm2_wgrad(WgArgs a, RSide sd, int gz) {
     __shared__ __attribute__((aligned(16))) float smem[WgSmem<BM, BN>::FLOATS];
     if ((int)blockIdx.z >= gz) {  // a parked weight-gradient reduce rides BEHIND this launch's own blocks (conv_igemm.hip: RSide)
         const int bid = (((int)blockIdx.z - gz) * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
         if (bid < sd.nblk) side_reduce(sd, bid, smem);
         return;
     }
-    int bx = blockIdx.x, by = blockIdx.y;
-    xcd_tile(xr & 1, bx, by);
-    igemm2_wgrad_body<BM, BN, BF>(a, smem, bx, by, blockIdx.z);
+    igemm2_wgrad_body<BM, BN, BF>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // ---- one launch, two problems: the input gradient (FWD or BWD gather form) and the weight gradient of one layer ----------
@@ -1334,7 +1312,7 @@ __global__ __launch_bounds__(256) void igemm2_wgrad(WgArgs a, RSide sd, int gz, 
 // of the two bodies' needs.
 template <int FORM, int ABM, int ABN, int WBM, int WBN>
 __global__ __launch_bounds__(256) void igemm2_pair(FwdArgs fa, BwdArgs ba, WgArgs wa, int nd, int dgx, int dgy, int wgx, int wgy,
-                                                   int nw, int inter, RSide sd) {
+                                                   int nw, RSide sd) {
     constexpr int DF = FORM == 0 ? FwdSmem<ABM, ABN>::FLOATS : BwdSmem<ABM, ABN>::FLOATS;
     constexpr int WF = WgSmem<WBM, WBN>::FLOATS;
     __shared__ __attribute__((aligned(16))) float smem[DF > WF ? DF : WF];
@@ -1343,21 +1321,14 @@ __global__ __launch_bounds__(256) void igemm2_pair(FwdArgs fa, BwdArgs ba, WgArg
         side_reduce(sd, b - nd - nw, smem);
         return;
     }
-    const int rev = inter >> 2;  // (bit 2: cls_order())
-    inter &= 3;
-    if (inter == 2) {  // weight-gradient blocks first
-        b = b < nw ? nd + b : b - nw;
-    } else if (inter) {  // alternate the two problems' blocks while both last (the dispatcher hands out blocks in index order)
-        const int m = nd < nw ? nd : nw;
-        if (b < 2 * m) b = (b & 1) ? nd + (b >> 1) : (b >> 1);
-        else b = nd < nw ? b : b - m;  // tail: the longer problem's remaining blocks (dgrad tail keeps indices m.., wgrad tail nd + m..)
-    }
+    // the weight gradient's blocks first: they are the longer ones and blocks are dispatched in index order (C2 0.793 -> 0.780 ms)
+    b = b < nw ? nd + b : b - nw;
     if (b < nd) {
         const int bx = b % dgx, r = b / dgx;
         if (FORM == 0)
             igemm2_fwd_body<ABM, ABN>(fa, smem, bx, r % dgy, r / dgy);
         else
-            igemm2_bwd_body<ABM, ABN>(ba, smem, bx, r % dgy, rev ? nd / (dgx * dgy) - 1 - r / dgy : r / dgy);  // (cls_order())
+            igemm2_bwd_body<ABM, ABN>(ba, smem, bx, r % dgy, r / dgy);
     } else {
         b -= nd;
         const int bx = b % wgx, r = b / wgx;
@@ -1388,13 +1359,6 @@ struct PendingDgrad {
 };
 static thread_local PendingDgrad g_pending;
 static thread_local bool g_pair_collect = false;
-
-// a paired launch brings the partner's blocks onto the chip as well: the split-K cost model is asked about this many
-// times the own tiles (tuning knob MOVAE_PAIR_TILES, percent)
-inline long pair_tiles(long tiles, bool paired) {
-    static const int pct = getenv("MOVAE_PAIR_TILES") ? atoi(getenv("MOVAE_PAIR_TILES")) : 100;
-    return paired ? (tiles * pct + 99) / 100 : tiles;
-}
 
 template <int BM, int BN>
 constexpr bool pair_dgrad_tile() { return (BM == 64 && BN == 64) || (BM == 128 && BN == 32); }
@@ -1437,19 +1401,6 @@ inline int finish_pending(hipStream_t st) {  // the stashed dgrad's reduce
     return MOVAE_OK;
 }
 
-// MOVAE_CLS_ORDER=1: a BWD-form launch enumerates its (class, split) pairs last class first (bit 1 of the kernels' `xr`).  Measured
-// neutral (C2 0.759 vs 0.768 ms, inside the noise; C1, C5 level: the per-class split factors already balance the classes): off.
-inline int cls_order() {
-    static const int v = getenv("MOVAE_CLS_ORDER") ? atoi(getenv("MOVAE_CLS_ORDER")) : 0;
-    return v ? 2 : 0;
-}
-
-// MOVAE_XCD_REMAP: 1 = XCD-aware tile map (xcd_tile) for launches of at least 64 tiles per z slice, 0 = tile = block id
-inline int xcd_remap(const dim3& grid) {
-    static const int mode = getenv("MOVAE_XCD_REMAP") ? atoi(getenv("MOVAE_XCD_REMAP")) : 0;
-    return mode && (long)grid.x * grid.y >= 64 ? 1 : 0;
-}
-
 inline int flush_pending(hipStream_t st) {  // launch the stashed dgrad on its own
     if (g_kpair.flush)
         if (int rc = g_kpair.flush(st)) return rc;
@@ -1460,11 +1411,11 @@ inline int flush_pending(hipStream_t st) {  // launch the stashed dgrad on its o
     int gz;
     const RSide sd = defer_take_3d(st, &grid, &gz);
     if (p.form == 0) {
-        if (p.bm == 64) hipLaunchKernelGGL((igemm2_fwd<64, 64>), grid, dim3(256), 0, st, p.fa, sd, gz, xcd_remap(grid));
-        else hipLaunchKernelGGL((igemm2_fwd<128, 32>), grid, dim3(256), 0, st, p.fa, sd, gz, xcd_remap(grid));
+        if (p.bm == 64) hipLaunchKernelGGL((igemm2_fwd<64, 64>), grid, dim3(256), 0, st, p.fa, sd, gz);
+        else hipLaunchKernelGGL((igemm2_fwd<128, 32>), grid, dim3(256), 0, st, p.fa, sd, gz);
     } else {
-        if (p.bm == 64) hipLaunchKernelGGL((igemm2_bwd<64, 64>), grid, dim3(256), 0, st, p.ba, sd, gz, xcd_remap(grid) | cls_order());
-        else hipLaunchKernelGGL((igemm2_bwd<128, 32>), grid, dim3(256), 0, st, p.ba, sd, gz, xcd_remap(grid) | cls_order());
+        if (p.bm == 64) hipLaunchKernelGGL((igemm2_bwd<64, 64>), grid, dim3(256), 0, st, p.ba, sd, gz);
+        else hipLaunchKernelGGL((igemm2_bwd<128, 32>), grid, dim3(256), 0, st, p.ba, sd, gz);
     }
     MOVAE_CHECK_LAUNCH("igemm2 dgrad (unpaired)");
     return finish_pending(st);
@@ -1475,9 +1426,7 @@ int launch_fwd2(const float* X, const float* W, float* Y, const Geom& g, const E
                 size_t ws_bytes, hipStream_t st) {
     const int gx = ceil_div(M, BM), gy = ceil_div(g.Nn, BN);
     const int nk = ceil_div(K, BK2);
-    const bool pairing = g_pair_collect && pair_dgrad_tile<BM, BN>();
-    int S = choose_split(FORM_FWD, BM * BN, BK2, pair_tiles((long)gx * gy, pairing), nk, (size_t)M * g.Nn * sizeof(float), ws_bytes,
-                         ws != nullptr);
+    int S = choose_split(FORM_FWD, BM * BN, BK2, (long)gx * gy, nk, (size_t)M * g.Nn * sizeof(float), ws_bytes, ws != nullptr);
     const int per_split = ceil_div(nk, S);
     S = ceil_div(nk, per_split);
     float* slab = S > 1 ? static_cast<float*>(ws) : nullptr;
@@ -1532,8 +1481,8 @@ int launch_fwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     dim3 grid(gx, gy, S);
     int gz;
     const RSide sd = defer_take_3d(st, &grid, &gz);
-    if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_fwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz, xcd_remap(grid));
-    else hipLaunchKernelGGL((igemm2_fwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz, xcd_remap(grid));
+    if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_fwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
+    else hipLaunchKernelGGL((igemm2_fwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_fwd");
     if (S > 1) {
         if (rbb.y && !g_bench_main_only) {
@@ -1574,15 +1523,14 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
         return MOVAE_EUNSUPPORTED;
     }
     // split factor of the heaviest class from the cost model, on the block count the balanced grid will have
-    const long tiles_eff = pair_tiles(ceil_div((long)gx * gy * nk_sum, nk_max), g_pair_collect && pair_dgrad_tile<BM, BN>());
+    const long tiles_eff = ceil_div((long)gx * gy * nk_sum, nk_max);
     int Smax = choose_split(FORM_BWD, BM * BN, BK2, tiles_eff, nk_max, (size_t)total * sizeof(float), ws_bytes, ws != nullptr);
     // the cost model sees balanced blocks; unsplit but unbalanced (heaviest class >= 2x the lightest) it is better to split
     int nk_min = nk_max;
     for (int c = 0; c < ncls; ++c)
         if (nk_c[c] > 0 && nk_c[c] < nk_min) nk_min = nk_c[c];
-    static const int balance = getenv("MOVAE_BWD_BALANCE") ? atoi(getenv("MOVAE_BWD_BALANCE")) : 1;
     // (measured: pays while the output is below ~5 MB -- every extra slab writes and re-reads it once)
-    if (balance && Smax == 1 && ws && nk_max >= 2 * nk_min && nk_min >= 4 && (size_t)total * sizeof(float) <= (5u << 20) &&
+    if (Smax == 1 && ws && nk_max >= 2 * nk_min && nk_min >= 4 && (size_t)total * sizeof(float) <= (5u << 20) &&
         (size_t)total * sizeof(float) * (nk_max / nk_min) <= ws_bytes && g.Nn % 4 == 0)
         Smax = nk_max / nk_min;
     ClsSplit scls, kps;
@@ -1590,7 +1538,7 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     for (int c = 0; c < 4; ++c) {
         int Sc = 1, per = 1;
         if (c < ncls && nk_c[c] > 0) {
-            Sc = balance ? (int)(((long)Smax * nk_c[c] + nk_max - 1) / nk_max) : Smax;
+            Sc = (int)(((long)Smax * nk_c[c] + nk_max - 1) / nk_max);
             if (Sc < 1) Sc = 1;
             per = ceil_div(nk_c[c], Sc);
             Sc = ceil_div(nk_c[c], per);
@@ -1672,8 +1620,8 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     dim3 grid(gx, gy, zsum);
     int gz;
     const RSide sd = defer_take_3d(st, &grid, &gz);
-    if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_bwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz, xcd_remap(grid) | cls_order());
-    else hipLaunchKernelGGL((igemm2_bwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz, xcd_remap(grid) | cls_order());
+    if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_bwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
+    else hipLaunchKernelGGL((igemm2_bwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_bwd");
     if (Sreal > 1 && !g_bench_main_only) {
         if (rbb.y) {
@@ -1694,21 +1642,12 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     return MOVAE_OK;
 }
 
-// Order of a paired launch's blocks (MOVAE_PAIR_INTERLEAVE): 2 = the weight gradient's first (default: they are the longer ones --
-// a deep reduction slice each -- and the dispatcher hands blocks out in index order, so the short input-gradient blocks fill in
-// behind them; C2 0.793 -> 0.780 ms, C4 level), 1 = alternating, 0 = the input gradient's first.
-inline int pair_order() {
-    static const int v = getenv("MOVAE_PAIR_INTERLEAVE") ? atoi(getenv("MOVAE_PAIR_INTERLEAVE")) : 2;
-    return v;
-}
-
 template <int FORM, int ABM, int ABN, int WBM, int WBN>
 inline void launch_pair(const PendingDgrad& p, const WgArgs& wa, int wgx, int wgy, int wgz, hipStream_t st) {
     const int nd = p.gx * p.gy * p.gz, nw = wgx * wgy * wgz;
-    const int inter = pair_order() | (cls_order() ? 4 : 0);
     const RSide sd = defer_take(st);  // the previous layer's parked weight-gradient reduce rides behind the two problems
     hipLaunchKernelGGL((igemm2_pair<FORM, ABM, ABN, WBM, WBN>), dim3(nd + nw + sd.nblk), dim3(256), 0, st, p.fa, p.ba, wa, nd, p.gx, p.gy,
-                       wgx, wgy, nw, inter, sd);
+                       wgx, wgy, nw, sd);
 }
 
 template <int BM, int BN>
@@ -1718,8 +1657,7 @@ int launch_wgrad2(const float* Sm, const float* Bg, float* const* dW, int G, lon
     const long stride = (long)M * N + (colsum ? M : 0);  // floats per slab
     const int gx = ceil_div(M, BM), gy = ceil_div(N, BN);
     // the G groups run side by side, so the split factor is chosen for G times the tiles
-    int Sp = choose_split(FORM_WGRAD, BM * BN, BK2, pair_tiles((long)gx * gy * G, (g_pending.active || (g_kpair.pending && g_kpair.pending())) && pair_wgrad_tile<BM, BN>()),
-                          ceil_div(K, BK2), (size_t)stride * sizeof(float) * G, ws_bytes, ws != nullptr);
+    int Sp = choose_split(FORM_WGRAD, BM * BN, BK2, (long)gx * gy * G, ceil_div(K, BK2), (size_t)stride * sizeof(float) * G, ws_bytes, ws != nullptr);
     const int kchunk = ceil_div(ceil_div(K, Sp), BK2) * BK2;
     Sp = ceil_div(K, kchunk);
     const bool slab = Sp > 1 || accumulate;
@@ -1764,8 +1702,8 @@ int launch_wgrad2(const float* Sm, const float* Bg, float* const* dW, int G, lon
         dim3 grid(gx, gy, Sp * G);
         int gz;
         const RSide sd = defer_take_3d(st, &grid, &gz);
-        if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_wgrad<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz, xcd_remap(grid));
-        else hipLaunchKernelGGL((igemm2_wgrad<BM, BN>), grid, dim3(256), 0, st, a, sd, gz, xcd_remap(grid));
+        if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_wgrad<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
+        else hipLaunchKernelGGL((igemm2_wgrad<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
         MOVAE_CHECK_LAUNCH("igemm2_wgrad");
     }
     if (slab) {  // ONE reduce launch for all groups (blockIdx.y = group)

@@ -392,14 +392,14 @@ __device__ __forceinline__ void kgemm_body(const KArgs& a, float* __restrict__ s
 }
 
 template <int FORM, int NW, int KS, bool NRM>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void kgemm_k(KArgs a, RSide sd, int gz, int rev) {
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 2) void kgemm_k(KArgs a, RSide sd, int gz) {
     __shared__ __attribute__((aligned(16))) float smem[smem_floats<NW>()];
     if (NW == 4 && (int)blockIdx.z >= gz) {  // a parked weight-gradient reduce rides behind this launch's own blocks (conv_igemm.hip: RSide)
         const int bid = (((int)blockIdx.z - gz) * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
         if (bid < sd.nblk) side_reduce(sd, bid, smem);
         return;
     }
-    kgemm_body<FORM, NW, KS, NRM>(a, smem, blockIdx.x, blockIdx.y, (FORM == 1 && rev) ? gz - 1 - (int)blockIdx.z : (int)blockIdx.z);  // (v2::cls_order())
+    kgemm_body<FORM, NW, KS, NRM>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // ---- weight gradient: dW[a][tap][b] = sum_p S[p][a] * Bg[p * s - pad + tap][b]   (M = Cs, N = taps * Cb) ------------------------
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(NW * 64, 2) void kwgrad_k(KWArgs a) {
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 // MOVAE_KGEMM=0 switches the family off (A/B); movae_bench_force_kgemm(1) makes every supported shape take it (tests).
 inline bool kgemm_enabled() {
-    static const bool on = !(getenv("MOVAE_KGEMM") && atoi(getenv("MOVAE_KGEMM")) == 0);
+    static const bool on = env_long("MOVAE_KGEMM", 1) != 0;
     return on;
 }
 
@@ -582,7 +582,7 @@ struct KSplit {
     int nw, ks;
 };
 inline KSplit choose_ks(long tiles) {
-    static const int forced = getenv("MOVAE_KGEMM_KS") ? atoi(getenv("MOVAE_KGEMM_KS")) : 0;
+    static const int forced = env_long("MOVAE_KGEMM_KS", 0);
     if (forced == 8) return KSplit{8, 8};
     if (forced == 1 || forced == 2 || forced == 4) return KSplit{4, forced};
     // (measured on the CIFAR VAE's middle layers, 256 tiles: eight waves per tile 12.1-14.0 us, four waves 11.4-12.9 us per call --
@@ -602,11 +602,11 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 inline bool small_problem(long rows, long cols, long k, long copies) {
     const long tiles64 = ((rows + 63) / 64) * ((cols + 63) / 64) * copies;
     const double flop = 2.0 * (double)rows * (double)cols * (double)k * (double)copies;
-    static const long tmax = getenv("MOVAE_KGEMM_TILES64") ? atol(getenv("MOVAE_KGEMM_TILES64")) : 384;
-    static const double fmax = getenv("MOVAE_KGEMM_GFLOP") ? atof(getenv("MOVAE_KGEMM_GFLOP")) * 1e9 : 4e9;
+    static const long tmax = env_long("MOVAE_KGEMM_TILES64", 384);
+    static const double fmax = env_double("MOVAE_KGEMM_GFLOP", 4.0) * 1e9;
     // a short reduction (K = 288: 32 -> 64 channels on 16x16 images) leaves a wave's slice nine groups long -- the fold and the
     // epilogue then outweigh the slabs they replace (measured 18.6 vs 13.5 us per call)
-    static const long kmin = getenv("MOVAE_KGEMM_KMIN") ? atol(getenv("MOVAE_KGEMM_KMIN")) : 512;
+    static const long kmin = env_long("MOVAE_KGEMM_KMIN", 512);
     // ... and enough 32x32 tiles to occupy half the chip: the reduction is only split INSIDE a block, so a problem with a handful
     // of tiles and a very long reduction (BetaTC-VAE's fc 32768 -> 256 at batch 32: 8 tiles) belongs to the split-K kernels
     // (measured at C5: 309 us here against 54 us there)
@@ -619,7 +619,7 @@ inline void launch_k2(const KArgs& a, KSplit k, dim3 tiles, hipStream_t st) {  /
     if (k.ks == 8) {
         KArgs b8 = a;
         b8.fin.group = (int)(tiles.x * tiles.z);
-        hipLaunchKernelGGL((kgemm_k<FORM, 8, 8, NRM>), tiles, dim3(512), 0, st, b8, RSide{}, (int)tiles.z, v2::cls_order());
+        hipLaunchKernelGGL((kgemm_k<FORM, 8, 8, NRM>), tiles, dim3(512), 0, st, b8, RSide{}, (int)tiles.z);
         return;
     }
     dim3 grid = k.ks == 4 ? tiles : k.ks == 2 ? dim3((tiles.x + 1) / 2, tiles.y, tiles.z) : dim3((tiles.x + 3) / 4, tiles.y, tiles.z);
@@ -627,9 +627,9 @@ inline void launch_k2(const KArgs& a, KSplit k, dim3 tiles, hipStream_t st) {  /
     b.fin.group = (int)(grid.x * grid.z);  // blocks per column tile (before any carried reduce's extra z layers)
     int gz;
     const RSide sd = defer_take_3d(st, &grid, &gz);
-    if (k.ks == 4) hipLaunchKernelGGL((kgemm_k<FORM, 4, 4, NRM>), grid, dim3(256), 0, st, b, sd, gz, v2::cls_order());
-    else if (k.ks == 2) hipLaunchKernelGGL((kgemm_k<FORM, 4, 2, NRM>), grid, dim3(256), 0, st, b, sd, gz, v2::cls_order());
-    else hipLaunchKernelGGL((kgemm_k<FORM, 4, 1, NRM>), grid, dim3(256), 0, st, b, sd, gz, v2::cls_order());
+    if (k.ks == 4) hipLaunchKernelGGL((kgemm_k<FORM, 4, 4, NRM>), grid, dim3(256), 0, st, b, sd, gz);
+    else if (k.ks == 2) hipLaunchKernelGGL((kgemm_k<FORM, 4, 2, NRM>), grid, dim3(256), 0, st, b, sd, gz);
+    else hipLaunchKernelGGL((kgemm_k<FORM, 4, 1, NRM>), grid, dim3(256), 0, st, b, sd, gz);
 }
 template <int FORM>
 inline void launch_k(const KArgs& a, KSplit k, dim3 tiles, hipStream_t st) {
@@ -640,8 +640,7 @@ inline void launch_k(const KArgs& a, KSplit k, dim3 tiles, hipStream_t st) {
 // ---- one launch, two problems (see v2::igemm2_pair): blocks [0, nd) run a stashed kgemm input gradient (four waves, KS = 4),
 // the rest the tiled weight gradient of the same layer.  The two share read-only operands only.
 template <int FORM, int WBM, int WBN>
-__global__ __launch_bounds__(256) void kpair_k(KArgs ka, v2::WgArgs wa, int nd, int dgx, int dgy, int wgx, int wgy, int nw, RSide sd,
-                                               int wfirst) {
+__global__ __launch_bounds__(256) void kpair_k(KArgs ka, v2::WgArgs wa, int nd, int dgx, int dgy, int wgx, int wgy, int nw, RSide sd) {
     constexpr int DF = smem_floats<4>(), WF = v2::WgSmem<WBM, WBN>::FLOATS;
     __shared__ __attribute__((aligned(16))) float smem[DF > WF ? DF : WF];
     int b = blockIdx.x;
@@ -649,10 +648,10 @@ __global__ __launch_bounds__(256) void kpair_k(KArgs ka, v2::WgArgs wa, int nd, 
         side_reduce(sd, b - nd - nw, smem);
         return;
     }
-    if (wfirst & 1) b = b < nw ? nd + b : b - nw;  // the weight gradient's (longer) blocks are dispatched first (v2::pair_order; bit 1: cls_order)
+    b = b < nw ? nd + b : b - nw;  // the weight gradient's (longer) blocks are dispatched first (see v2::igemm2_pair)
     if (b < nd) {
         const int bx = b % dgx, r = b / dgx;
-        kgemm_body<FORM, 4, 4, false>(ka, smem, bx, r % dgy, (FORM == 1 && (wfirst & 2)) ? nd / (dgx * dgy) - 1 - r / dgy : r / dgy);
+        kgemm_body<FORM, 4, 4, false>(ka, smem, bx, r % dgy, r / dgy);
     } else {
         b -= nd;
         const int bx = b % wgx, r = b / wgx;
@@ -686,7 +685,7 @@ inline int kpend_pair(const v2::WgArgs& wa, int wgx, int wgy, int wgz, bool w64,
     const int nd = p.tiles.x * p.tiles.y * p.tiles.z, nw = wgx * wgy * wgz;
     const RSide sd = defer_take(st);  // the previous layer's parked weight-gradient reduce rides behind the two problems
     const dim3 grid(nd + nw + sd.nblk);
-#define MOVAE_KP(F_, BM_, BN_) hipLaunchKernelGGL((kpair_k<F_, BM_, BN_>), grid, dim3(256), 0, st, p.a, wa, nd, (int)p.tiles.x, (int)p.tiles.y, wgx, wgy, nw, sd, (v2::pair_order() == 2 ? 1 : 0) | v2::cls_order())
+#define MOVAE_KP(F_, BM_, BN_) hipLaunchKernelGGL((kpair_k<F_, BM_, BN_>), grid, dim3(256), 0, st, p.a, wa, nd, (int)p.tiles.x, (int)p.tiles.y, wgx, wgy, nw, sd)
     if (p.form == 0 && w64) {
         MOVAE_KP(0, 64, 64);
         g_last_kernel = "kpair_k<0,64,64>";
@@ -715,7 +714,7 @@ static KPairInstall g_kpair_install;
 // bn_finalize launch each replaces -- 0.818 vs 0.821 ms per step, inside the noise, C1 0.602 vs 0.599.
 static int g_kgemm_bn_fin = -1;
 inline bool kgemm_bn_fin() {
-    static const bool env = getenv("MOVAE_KGEMM_BN_FIN") && atoi(getenv("MOVAE_KGEMM_BN_FIN")) != 0;
+    static const bool env = env_long("MOVAE_KGEMM_BN_FIN", 0) != 0;
     return g_kgemm_bn_fin < 0 ? env : g_kgemm_bn_fin != 0;
 }
 
@@ -856,7 +855,7 @@ inline int launch_kwgrad(const float* Sm, const float* Bg, float* const* dW, int
     // 128->256 @4x4 16.6 vs 16.4, 256->512 @2x2 14.2 vs 10.6 -- every operand element is its own 4-byte load here (the reduction
     // index is the slow axis of both operands), eight times the load instructions of the LDS-staged 16-byte path.  Not selected by
     // the size heuristic; MOVAE_KWGRAD=1 or movae_bench_force_kgemm(1) take it.
-    static const bool kw_on = getenv("MOVAE_KWGRAD") && atoi(getenv("MOVAE_KWGRAD")) != 0;
+    static const bool kw_on = env_long("MOVAE_KWGRAD", 0) != 0;
     if (!forced && !(kw_on && small_problem(M, N, K, G))) return MOVAE_OK;
     const long tiles = (long)ceil_div(M, 32) * (N / 32) * G;
     const KSplit ks = choose_ks(tiles);

@@ -9,7 +9,7 @@
 //                       stay in registers; per-block partials of sum ssim, sum (x-y)^2, sum x, sum x^2 in fp64
 //   metric_finalize_k   one block folds the partials in a fixed order: per-image SSIM / MSE / SSNR and the chunk's ssim / psnr
 // No float atomics and no in-launch hand-offs (each kernel boundary orders the next one's reads): every sum has a fixed order, so
-// results are bit-identical from run to run.  (A last-block fold through a workspace counter, as in common.h, measured slower
+// results are bit-identical from run to run.  (A last-block fold through a workspace counter measured slower
 // here: with hundreds of blocks the agent-scope release of every block cost more than the finalize launch it saved.)
 #include "common.h"
 

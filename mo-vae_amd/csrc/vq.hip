@@ -436,7 +436,7 @@ static int segmented_code_sum(const float* x, const float* q, const int64_t* idx
     int* item_base = seg_lo + k + 2;
     void* temp = reinterpret_cast<void*>(item_base + k + 2);
     temp = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(temp) + 255) & ~(uintptr_t)255);
-    static const bool no_place = getenv("MOVAE_VQ_RADIX") && atoi(getenv("MOVAE_VQ_RADIX")) != 0;  // (A/B knob: the radix-sort path)
+    static const bool no_place = env_long("MOVAE_VQ_RADIX", 0) != 0;  // (A/B knob: the radix-sort path)
     if (k <= VQ_PLACE_MAX_K && !no_place) {  // counting placement: three launches instead of the sort's nine, the same order
         const int nblk = ceil_div(rows, 256);
         int* blk_hist = reinterpret_cast<int*>(temp);

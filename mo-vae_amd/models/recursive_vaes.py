@@ -12,8 +12,7 @@ What the fusion machinery assumes about one call per module per step, and why it
   * the ActLinks / LazyBNs inside nn.Stack live per call (each encoder / decoder call builds its own), the encoder ends in a
     flatten (a LazyBN never leaves it), and `x_gen` enters the encoder unlinked;
   * the Jacobian spans all parameters (`features is None`): by default one torch.autograd pass per loss (the engine sums a reused
-    parameter's uses; no gradient sink, in-place accumulation or parked reduce is armed, and the weight-gradient side stream stays
-    off).  MOVAE_BATCHED_FULL_JACOBIAN=1 pulls the K cotangents of the loss kernel's inputs back together instead
+    parameter's uses; no gradient sink, in-place accumulation or parked reduce is armed).  MOVAE_BATCHED_FULL_JACOBIAN=1 pulls the K cotangents of the loss kernel's inputs back together instead
     (autojac.backward_through): the Jacobian-row sinks are consumed by a parameter's first use and the walker adds the later uses
     before the leaf copy.
 

@@ -146,8 +146,8 @@ class _Dest:
       zeros(g, param, shape)  an identically zero gradient, handed out untouched (SINK_ZERO_LOG); the engine's form keeps ONE
                               persistent zero tensor per parameter that has no sink
       accum(w, b, need_b)     in-place accumulation targets (GRAD_ACCUM), the engine's alone; else (None, None)
-      engine                  the engine's launch choices: the per-layer fork (MOVAE_SIDE_STREAM=fork), and the entry points of
-                              one cotangent (movae_act_bwd, movae_bn_act_bwd) where the walker takes the grouped ones"""
+      engine                  the engine takes the entry points of one cotangent (movae_act_bwd, movae_bn_act_bwd) where the
+                              walker takes the grouped ones"""
     __slots__ = ("sink", "zeros", "accum", "engine")
 
     def __init__(self, sink, zeros, accum, engine):
@@ -297,43 +297,6 @@ def unflatten_nchw(x, c, h, w):
 
 
 # ---------------------------------------------------------------------------------------------
-class wgrad_side_stream:
-    """Inside this block every convolution's weight / bias gradient is launched on a forked side stream (own scratch arena)
-    and the compute stream does NOT wait for it: the backward's critical path is dgrad -> BatchNorm backward -> dgrad ...,
-    the weight gradients are leaves nobody reads until the aggregation / optimizer.  Two short latency-bound launches
-    then share the chip (measured on the C2 layers: 333 us for the 13 dgrad+wgrad pairs side by side vs 462 us in
-    sequence).  The block's exit -- or join_wgrad() -- makes the compute stream wait for the side stream once.  Works
-    under hipGraph capture (the side stream joins the capture at its first wait and returns at the join)."""
-
-    def __init__(self, device, enabled=True):
-        self.device, self.enabled = device, enabled and device.type == "cuda"
-        self.keep, self.used, self.prev = [], False, None
-
-    def __enter__(self):
-        if self.enabled:
-            self.prev, L.DEFER = L.DEFER, self
-            self.side = L.side_stream(self.device)
-        return self
-
-    def join(self):
-        if self.used:
-            torch.cuda.current_stream(self.device).wait_stream(self.side)
-            self.keep.clear()  # operands the side stream was still reading (the allocator may recycle them now)
-            self.used = False
-
-    def __exit__(self, *exc):
-        if self.enabled:
-            self.join()
-            L.DEFER = self.prev
-        return False
-
-
-def join_wgrad():
-    """Make the compute stream wait for every deferred weight gradient (no-op outside wgrad_side_stream)."""
-    if L.DEFER is not None:
-        L.DEFER.join()
-
-
 #: MOVAE_DEFER_REDUCE=0: every weight-gradient reduce is a launch of its own (A/B knob)
 DEFER_REDUCE = _knob("DEFER_REDUCE")
 
@@ -347,7 +310,7 @@ class deferred_reduces:
     gradient to anything else (torch arithmetic, a collective) inside the block calls flush_deferred() first."""
 
     def __init__(self, enabled=True):
-        self.enabled = enabled and DEFER_REDUCE and L.DEFER is None
+        self.enabled = enabled and DEFER_REDUCE
         self.prev = False
 
     def __enter__(self):
@@ -369,7 +332,7 @@ def flush_deferred():
 
 def _defer_ws(t, sunk):
     """(ws pointer, bytes) for a weight-gradient call: armed for a deferred reduce when every destination is a sink."""
-    if sunk and L.DEFER_ON[0] and L.DEFER is None:
+    if sunk and L.DEFER_ON[0]:
         return L.defer_arm(t.device)
     return None
 
@@ -737,17 +700,7 @@ class Conv(Function):
         dx = dw = db = None
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         need_w = ctx.needs_input_grad[1] or need_b
-        # dgrad and wgrad only share read-only operands: inside wgrad_side_stream (L.DEFER) the wgrad (+ its reduce / bias sum) is
-        # issued on a forked side stream with its own scratch arena, so the two short, latency-bound launches overlap on the
-        # device (also inside a captured hipGraph, as parallel branches).  The per-layer fork with its own join
-        # (MOVAE_SIDE_STREAM=fork) is the engine's alone.
-        defer = L.DEFER
-        fork = need_w and (defer is not None or (dest.engine and L.SIDE_STREAM_WGRAD and ctx.needs_input_grad[0]))
-        pair = need_w and ctx.needs_input_grad[0] and not fork  # both gradients, one stream: one call, one main launch
-        if fork:
-            main, side = torch.cuda.current_stream(dy.device), L.side_stream(dy.device)
-            if dest.engine:  # (the engine's form forks in front of the dgrad, the walker's behind it: kept as they were)
-                side.wait_stream(main)
+        pair = need_w and ctx.needs_input_grad[0]  # both gradients: one call, one main launch
         bn = _bn_request(ctx, x, in_norm, G)
         ep = _act_request(ctx, x, bn, (G,) + tuple(x.shape))
         if ctx.needs_input_grad[0]:
@@ -763,11 +716,6 @@ class Conv(Function):
                           wsp, wsb, st, C.byref(f), G)
                     _bn_publish(ctx, f, bn, dx, G)
                     _act_publish(ep, f, dx)
-        if fork:
-            if not dest.engine:
-                side.wait_stream(main)
-            ws2 = L.workspace(dy.device, slot=1)
-            wsp, wsb, st = ws2.data_ptr(), ws2.numel(), side.cuda_stream
         if need_w:
             wm_shape = (ci, kh, kw, co) if ctx.transposed else (co, kh, kw, ci)
             # a task-side parameter that an earlier loss already reached: add into its gradient inside the kernels' reduce
@@ -789,7 +737,7 @@ class Conv(Function):
             # one grouped launch: blockIdx.z = group * splits + split, x is read by every group, dy by its own; with the
             # input gradient wanted too, dgrad and wgrad share the launch (igemm2_pair).  Every destination a sink (or an
             # in-place accumulation target): the split-K reduce may ride on a later launch (deferred_reduces)
-            armed = _defer_ws(dy, not fork and (acc or len(SINK_LOG) - nlog == G * (1 + (db_k is not None))))
+            armed = _defer_ws(dy, acc or len(SINK_LOG) - nlog == G * (1 + (db_k is not None)))
             if armed is not None:
                 wsp, wsb = armed
             tail = (n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, acc, wsp, wsb, st)
@@ -801,11 +749,6 @@ class Conv(Function):
             else:
                 x, _ = Conv._wgrad_call(pre + "wgrad_grouped", in_norm, ctx.geom, ((G, dy, x, dwp, dbp), 2, tail))
             dw = [t.permute(0, 3, 1, 2) for t in dwm]
-        if fork and defer is not None:
-            defer.keep.append((dy, x, dwm, db))  # joined once, by wgrad_side_stream
-            defer.used = True
-        elif fork:
-            main.wait_stream(side)
         return _res_finish(ctx, dx), dw, db
 
     @staticmethod

@@ -84,33 +84,27 @@ def forward_backward_begin(net, images, optimizer, aggregator):
     optimizer.zero_grad()
     outputs = net(images)
     loss_dict = net.loss_function(images, args=outputs)
-    # weight gradients leave the backward's critical path (ops.wgrad_side_stream); the block's exit is the one join.  Not for a
-    # Jacobian over all parameters (features is None): those models reuse parameters, whose per-use gradients are summed on the
-    # compute stream while the side stream may still be writing them
-    side = L.DEFER_WGRAD_DEFAULT and net.features is not None
-    with ops.wgrad_side_stream(images.device, enabled=side):
-        if aggregator is None or aggregator == "sum":
-            loss_dict["total_loss"].backward()
-            return loss_dict, outputs, None
-        features = [outputs[f] for f in net.features] if net.features is not None else None
-        component_losses = [v for k, v in loss_dict.items() if k != "total_loss"]  # main.py:184
-        if isinstance(aggregator, (MGDA, COMFORT)):  # main.py:185
-            aggregator.set_losses(_stacked(component_losses))
-        if features is None:
-            if getattr(net, "_jacobian_from_loss_op", False):  # (internal: the K rows can be pulled back from the loss op's inputs)
-                autojac.backward_through(component_losses, aggregator)
-            else:
-                autojac.backward(component_losses, aggregator=aggregator)
-            return loss_dict, outputs, None
-        pending = autojac.mtl_backward_begin(component_losses, features, aggregator)
+    if aggregator is None or aggregator == "sum":
+        loss_dict["total_loss"].backward()
+        return loss_dict, outputs, None
+    features = [outputs[f] for f in net.features] if net.features is not None else None
+    component_losses = [v for k, v in loss_dict.items() if k != "total_loss"]  # main.py:184
+    if isinstance(aggregator, (MGDA, COMFORT)):  # main.py:185
+        aggregator.set_losses(_stacked(component_losses))
+    if features is None:
+        if getattr(net, "_jacobian_from_loss_op", False):  # (internal: the K rows can be pulled back from the loss op's inputs)
+            autojac.backward_through(component_losses, aggregator)
+        else:
+            autojac.backward(component_losses, aggregator=aggregator)
+        return loss_dict, outputs, None
+    pending = autojac.mtl_backward_begin(component_losses, features, aggregator)
     pending.device = images.device
     return loss_dict, outputs, pending
 
 
 def forward_backward_finish(pending):
     if pending is not None:
-        with ops.wgrad_side_stream(pending.device, enabled=L.DEFER_WGRAD_DEFAULT):
-            autojac.mtl_backward_finish(pending)
+        autojac.mtl_backward_finish(pending)
 
 
 def forward_backward(net, images, optimizer, aggregator):

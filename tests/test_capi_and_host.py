@@ -315,3 +315,22 @@ def test_concurrent_rebuilds_are_serialised(pkg, tmp_path):
     assert len(lines) == 3, lines  # two objects + one link, not 4 x 3
     left = [f for f in os.listdir(bdir) if ".tmp" in f] + [f for f in os.listdir(tmp_path) if ".tmp" in f]
     assert not left, left
+
+
+def test_env_switches_are_documented():
+    """Every MOVAE_* name the package reads from the environment has a row in INTEGRATION.md's switch table, and the table names
+    nothing the code no longer reads.  Source text only."""
+    read = set()
+    call = re.compile(r'\b(getenv|env_long|env_double|os\.environ\.get|_knob)\(\s*"([A-Za-z0-9_]+)"')
+    for d, _, files in os.walk(os.path.join(ROOT, "mo-vae_amd")):
+        for f in files:
+            if f.endswith((".py", ".h", ".hip", ".cpp")):
+                for fn, name in call.findall(open(os.path.join(d, f)).read()):
+                    name = "MOVAE_" + name if fn == "_knob" else name
+                    if name.startswith("MOVAE_") and name != "MOVAE_":  # (_knob itself reads "MOVAE_" + name)
+                        read.add(name)
+    assert len(read) >= 40, sorted(read)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = set(re.findall(r"^\| `(MOVAE_[A-Za-z0-9_]+)` \|", doc, flags=re.M))
+    assert read == table, f"read but not in the table: {sorted(read - table)}; in the table but not read: {sorted(table - read)}"
+
