@@ -188,6 +188,12 @@ inline float* fuse_bn_claim(long ppg, int n) {
         }                                                                                                   \
     } while (0)
 
+// Row, inside its 32x32 MFMA tile, of accumulator register r (0..15) of a lane in lane half `half` (lane >> 5); the column is
+// lane & 31.  Every kernel that stores v_mfma_f32_32x32x2_f32 results -- here and in igemm_v2.h -- maps its rows through this.
+// (`base`, the tile's first row, comes FIRST in the sum: the order the stores were written in and the kernels measured with --
+// added behind, igemm_bwd<128,64> takes one VGPR more and drops from 6 to 5 waves per SIMD.)
+__device__ __forceinline__ int acc_row(int r, int half, int base = 0) { return base + (r & 3) + 8 * (r >> 2) + 4 * half; }
+
 template <int TM>
 __device__ __forceinline__ void mma_tile(const float* __restrict__ As, const float* __restrict__ Bs, int lda, int ldb,
                                          int a_off, int b_off, f32x16 (&acc)[TM]) {
@@ -332,7 +338,7 @@ __global__ __launch_bounds__(256) void igemm_fwd(const float* __restrict__ X, co
     for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int m = acc_row(r, half, m0 + wm * T::TM * 32 + tm * 32);
             if (m < M) {
                 float v = acc[tm][r];
                 if (!to_slab) v = apply_act(v + bv, ep.act, ep.slope);
@@ -481,7 +487,7 @@ __global__ __launch_bounds__(256) void igemm_bwd(const float* __restrict__ X, co
     for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int m = acc_row(r, half, m0 + wm * T::TM * 32 + tm * 32);
             if (m < M) {
                 const int hw = Hoc * Woc;
                 const int img = m / hw, rem = m - img * hw;
@@ -610,7 +616,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad(const float* __restrict__ S, 
     for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int m = acc_row(r, half, m0 + wm * T::TM * 32 + tm * 32);
             if (m < M) dst[(long)m * N + n] = acc[tm][r];
         }
 }

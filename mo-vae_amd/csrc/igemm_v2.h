@@ -171,6 +171,208 @@ __device__ __forceinline__ f32x4 buf_load4(rsrc_t r, int byte_off) {
 inline bool buf_span_ok(long floats) { return floats * 4 < 0x7fffff00L; }
 
 // ------------------------------------------------------------------------------------------------
+// The store epilogue of the FWD-form and BWD-form bodies.  The two gather forms differ in their ROW MAP only: which output pixel
+// a tile row lands on, and where that pixel's row of an auxiliary tensor shared by the cotangent groups (BnBwd::y, ActMul::y)
+// lies -- `base` pixels earlier, the first pixel of the block's group.  (No row block straddles two cotangent groups: host.)
+struct RowsFwd {  // tile row -> output row m0 + row (an int: the epilogue's 64-bit offsets stay one 32 x 32 -> 64 bit multiply-add)
+    int m0, M, base;
+    __device__ __forceinline__ int pixel(int row) const { return m0 + row < M ? m0 + row : -1; }  // -1: past the end
+    __device__ __forceinline__ int aux(int p) const { return p - base; }
+};
+struct RowsBwd {  // tile row -> row m0 + row of the block's output-parity class (ph, pw) -> that class's pixel
+    int m0, M, hwc, Woc, s, ph, pw, Ho, Wo;
+    FastDiv fd_hw, fd_w;  // by hwc = Hoc * Woc and by Woc
+    long base;
+    __device__ __forceinline__ long pixel(int row) const {
+        const int m = m0 + row;
+        if (m >= M) return -1;
+        const int img = fdiv(m, fd_hw), rem = m - img * hwc;
+        const int hc = fdiv(rem, fd_w), wc = rem - hc * Woc;
+        return (long)(img * Ho + (hc * s + ph)) * Wo + (wc * s + pw);
+    }
+    __device__ __forceinline__ long aux(long p) const { return p - base; }
+};
+
+// Accumulators to an LDS tile [BM][BN + 4] (free after the k loop's last barrier): register r of a lane holds row
+// acc_row(r, half), i.e. (r & 3) + 8 * (r >> 2) + 4 * half, and column lane & 31 of its 32x32 tile.
+template <int BM, int BN>
+__device__ __forceinline__ void acc_to_lds(float* __restrict__ Ts, const f32x16 (&acc)[T2<BM, BN>::TM * T2<BM, BN>::TN]) {
+    using T = T2<BM, BN>;
+    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
+    const int wave = threadIdx.x >> 6, wm = wave / T::WN, wn = wave % T::WN;
+#pragma unroll
+    for (int tn = 0; tn < T::TN; ++tn)
+#pragma unroll
+        for (int tm = 0; tm < T::TM; ++tm)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                Ts[acc_row(r, half, wm * T::TM * 32 + tm * 32) * (BN + 4) + wn * T::TN * 32 + tn * 32 + l31] = acc[tm * T::TN + tn][r];
+}
+
+// Args: FwdArgs / BwdArgs (ep, g, stats, bb, am, side_lds).  `pidx`: the block's first partial slot -- its only one with
+// side_lds, else it owns WM slots, one per wave row.
+template <int BM, int BN, class Args, class Rows>
+__device__ __forceinline__ void tile_epilogue(const Args& a, const Rows& rows, float* __restrict__ smem,
+                                              const f32x16 (&acc)[T2<BM, BN>::TM * T2<BM, BN>::TN], float* out, bool to_slab, int n0,
+                                              long pidx) {
+    using T = T2<BM, BN>;
+    const Epilogue ep = a.ep;
+    const int N = a.g.Nn;
+    const int t = threadIdx.x, lane = t & 63, half = lane >> 5, l31 = lane & 31;
+    const int wave = t >> 6, wm = wave / T::WN, wn = wave % T::WN;
+    // Fused BatchNorm side products of the stores (never both): `stats` = column sums (v, v^2) of what is stored (the host asks
+    // only with act == none); `bb` = the stored value is dout of a fused BatchNorm over bb.y: sums (d, d * y).
+    const bool st_on = a.stats && !to_slab, bb_on = a.bb.y && !to_slab, am_on = actmul_on(a.am) && !to_slab;
+    constexpr int LDT = BN + 4, QPR = BN / 4, RSTEP = 256 / QPR;
+    float* Ts = smem;
+    // Every epilogue that emits no BatchNorm side product moves its tile through LDS once and then works in 16-byte pieces
+    // along n: in accumulator layout a lane holds one COLUMN -- 64 four-byte stores per lane (and as many loads per auxiliary
+    // operand of the ActMul form, issued in batches as registers allow).  Measured: plain stores / slab writes -3 % (C3 layers)
+    // to -6 % (C2 layers) per call; the ActMul form was 6 % SLOWER than the element-wise pass it replaces before this.
+    // (ActMul: the host guarantees N % 4 == 0 and 16-byte aligned operands.)
+    const bool lds_ep = am_on || (!st_on && !bb_on && (N & 3) == 0 &&
+                                  ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ep.bias)) & 15) == 0);
+    if (lds_ep) {
+        acc_to_lds<BM, BN>(Ts, acc);
+        __syncthreads();
+        const float* __restrict__ yp = a.am.y;
+        const float* __restrict__ rp = a.am.res;
+        for (int q = t; q < BM * QPR; q += 256) {
+            const int row = q / QPR, n = n0 + (q - row * QPR) * 4;
+            const auto p = rows.pixel(row);
+            if (p < 0 || n >= N) continue;
+            f32x4 v = *reinterpret_cast<const f32x4*>(Ts + row * LDT + (n - n0));
+            if (!to_slab) {
+                if (ep.bias) v += *reinterpret_cast<const f32x4*>(ep.bias + n);
+                if (am_on) {
+                    if (yp) {
+                        const f32x4 y4 = *reinterpret_cast<const f32x4*>(yp + (long)rows.aux(p) * N + n);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] *= act_grad_from_out(y4[j], a.am.act, a.am.slope);
+                    }
+                    if (rp) v += *reinterpret_cast<const f32x4*>(rp + (long)p * N + n);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = apply_act(v[j], ep.act, ep.slope);
+                }
+            }
+            *reinterpret_cast<f32x4*>(out + (long)p * N + n) = v;
+        }
+        return;
+    }
+    // All y values of a batch of rows are requested BEFORE the batch's first store, on both paths below: `out` and `y` may alias
+    // as far as the compiler knows, so a load placed after a store waits for it -- sixteen serial round trips per tile otherwise.
+    if ((st_on || bb_on) && a.side_lds) {
+        // the same through-LDS epilogue with a BatchNorm side product: a thread owns one column quad and every (256 / QPR)-th row
+        // of the tile, adds up its part of the column sums, the row lanes fold through LDS in fixed order.  ONE partial pair per
+        // block, and the host sized the partial layout for that (side_lds: N % 4 == 0, 16-byte aligned operands).
+        acc_to_lds<BM, BN>(Ts, acc);
+        __syncthreads();
+        const int cq = t % QPR, rowi = t / QPR, n = n0 + cq * 4;
+        f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
+        if (n < N) {
+            const f32x4 b4 = ep.bias ? *reinterpret_cast<const f32x4*>(ep.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+            const f32x4 sc4 = bb_on ? *reinterpret_cast<const f32x4*>(a.bb.scale + n) : b4;
+            const f32x4 sh4 = bb_on ? *reinterpret_cast<const f32x4*>(a.bb.shift + n) : b4;
+            const float* __restrict__ yp = a.bb.y;
+            for (int rb = rowi; rb < BM; rb += 4 * RSTEP) {
+                f32x4 y4[4];
+                decltype(rows.pixel(0)) px[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int row = rb + u * RSTEP;
+                    px[u] = row < BM ? rows.pixel(row) : -1;
+                    y4[u] = (bb_on && px[u] >= 0) ? *reinterpret_cast<const f32x4*>(yp + (long)rows.aux(px[u]) * N + n)
+                                                  : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (px[u] < 0) continue;
+                    f32x4 v = *reinterpret_cast<const f32x4*>(Ts + (rb + u * RSTEP) * LDT + cq * 4);
+                    if (st_on) {
+                        v += b4;
+                        s1 += v;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) s2[j] = fmaf(v[j], v[j], s2[j]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float d = v[j] * (fmaf(y4[u][j], sc4[j], sh4[j]) > 0.f ? 1.f : a.bb.slope);
+                            s1[j] += d;
+                            s2[j] = fmaf(d, y4[u][j], s2[j]);
+                        }
+                    }
+                    *reinterpret_cast<f32x4*>(out + (long)px[u] * N + n) = v;
+                }
+            }
+        }
+        __syncthreads();
+        *reinterpret_cast<f32x4*>(Ts + rowi * BN + cq * 4) = s1;
+        *reinterpret_cast<f32x4*>(Ts + (RSTEP + rowi) * BN + cq * 4) = s2;
+        __syncthreads();
+        if (t < BN && n0 + t < N) {
+            float c1 = 0.f, c2 = 0.f;
+            for (int i = 0; i < RSTEP; ++i) c1 += Ts[i * BN + t], c2 += Ts[(RSTEP + i) * BN + t];
+            float* P = st_on ? a.stats : a.bb.part;
+            P[(pidx * 2 + 0) * N + n0 + t] = c1;
+            P[(pidx * 2 + 1) * N + n0 + t] = c2;
+        }
+        return;
+    }
+    // The scalar path (misaligned operands, N % 4 != 0): a lane stores its column of every 32x32 tile.  One partial pair per
+    // wave row and column; the two lane halves fold with one shuffle.
+    // (the row map is asked again for every column and use: held in registers next to the accumulators, the pixels of a lane's
+    // rows cost the FWD form up to 30 VGPRs; the BWD form's decode is cheap next to this path's four-byte stores)
+#pragma unroll
+    for (int tn = 0; tn < T::TN; ++tn) {
+        const int n = n0 + wn * T::TN * 32 + tn * 32 + l31;
+        if (n >= N) continue;
+        const float bv = (!to_slab && ep.bias) ? ep.bias[n] : 0.f;
+        const float sc = bb_on ? a.bb.scale[n] : 0.f, sh = bb_on ? a.bb.shift[n] : 0.f;
+        float s1 = 0.f, s2 = 0.f;
+        float yv[T::TM * 16];
+        if (bb_on) {
+            const float* __restrict__ yp = a.bb.y;
+#pragma unroll
+            for (int tm = 0; tm < T::TM; ++tm)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const auto p = rows.pixel(acc_row(r, half, wm * T::TM * 32 + tm * 32));
+                    yv[tm * 16 + r] = p >= 0 ? yp[(long)rows.aux(p) * N + n] : 0.f;
+                }
+        }
+#pragma unroll
+        for (int tm = 0; tm < T::TM; ++tm)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const auto p = rows.pixel(acc_row(r, half, wm * T::TM * 32 + tm * 32));
+                if (p < 0) continue;
+                const float v = acc[tm * T::TN + tn][r];
+                const float o = to_slab ? v : apply_act(v + bv, ep.act, ep.slope);
+                out[(long)p * N + n] = o;
+                if (st_on) {
+                    s1 += o;
+                    s2 = fmaf(o, o, s2);
+                } else if (bb_on) {
+                    const float y1 = yv[tm * 16 + r];
+                    const float d = v * (fmaf(y1, sc, sh) > 0.f ? 1.f : a.bb.slope);
+                    s1 += d;
+                    s2 = fmaf(d, y1, s2);
+                }
+            }
+        if (st_on || bb_on) {
+            s1 += __shfl_xor(s1, 32, 64);
+            s2 += __shfl_xor(s2, 32, 64);
+            if (half == 0) {
+                float* P = st_on ? a.stats : a.bb.part;
+                P[((pidx + wm) * 2 + 0) * N + n] = s1;
+                P[((pidx + wm) * 2 + 1) * N + n] = s2;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Kernel arguments as plain structs and kernel bodies as device functions of an explicit block index (bx, by, bz) and an
 // LDS base: the stand-alone kernels below pass blockIdx, the paired kernel (igemm2_pair) runs a dgrad body and a wgrad
 // body side by side in ONE launch, sharing one LDS allocation.
@@ -210,7 +412,6 @@ __device__ __forceinline__ void igemm2_fwd_body(const FwdArgs& a, float* __restr
     float* __restrict__ Y = a.Y;
     float* __restrict__ slab = a.slab;
     const Geom g = a.g;
-    const Epilogue ep = a.ep;
     const int M = a.M, K = a.K, ktiles_per_split = a.ktiles_per_split;
     const int t = threadIdx.x;
     const int m0 = bx * BM, n0 = by * BN;
@@ -372,176 +573,15 @@ __device__ __forceinline__ void igemm2_fwd_body(const FwdArgs& a, float* __restr
         pipeline(std::false_type{}, std::false_type{});
     }
 
-    const int lane = t & 63, half = lane >> 5, l31 = lane & 31;
     const bool to_slab = slab != nullptr;
     float* out = to_slab ? slab + (long)bz * M * N : Y;
-    // Fused BatchNorm side products of the stores (never both): `stats` = column sums (v, v^2) of what is stored (the host asks
-    // only with act == none); `bb` = the stored value is dout of a fused BatchNorm over bb.y: sums (d, d * y).  One partial pair
-    // per wave and column; the two lane halves fold with one shuffle.  (No row block straddles two cotangent groups: host.)
-    const bool st_on = a.stats && !to_slab, bb_on = a.bb.y && !to_slab, am_on = actmul_on(a.am) && !to_slab;
-    const long pidx = (long)bx * T::WM + wm;  // (per-wave partials: the scalar epilogue, side_lds == 0)
+    const bool bb_on = a.bb.y && !to_slab, am_on = actmul_on(a.am) && !to_slab;
     // the block's first row inside its cotangent group (bb / am: the auxiliary tensor is shared by the groups)
     const int yrow0 = bb_on ? m0 % a.bb.rows_per_group : ((am_on && a.am.y) ? (int)(m0 % (a.am.per_group / N)) : 0);
-    // Every epilogue that emits no BatchNorm side product moves its tile through LDS once (free after the loop's last barrier)
-    // and then works in 16-byte pieces along n: in accumulator layout a lane holds one COLUMN -- 64 four-byte stores per lane
-    // (and as many loads per auxiliary operand of the ActMul form, issued in batches as registers allow).  Measured: plain
-    // stores / slab writes -3 % (C3 layers) to -6 % (C2 layers) per call; the ActMul form was 6 % SLOWER than the element-wise
-    // pass it replaces before this.  (ActMul: the host guarantees N % 4 == 0 and 16-byte aligned operands.)
-    const bool lds_ep = am_on || (!st_on && !bb_on && (N & 3) == 0 &&
-                                  ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ep.bias)) & 15) == 0);
-    if (lds_ep) {
-        constexpr int LDT = BN + 4, QPR = BN / 4;
-        static_assert(BM * LDT <= FwdSmem<BM, BN>::FLOATS, "tile fits the stage buffers");
-        float* Ts = smem;
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Ts[(wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + wn * T::TN * 32 + tn * 32 + l31] =
-                        acc[tm * T::TN + tn][r];
-        __syncthreads();
-        const float* __restrict__ yp = a.am.y;
-        const float* __restrict__ rp = a.am.res;
-        for (int q = t; q < BM * QPR; q += 256) {
-            const int row = q / QPR, n = n0 + (q - row * QPR) * 4, m = m0 + row;
-            if (m >= M || n >= N) continue;
-            f32x4 v = *reinterpret_cast<const f32x4*>(Ts + row * LDT + (n - n0));
-            if (!to_slab) {
-                if (ep.bias) v += *reinterpret_cast<const f32x4*>(ep.bias + n);
-                if (am_on) {
-                    if (yp) {
-                        const f32x4 y4 = *reinterpret_cast<const f32x4*>(yp + (long)(yrow0 + row) * N + n);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] *= act_grad_from_out(y4[j], a.am.act, a.am.slope);
-                    }
-                    if (rp) v += *reinterpret_cast<const f32x4*>(rp + (long)m * N + n);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = apply_act(v[j], ep.act, ep.slope);
-                }
-            }
-            *reinterpret_cast<f32x4*>(out + (long)m * N + n) = v;
-        }
-        return;
-    }
-    if ((st_on || bb_on) && a.side_lds) {
-        // the same through-LDS epilogue with a BatchNorm side product: a thread owns one column quad and every (256 / QPR)-th row
-        // of the tile, adds up its part of the column sums, the row lanes fold through LDS in fixed order.  ONE partial pair per
-        // block, and the host sized the partial layout for that (side_lds: N % 4 == 0, 16-byte aligned operands).
-        constexpr int LDT = BN + 4, QPR = BN / 4, RSTEP = 256 / QPR;
-        float* Ts = smem;
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Ts[(wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + wn * T::TN * 32 + tn * 32 + l31] =
-                        acc[tm * T::TN + tn][r];
-        __syncthreads();
-        const int cq = t % QPR, rowi = t / QPR, n = n0 + cq * 4;
-        f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
-        if (n < N) {
-            const f32x4 b4 = ep.bias ? *reinterpret_cast<const f32x4*>(ep.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-            const f32x4 sc4 = bb_on ? *reinterpret_cast<const f32x4*>(a.bb.scale + n) : b4;
-            const f32x4 sh4 = bb_on ? *reinterpret_cast<const f32x4*>(a.bb.shift + n) : b4;
-            const float* __restrict__ yp = a.bb.y;
-            for (int rb = rowi; rb < BM; rb += 4 * RSTEP) {
-                f32x4 y4[4];  // (the y loads of four rows ahead of their stores: see the note on aliasing below)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int row = rb + u * RSTEP;
-                    y4[u] = (bb_on && row < BM && m0 + row < M) ? *reinterpret_cast<const f32x4*>(yp + (long)(yrow0 + row) * N + n)
-                                                                : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int row = rb + u * RSTEP, m = m0 + row;
-                    if (row >= BM || m >= M) continue;
-                    f32x4 v = *reinterpret_cast<const f32x4*>(Ts + row * LDT + cq * 4);
-                    if (st_on) {
-                        v += b4;
-                        s1 += v;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) s2[j] = fmaf(v[j], v[j], s2[j]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float d = v[j] * (fmaf(y4[u][j], sc4[j], sh4[j]) > 0.f ? 1.f : a.bb.slope);
-                            s1[j] += d;
-                            s2[j] = fmaf(d, y4[u][j], s2[j]);
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(out + (long)m * N + n) = v;
-                }
-            }
-        }
-        __syncthreads();
-        *reinterpret_cast<f32x4*>(Ts + rowi * BN + cq * 4) = s1;
-        *reinterpret_cast<f32x4*>(Ts + (RSTEP + rowi) * BN + cq * 4) = s2;
-        __syncthreads();
-        if (t < BN && n0 + t < N) {
-            float c1 = 0.f, c2 = 0.f;
-            for (int i = 0; i < RSTEP; ++i) c1 += Ts[i * BN + t], c2 += Ts[(RSTEP + i) * BN + t];
-            float* P = st_on ? a.stats : a.bb.part;
-            P[((long)bx * 2 + 0) * N + n0 + t] = c1;
-            P[((long)bx * 2 + 1) * N + n0 + t] = c2;
-        }
-        return;
-    }
-#pragma unroll
-    for (int tn = 0; tn < T::TN; ++tn) {
-        const int n = n0 + wn * T::TN * 32 + tn * 32 + l31;
-        if (n >= N) continue;
-        const float bv = (!to_slab && ep.bias) ? ep.bias[n] : 0.f;
-        const float sc = bb_on ? a.bb.scale[n] : 0.f, sh = bb_on ? a.bb.shift[n] : 0.f;
-        float s1 = 0.f, s2 = 0.f;
-        // all of the column's y values are requested BEFORE the first store: `out` and `y` may alias as far as the compiler
-        // knows, so a load placed after a store waits for it -- sixteen serial round trips per tile otherwise
-        float yv[T::TM * 16];
-        if (bb_on) {
-            const float* __restrict__ yp = a.bb.y;
-#pragma unroll
-            for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ml = wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    yv[tm * 16 + r] = (m0 + ml < M) ? yp[(long)(yrow0 + ml) * N + n] : 0.f;
-                }
-        }
-#pragma unroll
-        for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ml = wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;  // row inside the block
-                const int m = m0 + ml;
-                const float v = acc[tm * T::TN + tn][r];
-                if (m < M) {
-                    const float o = to_slab ? v : apply_act(v + bv, ep.act, ep.slope);
-                    out[(long)m * N + n] = o;
-                    if (st_on) {
-                        s1 += o;
-                        s2 = fmaf(o, o, s2);
-                    } else if (bb_on) {
-                        const float y1 = yv[tm * 16 + r];
-                        const float d = v * (fmaf(y1, sc, sh) > 0.f ? 1.f : a.bb.slope);
-                        s1 += d;
-                        s2 = fmaf(d, y1, s2);
-                    }
-                }
-            }
-        if (st_on || bb_on) {
-            s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 32, 64);
-            if (half == 0) {
-                float* P = st_on ? a.stats : a.bb.part;
-                P[(pidx * 2 + 0) * N + n] = s1;
-                P[(pidx * 2 + 1) * N + n] = s2;
-            }
-        }
-    }
+    const int SL = a.side_lds ? 1 : T::WM;  // partial slots per block (tile_epilogue)
+    static_assert(BM * (BN + 4) <= FwdSmem<BM, BN>::FLOATS, "the epilogue's tile fits the stage buffers");
+    const RowsFwd rows{m0, M, m0 - yrow0};
+    tile_epilogue<BM, BN>(a, rows, smem, acc, out, to_slab, n0, (long)bx * SL);
 }
 
 template <int BM, int BN, bool BF = false>
@@ -597,7 +637,6 @@ __device__ __forceinline__ void igemm2_bwd_body(const BwdArgs& a, float* __restr
     float* __restrict__ Y = a.Y;
     float* __restrict__ slab = a.slab;
     const Geom g = a.g;
-    const Epilogue ep = a.ep;
     const ClsSplit& scls = a.scls;  // indexed by a run-time class: stays in the kernel-argument segment (a local copy
     const ClsSplit& kps = a.kps;    // would be an alloca the compiler parks in LDS, 4 KiB per block)
     const long total = a.total;
@@ -786,205 +825,23 @@ __device__ __forceinline__ void igemm2_bwd_body(const BwdArgs& a, float* __restr
         pipeline(std::false_type{}, std::false_type{});
     }
 
-    const int lane = t & 63, half = lane >> 5, l31 = lane & 31;
     const bool to_slab = slab != nullptr;
     float* out = to_slab ? slab + (long)split * total : Y;
-    // fused BatchNorm side products of the stores (see igemm2_fwd_body); the output pixel p is computed once for both
-    const bool st_on = a.stats && !to_slab, bb_on = a.bb.y && !to_slab, am_on = actmul_on(a.am) && !to_slab;
-    const int SL = a.side_lds ? 1 : T::WM, sw = a.side_lds ? 0 : wm;  // partial slots per block, this wave's slot
-    long pidx = ((long)cls * a.stats_gx + bx) * SL + sw;
+    const bool bb_on = a.bb.y && !to_slab, am_on = actmul_on(a.am) && !to_slab;
+    const int SL = a.side_lds ? 1 : T::WM;  // partial slots per block (tile_epilogue)
+    long pidx = ((long)cls * a.stats_gx + bx) * SL;
     long ybase = 0;  // first pixel of the block's cotangent group
     if (am_on && a.am.y && a.am.gx_per_group > 0) ybase = (long)(bx / a.am.gx_per_group) * (a.am.per_group / N);
     if (bb_on) {
         // classes are equally large and no row block straddles two cotangent groups (host): group gi owns bpg row blocks of
         // every class; its partials are [gi * ppg, (gi + 1) * ppg), ordered (class, block in group, wave row)
         const int bpg = a.bb.ppg / (s * s * SL), gi = bx / bpg;
-        pidx = (long)gi * a.bb.ppg + ((long)cls * bpg + (bx - gi * bpg)) * SL + sw;
+        pidx = (long)gi * a.bb.ppg + ((long)cls * bpg + (bx - gi * bpg)) * SL;
         ybase = (long)gi * a.bb.rows_per_group;
     }
-    const bool lds_ep = am_on || (!st_on && !bb_on && (N & 3) == 0 &&
-                                  ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ep.bias)) & 15) == 0);
-    if (lds_ep) {  // epilogue through LDS in 16-byte pieces: see igemm2_fwd_body (rows are the class's pixels here)
-        constexpr int LDT = BN + 4, QPR = BN / 4;
-        static_assert(BM * LDT <= BwdSmem<BM, BN>::FLOATS, "tile fits the stage buffers");
-        float* Ts = smem;
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Ts[(wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + wn * T::TN * 32 + tn * 32 + l31] =
-                        acc[tm * T::TN + tn][r];
-        __syncthreads();
-        const float* __restrict__ yp = a.am.y;
-        const float* __restrict__ rp = a.am.res;
-        const int hwc = Hoc * Woc;
-        for (int q = t; q < BM * QPR; q += 256) {
-            const int row = q / QPR, n = n0 + (q - row * QPR) * 4, m = m0 + row;
-            if (m >= M || n >= N) continue;
-            const int img = fdiv(m, a.fd_hw[cls]), rem = m - img * hwc;
-            const int hc = fdiv(rem, a.fd_w[cls]), wc = rem - hc * Woc;
-            const long p = (long)(img * g.Ho + (hc * s + ph)) * g.Wo + (wc * s + pw);
-            f32x4 v = *reinterpret_cast<const f32x4*>(Ts + row * LDT + (n - n0));
-            if (!to_slab) {
-                if (ep.bias) v += *reinterpret_cast<const f32x4*>(ep.bias + n);
-                if (am_on) {
-                    if (yp) {
-                        const f32x4 y4 = *reinterpret_cast<const f32x4*>(yp + (p - ybase) * N + n);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] *= act_grad_from_out(y4[j], a.am.act, a.am.slope);
-                    }
-                    if (rp) v += *reinterpret_cast<const f32x4*>(rp + p * N + n);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = apply_act(v[j], ep.act, ep.slope);
-                }
-            }
-            *reinterpret_cast<f32x4*>(out + p * N + n) = v;
-        }
-        return;
-    }
-    if ((st_on || bb_on) && a.side_lds) {
-        // through-LDS epilogue with a BatchNorm side product: see igemm2_fwd_body (one partial pair per block)
-        constexpr int LDT = BN + 4, QPR = BN / 4, RSTEP = 256 / QPR;
-        float* Ts = smem;
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Ts[(wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + wn * T::TN * 32 + tn * 32 + l31] =
-                        acc[tm * T::TN + tn][r];
-        __syncthreads();
-        const int cq = t % QPR, rowi = t / QPR, n = n0 + cq * 4;
-        const int hwc = Hoc * Woc;
-        f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
-        if (n < N) {
-            const f32x4 b4 = ep.bias ? *reinterpret_cast<const f32x4*>(ep.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-            const f32x4 sc4 = bb_on ? *reinterpret_cast<const f32x4*>(a.bb.scale + n) : b4;
-            const f32x4 sh4 = bb_on ? *reinterpret_cast<const f32x4*>(a.bb.shift + n) : b4;
-            const float* __restrict__ yp = a.bb.y;
-            for (int rb = rowi; rb < BM; rb += 4 * RSTEP) {
-                f32x4 y4[4];
-                long px[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int row = rb + u * RSTEP, m = m0 + row;
-                    px[u] = -1;
-                    y4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (row < BM && m < M) {
-                        const int img = fdiv(m, a.fd_hw[cls]), rem = m - img * hwc;
-                        const int hc = fdiv(rem, a.fd_w[cls]), wc = rem - hc * Woc;
-                        px[u] = (long)(img * g.Ho + (hc * s + ph)) * g.Wo + (wc * s + pw);
-                        if (bb_on) y4[u] = *reinterpret_cast<const f32x4*>(yp + (px[u] - ybase) * N + n);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (px[u] < 0) continue;
-                    f32x4 v = *reinterpret_cast<const f32x4*>(Ts + (rb + u * RSTEP) * LDT + cq * 4);
-                    if (st_on) {
-                        v += b4;
-                        s1 += v;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) s2[j] = fmaf(v[j], v[j], s2[j]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float d = v[j] * (fmaf(y4[u][j], sc4[j], sh4[j]) > 0.f ? 1.f : a.bb.slope);
-                            s1[j] += d;
-                            s2[j] = fmaf(d, y4[u][j], s2[j]);
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(out + px[u] * N + n) = v;
-                }
-            }
-        }
-        __syncthreads();
-        *reinterpret_cast<f32x4*>(Ts + rowi * BN + cq * 4) = s1;
-        *reinterpret_cast<f32x4*>(Ts + (RSTEP + rowi) * BN + cq * 4) = s2;
-        __syncthreads();
-        if (t < BN && n0 + t < N) {
-            float c1 = 0.f, c2 = 0.f;
-            for (int i = 0; i < RSTEP; ++i) c1 += Ts[i * BN + t], c2 += Ts[(RSTEP + i) * BN + t];
-            float* P = st_on ? a.stats : a.bb.part;
-            P[(pidx * 2 + 0) * N + n0 + t] = c1;  // (side_lds: pidx is the block's one slot)
-            P[(pidx * 2 + 1) * N + n0 + t] = c2;
-        }
-        return;
-    }
-    float sc[T::TN], sh[T::TN], s1[T::TN], s2[T::TN];
-#pragma unroll
-    for (int tn = 0; tn < T::TN; ++tn) {
-        const int n = n0 + wn * T::TN * 32 + tn * 32 + l31;
-        sc[tn] = (bb_on && n < N) ? a.bb.scale[n] : 0.f;
-        sh[tn] = (bb_on && n < N) ? a.bb.shift[n] : 0.f;
-        s1[tn] = s2[tn] = 0.f;
-    }
-    // output pixel of every accumulator row, computed once (three integer divisions each); -1 = past the class's rows
-    int pix[T::TM * 16];
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int hw = Hoc * Woc;
-            const int img = fdiv(m, a.fd_hw[cls]), rem = m - img * hw;
-            const int hc = fdiv(rem, a.fd_w[cls]), wc = rem - hc * Woc;
-            pix[tm * 16 + r] = m < M ? (img * g.Ho + (hc * s + ph)) * g.Wo + (wc * s + pw) : -1;
-        }
-    // BnBwd: every y value is requested before the first store (see igemm2_fwd_body)
-    float yv[T::TM * 16 * T::TN];
-    if (bb_on) {
-        const float* __restrict__ yp = a.bb.y;
-#pragma unroll
-        for (int i = 0; i < T::TM * 16; ++i)
-#pragma unroll
-            for (int tn = 0; tn < T::TN; ++tn) {
-                const int n = n0 + wn * T::TN * 32 + tn * 32 + l31;
-                yv[i * T::TN + tn] = (pix[i] >= 0 && n < N) ? yp[((long)pix[i] - ybase) * N + n] : 0.f;
-            }
-    }
-#pragma unroll
-    for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int pi = pix[tm * 16 + r];
-            if (pi < 0) continue;
-            const long p = pi;
-#pragma unroll
-            for (int tn = 0; tn < T::TN; ++tn) {
-                const int n = n0 + wn * T::TN * 32 + tn * 32 + l31;
-                if (n >= N) continue;
-                const float bv = (!to_slab && ep.bias) ? ep.bias[n] : 0.f;
-                const float v = acc[tm * T::TN + tn][r];
-                const float o = to_slab ? v : apply_act(v + bv, ep.act, ep.slope);
-                out[p * N + n] = o;
-                if (st_on) {
-                    s1[tn] += o;
-                    s2[tn] = fmaf(o, o, s2[tn]);
-                } else if (bb_on) {
-                    const float y1 = yv[(tm * 16 + r) * T::TN + tn];
-                    const float d = v * (fmaf(y1, sc[tn], sh[tn]) > 0.f ? 1.f : a.bb.slope);
-                    s1[tn] += d;
-                    s2[tn] = fmaf(d, y1, s2[tn]);
-                }
-            }
-        }
-    if (st_on || bb_on) {
-        float* P = st_on ? a.stats : a.bb.part;
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn) {
-            const int n = n0 + wn * T::TN * 32 + tn * 32 + l31;
-            const float t1 = s1[tn] + __shfl_xor(s1[tn], 32, 64), t2 = s2[tn] + __shfl_xor(s2[tn], 32, 64);
-            if (half == 0 && n < N) {
-                P[(pidx * 2 + 0) * N + n] = t1;
-                P[(pidx * 2 + 1) * N + n] = t2;
-            }
-        }
-    }
+    static_assert(BM * (BN + 4) <= BwdSmem<BM, BN>::FLOATS, "the epilogue's tile fits the stage buffers");
+    const RowsBwd rows{m0, M, hwc, Woc, s, ph, pw, g.Ho, g.Wo, a.fd_hw[cls], a.fd_w[cls], ybase};
+    tile_epilogue<BM, BN>(a, rows, smem, acc, out, to_slab, n0, pidx);
 }
 
 template <int BM, int BN, bool BF = false>
@@ -1258,21 +1115,13 @@ __device__ __forceinline__ void igemm2_wgrad_body(const WgArgs& a, float* __rest
         }
     }
 
-    const int lane = t & 63, half = lane >> 5, l31 = lane & 31;
     float* dst = to_slab ? out + (long)bz * a.slab_stride : a.tab.p[grp];
-    if ((N & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {  // through LDS in 16-byte pieces (see igemm2_fwd_body)
+    if ((N & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {  // through LDS in 16-byte pieces (see tile_epilogue)
         constexpr int LDT = BN + 4, QPR = BN / 4;
         static_assert(BM * LDT <= WgSmem<BM, BN>::FLOATS, "tile fits the stage buffers");
         __syncthreads();  // (the column-sum fold above may still be reading LDS)
         float* Ts = smem;
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Ts[(wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * LDT + wn * T::TN * 32 + tn * 32 + l31] =
-                        acc[tm * T::TN + tn][r];
+        acc_to_lds<BM, BN>(Ts, acc);
         __syncthreads();
         for (int q = t; q < BM * QPR; q += 256) {
             const int row = q / QPR, n = n0 + (q - row * QPR) * 4, m = m0 + row;
@@ -1280,6 +1129,7 @@ __device__ __forceinline__ void igemm2_wgrad_body(const WgArgs& a, float* __rest
         }
         return;
     }
+    const int lane = t & 63, half = lane >> 5, l31 = lane & 31;
 #pragma unroll
     for (int tn = 0; tn < T::TN; ++tn) {
         const int n = n0 + wn * T::TN * 32 + tn * 32 + l31;
@@ -1288,7 +1138,7 @@ __device__ __forceinline__ void igemm2_wgrad_body(const WgArgs& a, float* __rest
         for (int tm = 0; tm < T::TM; ++tm)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * T::TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int m = acc_row(r, half, m0 + wm * T::TM * 32 + tm * 32);
                 if (m < M) dst[(long)m * N + n] = acc[tm * T::TN + tn][r];
             }
     }
@@ -1375,30 +1225,60 @@ struct KPairHooks {
 };
 static KPairHooks g_kpair{nullptr, nullptr, nullptr};
 
-inline int finish_pending(hipStream_t st) {  // the stashed dgrad's reduce
-    PendingDgrad& p = g_pending;
-    if (!p.reduce || g_bench_main_only) return MOVAE_OK;
-    if (p.form == 0) {
-        const FwdArgs& a = p.fa;
-        if (p.rbb.y) {
-            launch_reduce_bnbwd(a.slab, a.Y, a.M, a.g.Nn, p.S, nullptr, 0, 0, 0, p.rbb, p.rbb_rpb, st);
-            MOVAE_CHECK_LAUNCH("splitk_reduce_stats (bn bwd)");
-            return MOVAE_OK;
-        }
-        return launch_reduce(a.slab, a.Y, (long)a.M * a.g.Nn, p.S, a.g.Nn, a.ep.bias, a.ep.act, a.ep.slope, 0, st, nullptr, 0, p.ram);
-    }
-    const BwdArgs& a = p.ba;
-    if (p.rbb.y) {
-        launch_reduce_bnbwd(a.slab, a.Y, (long)a.g.Nimg * a.g.Ho * a.g.Wo, a.g.Nn, p.S, &a.scls, a.g.Ho, a.g.Wo, a.g.stride, p.rbb, p.rbb_rpb, st);
+// The main launch of a split-K plan wrote S > 1 slabs: the ONE reduce that turns them into the result, for both gather forms
+// (BwdArgs: per-class split factors, rows are output pixels).  In order of precedence: with the backward sums of a fused
+// BatchNorm (rbb, planned by the launcher), with the statistics of the result (want_stats; where the shape does not fit that
+// kernel no statistics are produced), else plain or with the ActMul `ram`.
+template <class Args>
+int finish_splitk(const Args& a, int S, const BnBwd& rbb, int rbb_rpb, const ActMul& ram, bool want_stats, hipStream_t st) {
+    if (S <= 1 || g_bench_main_only) return MOVAE_OK;
+    constexpr bool CLS = std::is_same<Args, BwdArgs>::value;
+    const Geom& g = a.g;
+    long rows;
+    const ClsSplit* scls = nullptr;
+    if constexpr (CLS) rows = (long)g.Nimg * g.Ho * g.Wo, scls = &a.scls;
+    else rows = a.M;
+    const int Ho = CLS ? g.Ho : 0, Wo = CLS ? g.Wo : 0, stride = CLS ? g.stride : 0;
+    if (rbb.y) {
+        launch_reduce_bnbwd(a.slab, a.Y, rows, g.Nn, S, scls, Ho, Wo, stride, rbb, rbb_rpb, st);
         MOVAE_CHECK_LAUNCH("splitk_reduce_stats (bn bwd)");
         return MOVAE_OK;
     }
-    long gq = (a.total / 4 + 255) / 256;
-    if (gq > 4096) gq = 4096;
-    hipLaunchKernelGGL(splitk_reduce_cls, dim3((unsigned)gq), dim3(256), 0, st, a.slab, a.Y, a.total, a.g.Nn, a.g.Ho, a.g.Wo, a.g.stride,
-                       a.scls, a.ep.bias, a.ep.act, a.ep.slope, p.ram);
-    MOVAE_CHECK_LAUNCH("splitk_reduce_cls");
-    return MOVAE_OK;
+    if (want_stats && launch_reduce_stats(a.slab, a.Y, rows, g.Nn, S, scls, Ho, Wo, stride, a.ep.bias, st)) {
+        MOVAE_CHECK_LAUNCH("splitk_reduce_stats");
+        return MOVAE_OK;
+    }
+    if constexpr (CLS) {
+        long gq = (a.total / 4 + 255) / 256;
+        if (gq > 4096) gq = 4096;
+        hipLaunchKernelGGL(splitk_reduce_cls, dim3((unsigned)gq), dim3(256), 0, st, a.slab, a.Y, a.total, g.Nn, g.Ho, g.Wo, g.stride, a.scls,
+                           a.ep.bias, a.ep.act, a.ep.slope, ram);
+        MOVAE_CHECK_LAUNCH("splitk_reduce_cls");
+        return MOVAE_OK;
+    } else {
+        return launch_reduce(a.slab, a.Y, rows * g.Nn, S, g.Nn, a.ep.bias, a.ep.act, a.ep.slope, 0, st, nullptr, 0, ram);
+    }
+}
+
+// What the BatchNorm side products of a launch need from the host: are statistics of the result wanted (for the BatchNorm that
+// follows; never on a backward pass: those are the paired / collected ones), do the side products leave through the LDS tile
+// epilogue, where its 16-byte pieces apply, and how many partial slots a block then owns (one; else one per wave row).
+struct SidePlan {
+    bool want_stats;
+    int side_lds, slots;
+};
+template <int BM, int BN>
+SidePlan side_plan(const float* Y, const Epilogue& ep, int Nn) {
+    const int lds = (Nn % 4 == 0 && ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias) |
+                                      reinterpret_cast<uintptr_t>(g_fuse.bn_y)) & 15) == 0) ? 1 : 0;
+    return SidePlan{g_fuse.stats && ep.act == MOVAE_ACT_NONE && !g_pair_collect, lds, lds ? 1 : T2<BM, BN>::WM};
+}
+
+// the stashed dgrad's reduce: never with statistics -- a dgrad is stashed under g_pair_collect only, where side_plan wants none
+inline int finish_pending(hipStream_t st) {
+    const PendingDgrad& p = g_pending;
+    if (!p.reduce) return MOVAE_OK;
+    return p.form == 0 ? finish_splitk(p.fa, p.S, p.rbb, p.rbb_rpb, p.ram, false, st) : finish_splitk(p.ba, p.S, p.rbb, p.rbb_rpb, p.ram, false, st);
 }
 
 inline int flush_pending(hipStream_t st) {  // launch the stashed dgrad on its own
@@ -1433,12 +1313,10 @@ int launch_fwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     FwdArgs a{X, W, Y, g, ep, M, K, per_split, slab};
     a.fd_cr = fastdiv_make(g.Cr), a.fd_kw = fastdiv_make(g.KW), a.fd_wlen = fastdiv_make(g.wlen > 0 ? g.wlen : 1);
     a.nrm = g_fuse.nrm;
-    // statistics of the result for the BatchNorm that follows (never on a backward pass: those are the paired / collected ones)
-    const bool want_stats = g_fuse.stats && ep.act == MOVAE_ACT_NONE && !g_pair_collect;
-    // BatchNorm side products through the LDS tile epilogue (one partial pair per block) where its 16-byte pieces apply
-    a.side_lds = (g.Nn % 4 == 0 && ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias) |
-                                     reinterpret_cast<uintptr_t>(g_fuse.bn_y)) & 15) == 0) ? 1 : 0;
-    const int slots = a.side_lds ? 1 : T2<BM, BN>::WM;
+    const SidePlan sp = side_plan<BM, BN>(Y, ep, g.Nn);
+    const bool want_stats = sp.want_stats;
+    const int slots = sp.slots;
+    a.side_lds = sp.side_lds;
     if (want_stats && S == 1) a.stats = fuse_stats_claim((long)gx * slots, g.Nn);
     // the result is a fused BatchNorm's output gradient: its backward sums from the epilogue (unsplit) or from the reduce
     BnBwd rbb{};
@@ -1484,19 +1362,7 @@ int launch_fwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_fwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
     else hipLaunchKernelGGL((igemm2_fwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_fwd");
-    if (S > 1) {
-        if (rbb.y && !g_bench_main_only) {
-            launch_reduce_bnbwd(slab, Y, M, g.Nn, S, nullptr, 0, 0, 0, rbb, rbb_rpb, st);
-            MOVAE_CHECK_LAUNCH("splitk_reduce_stats (bn bwd)");
-            return MOVAE_OK;
-        }
-        if (want_stats && !g_bench_main_only && launch_reduce_stats(slab, Y, M, g.Nn, S, nullptr, 0, 0, 0, ep.bias, st)) {
-            MOVAE_CHECK_LAUNCH("splitk_reduce_stats");
-            return MOVAE_OK;
-        }
-        return launch_reduce(slab, Y, (long)M * g.Nn, S, g.Nn, ep.bias, ep.act, ep.slope, 0, st, nullptr, 0, ram);
-    }
-    return MOVAE_OK;
+    return finish_splitk(a, S, rbb, rbb_rpb, ram, want_stats, st);
 }
 
 template <int BM, int BN>
@@ -1566,10 +1432,10 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     }
     a.nrm = g_fuse.nrm;
     a.stats_gx = gx;
-    const bool want_stats = g_fuse.stats && ep.act == MOVAE_ACT_NONE && !g_pair_collect;
-    a.side_lds = (g.Nn % 4 == 0 && ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias) |
-                                     reinterpret_cast<uintptr_t>(g_fuse.bn_y)) & 15) == 0) ? 1 : 0;  // (see launch_fwd2)
-    const int slots = a.side_lds ? 1 : T2<BM, BN>::WM;
+    const SidePlan sp = side_plan<BM, BN>(Y, ep, g.Nn);
+    const bool want_stats = sp.want_stats;
+    const int slots = sp.slots;
+    a.side_lds = sp.side_lds;
     if (want_stats && Sreal == 1) a.stats = fuse_stats_claim((long)ncls * gx * slots, g.Nn);
     BnBwd rbb{};
     int rbb_rpb = 0;
@@ -1623,23 +1489,7 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_bwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
     else hipLaunchKernelGGL((igemm2_bwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_bwd");
-    if (Sreal > 1 && !g_bench_main_only) {
-        if (rbb.y) {
-            launch_reduce_bnbwd(slab, Y, (long)g.Nimg * g.Ho * g.Wo, g.Nn, Sreal, &scls, g.Ho, g.Wo, s, rbb, rbb_rpb, st);
-            MOVAE_CHECK_LAUNCH("splitk_reduce_stats (bn bwd)");
-            return MOVAE_OK;
-        }
-        if (want_stats && launch_reduce_stats(slab, Y, (long)g.Nimg * g.Ho * g.Wo, g.Nn, Sreal, &scls, g.Ho, g.Wo, s, ep.bias, st)) {
-            MOVAE_CHECK_LAUNCH("splitk_reduce_stats");
-            return MOVAE_OK;
-        }
-        long gq = (total / 4 + 255) / 256;
-        if (gq > 4096) gq = 4096;
-        hipLaunchKernelGGL(splitk_reduce_cls, dim3((unsigned)gq), dim3(256), 0, st, slab, Y, total, g.Nn, g.Ho, g.Wo, s, scls, ep.bias,
-                           ep.act, ep.slope, ram);
-        MOVAE_CHECK_LAUNCH("splitk_reduce_cls");
-    }
-    return MOVAE_OK;
+    return finish_splitk(a, Sreal, rbb, rbb_rpb, ram, want_stats, st);
 }
 
 template <int FORM, int ABM, int ABN, int WBM, int WBN>
