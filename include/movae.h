@@ -210,6 +210,46 @@ int movae_recursive_losses_bwd(const float* recons, const float* inputs, size_t 
                                const float* z_prior, const float* mu_gen, int b, int d, float w_rec, float w_kl, float w_cyc,
                                const float* anneal_dev, const float* g_rec, const float* g_kl, const float* g_cyc, const float* g_tot,
                                float* drecons, float* dmu_hat, float* dlog_var_hat, float* dmu_gen, movae_stream_t stream);
+/* ---- the conv Sphere Encoder (models/sphere_encoder.py) -------------------------------------------------------------------------
+ * movae_sphere_latents_fwd: everything between encoder_proj and the two decoder calls in one launch.  With n(x) = radius * x /
+ * sqrt(mean(x^2) + eps) per row of z[b][l]:
+ *     v = n(z);   deg = u0 * angle_max, or mix_min + u2 * (mix_max - mix_min) where mix_prob > 0 and u1 < mix_prob;
+ *     sigma = tan(deg * pi / 180);  sigma_sub = (0.5 * u3) * sigma;   v_noisy = n(v + sigma * e);   v_noisy_small = n(v + sigma_sub * e)
+ * u[b][4] = (angle, mix mask, mix angle, s) uniforms and e[b][l] the noise direction.  Modes:
+ *   schedule     e and u given (state null, fixed_sigma 0);
+ *   in-kernel    state = device uint64[2] {seed, draws}: e and u are DRAWN in the launch (Philox4x32-10 keyed by the seed; per row
+ *                ceil(l / 4) counter blocks of e through Box-Muller, then one of u) and written out for the backward; advance != 0:
+ *                state[1] += 1 by the block that finishes last.  One such call at a time per process (the arrival count is a device
+ *                global), as for movae_reparam_rng_fwd;
+ *   given sigma  fixed_sigma != 0: sigma_in[b] (sigma_rows != 0), sigma_in[0], or sigma_val when sigma_in is null; e given; produces
+ *                v_noisy (and v when asked), no v_noisy_small;
+ *   clean        e null: v only.
+ * Outputs are nullable; inv_rms[3][b] keeps 1 / rms of z, w, w' for the backward.  l <= 16384.
+ * movae_sphere_latents_bwd: dz = nT(g_v + nT(g_noisy; w) + nT(g_small; w'); z) with nT(g; x) = radius * (g / rms - x * (g . x) /
+ * (l * rms^3)), w and w' recomputed from v, e and sigma; the cotangents are nullable (e / sigma only needed with theirs); the
+ * noise terms carry no gradient. */
+int movae_sphere_latents_fwd(const float* z, float* e, float* u, const float* sigma_in, int sigma_rows, float sigma_val, int fixed_sigma,
+                             unsigned long long* state, int advance, int b, int l, float angle_max_deg, float mix_prob, float mix_min_deg,
+                             float mix_max_deg, float radius, float eps, float* v, float* v_noisy, float* v_noisy_small, float* sigma,
+                             float* sigma_sub, float* inv_rms, movae_stream_t stream);
+int movae_sphere_latents_bwd(const float* v, const float* e, const float* sigma, const float* sigma_sub, const float* inv_rms,
+                             const float* g_v, const float* g_noisy, const float* g_small, float* dz, int b, int l, float radius,
+                             movae_stream_t stream);
+/* SphereEncoder.loss_function in two launches: out[4] = (lam_rec * (w_rec_sl1 * mean smooth_l1(recons - inputs)), lam_con * (w_con_sl1 *
+ * mean smooth_l1(x_noisy - sg)), lam_lat * mean_b(1 - cos(v, v_enc_dec)), their fp32 sum in that order); sg = recons_sg, or recons
+ * itself when recons_sg is null (recons is then read once for both pixel terms); smooth-L1 with beta = 1; the cosine with
+ * F.cosine_similarity's clamp of each norm at 1e-8.  n image elements in one memory order, v / v_enc_dec [b][l].
+ * ws >= movae_sphere_losses_ws_bytes(n, b).  The backward serves the present cotangents g_* (device scalars, nullable; g_tot reaches
+ * every term) and writes the outputs given (nullable): drecons from pix_recon alone (pix_con's target is a constant), dx_noisy,
+ * dv, dv_enc_dec. */
+size_t movae_sphere_losses_ws_bytes(size_t n, int b);
+int movae_sphere_losses_fwd(const float* recons, const float* inputs, const float* x_noisy, const float* recons_sg, size_t n, const float* v,
+                            const float* v_enc_dec, int b, int l, float lam_rec, float w_rec_sl1, float lam_con, float w_con_sl1,
+                            float lam_lat, float* out, void* ws, size_t ws_bytes, movae_stream_t stream);
+int movae_sphere_losses_bwd(const float* recons, const float* inputs, const float* x_noisy, const float* recons_sg, size_t n, const float* v,
+                            const float* v_enc_dec, int b, int l, float lam_rec, float w_rec_sl1, float lam_con, float w_con_sl1,
+                            float lam_lat, const float* g_rec, const float* g_con, const float* g_lat, const float* g_tot, float* drecons,
+                            float* dx_noisy, float* dv, float* dv_enc_dec, movae_stream_t stream);
 int movae_kl_bwd(const float* mu, const float* log_var, const float* gscale_dev, float* dmu, float* dlog_var,
                  int b, int d, float scale, movae_stream_t stream);
 /* Beta-TC decomposition: models/betatc_vae.py:262-296.  out[0..2] = mi, tc, kld (unweighted means).

@@ -79,6 +79,11 @@ SIGNATURES = {
     "movae_kl_bwd": ([_p, _p, _p, _p, _p, _i, _i, _f, _p], _i),
     "movae_recursive_losses_fwd": ([_p, _p, _z, _i, _p, _p, _p, _p, _i, _i, _f, _f, _f, _p, _f, _f, _i, _p, _p, _p, _z, _p], _i),
     "movae_recursive_losses_bwd": ([_p, _p, _z, _i, _p, _p, _p, _p, _i, _i, _f, _f, _f] + [_p] * 9 + [_p], _i),
+    "movae_sphere_latents_fwd": ([_p, _p, _p, _p, _i, _f, _i, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f] + [_p] * 6 + [_p], _i),
+    "movae_sphere_latents_bwd": ([_p] * 9 + [_i, _i, _f, _p], _i),
+    "movae_sphere_losses_ws_bytes": ([_z, _i], _z),
+    "movae_sphere_losses_fwd": ([_p, _p, _p, _p, _z, _p, _p, _i, _i, _f, _f, _f, _f, _f, _p, _p, _z, _p], _i),
+    "movae_sphere_losses_bwd": ([_p, _p, _p, _p, _z, _p, _p, _i, _i, _f, _f, _f, _f, _f] + [_p] * 8 + [_p], _i),
     "movae_tc_decomp_fwd": ([_p] * 7 + [_i, _i, _p, _z, _p], _i),
     "movae_tc_decomp_bwd": ([_p] * 10 + [_i, _i, _p], _i),
     "movae_edge_weights": ([_p, _p, _p, _i, _i, _i, _i, _p, _z, _p], _i),
@@ -227,7 +232,7 @@ DEFER_PASS = frozenset(
     ["movae_bn_bwd_finalize", "movae_bn_bwd_apply", "movae_bn_bwd_finalize_apply", "movae_bn_act_bwd", "movae_bn_act_bwd_grouped",
      "movae_act_bwd", "movae_act_bwd_bias_grouped", "movae_colsum", "movae_add", "movae_axpby", "movae_copy_channels", "movae_mul",
      "movae_nchw_to_nhwc", "movae_nhwc_to_nchw", "movae_reparam_bwd", "movae_kl_bwd", "movae_recon_loss_bwd", "movae_recon_loss_bwd_act", "movae_recursive_losses_bwd",
-     "movae_tc_decomp_bwd",
+     "movae_tc_decomp_bwd", "movae_sphere_latents_bwd", "movae_sphere_losses_bwd",
      "movae_combine_losses_bwd", "movae_vq_bwd", "movae_linear_pair_bwd", "movae_edge_weighted_mse_bwd", "movae_edge_match_bwd",
      "movae_gated_residual_bwd"])
 _defer_arena = [0]

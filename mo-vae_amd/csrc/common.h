@@ -98,7 +98,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // Philox4x32-10 (Salmon et al., SC'11; the counter-based generator family torch / cuRAND / rocRAND use): four 32-bit words of
 // counter (c0..c3) under key (k0, k1).  Shared by the reparameterisation draws (eltwise.hip) and the attention dropout mask
-// (attention.hip).
+// (attention.hip); unit_open / normal4 below turn its words into the uniforms and standard normals of the in-kernel noise draws
+// (eltwise.hip, sphere.hip).
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -108,6 +109,22 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
         k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
     }
     out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+__device__ __forceinline__ float unit_open(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.f / 16777216.f); }  // (0, 1), 24 bits
+
+// four standard normals of counter block (quad q, draw number): the Philox words through Box-Muller
+__device__ __forceinline__ void normal4(long q, unsigned long long draw, unsigned long long seed, float e[4]) {
+    unsigned w[4];
+    philox4x32_10((unsigned)q, (unsigned)((unsigned long long)q >> 32), (unsigned)draw, (unsigned)(draw >> 32), (unsigned)seed,
+                  (unsigned)(seed >> 32), w);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float r = sqrtf(-2.f * logf(unit_open(w[2 * h]))), t = 6.28318530717958647692f * unit_open(w[2 * h + 1]);
+        float sn, cs;
+        sincosf(t, &sn, &cs);
+        e[2 * h] = r * cs, e[2 * h + 1] = r * sn;
+    }
 }
 
 // block-wide sum for 256-thread blocks; result valid in every thread

@@ -265,22 +265,6 @@ __global__ void reparam_fwd_k(const float* __restrict__ mu, const float* __restr
 // last (g_reparam_done), so a replayed graph draws fresh noise every time.  eps is written out for the backward.
 __device__ unsigned g_reparam_done = 0;
 
-__device__ __forceinline__ float unit_open(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.f / 16777216.f); }  // (0, 1), 24 bits
-
-// four standard normals of counter block (quad q, draw number): the Philox words through Box-Muller
-__device__ __forceinline__ void normal4(long q, unsigned long long draw, unsigned long long seed, float e[4]) {
-    unsigned w[4];
-    philox4x32_10((unsigned)q, (unsigned)((unsigned long long)q >> 32), (unsigned)draw, (unsigned)(draw >> 32), (unsigned)seed,
-                  (unsigned)(seed >> 32), w);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float r = sqrtf(-2.f * logf(unit_open(w[2 * h]))), t = 6.28318530717958647692f * unit_open(w[2 * h + 1]);
-        float sn, cs;
-        sincosf(t, &sn, &cs);
-        e[2 * h] = r * cs, e[2 * h + 1] = r * sn;
-    }
-}
-
 // quads [0, ceil(n / 4)) draw eps (and z); with `prior`, the quads that follow draw prior[0 .. n_prior) -- the cycle branch's
 // z_prior of the recursive-cyclic VAEs -- from the same draw number: one launch and one counter advance for both
 __global__ __launch_bounds__(256) void reparam_rng_fwd_k(const float* __restrict__ mu, const float* __restrict__ lv, float* __restrict__ eps,

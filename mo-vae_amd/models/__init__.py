@@ -7,6 +7,7 @@ from .gg_vq_vae import GGVQVAE
 from .gg_vq_vae2 import GGVQVAE2
 from .pixelcnn_prior import HierarchicalPixelCNN, HierarchicalPixelSNAIL, PixelCNN, PixelSNAIL
 from .recursive_vaes import CycleVAE, RecursiveCyclicVAE, RecursiveKLVAE
+from .sphere_encoder import SphereEncoder
 from .vae import VAE
 from .vq_vae import VQVAE, VectorQuantizer
 from .vq_vae2 import VQVAE2
@@ -120,5 +121,20 @@ def get_network(input_size, num_channels=3, args=None, device=None):
     raise ValueError(f"Network architecture {arch} not supported")
 
 
+def build_sphere_encoder(input_size, num_channels=3, args=None, device=None, use_perceptual=False):
+    """The conv Sphere Encoder from the arguments the reference's factory reads for `--arch sphere_encoder` (models/__init__.py:80-106).
+    get_network still refuses that architecture: the reference's factory leaves use_perceptual at True, which needs the pretrained
+    VGG16; this builder is the way in until the CLI switch follows."""
+    return SphereEncoder(
+        latent_dim=getattr(args, "latent_dim", 128), hidden_dims=getattr(args, "hidden_dims", [32, 64, 128, 256, 512]),
+        input_size=input_size, in_channels=num_channels, recons_objective=_recons_objective(args),
+        recons_activation=getattr(args, "recons_activation", None), lambda_weights=[1.0, 0.0],
+        sigma_max_angle_deg=getattr(args, "sigma_max_angle_deg", 80.0), sigma_mix_prob=getattr(args, "sigma_mix_prob", 0.0),
+        sigma_mix_angle_min_deg=getattr(args, "sigma_mix_angle_min_deg", None),
+        sigma_mix_angle_max_deg=getattr(args, "sigma_mix_angle_max_deg", None), lambda_pix_recon=getattr(args, "lambda_pix_recon", 1.0),
+        lambda_pix_con=getattr(args, "lambda_pix_con", 0.5), lambda_lat_con=getattr(args, "lambda_lat_con", 0.1),
+        use_perceptual=use_perceptual, device=device)
+
+
 __all__ = ["VAE", "VQVAE", "VQVAE2", "BetaTCVAE", "GGVAE", "GGVQVAE", "GGVQVAE2", "VectorQuantizer", "RecursiveKLVAE", "CycleVAE",
-           "RecursiveCyclicVAE", "PixelCNN", "HierarchicalPixelCNN", "PixelSNAIL", "HierarchicalPixelSNAIL", "get_network"]
+           "RecursiveCyclicVAE", "SphereEncoder", "build_sphere_encoder", "PixelCNN", "HierarchicalPixelCNN", "PixelSNAIL", "HierarchicalPixelSNAIL", "get_network"]

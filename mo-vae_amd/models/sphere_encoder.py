@@ -1,0 +1,157 @@
+"""The conv Sphere Encoder on the HIP kernels -- drop-in for the reference's models/sphere_encoder.py, class SphereEncoder (same
+constructor signature and defaults, state_dict keys and order, init RNG order, forward / loss_function dictionaries), without its
+optional perceptual term: that one needs pretrained VGG16 weights, so `use_perceptual=True` raises.
+
+The latent is RMS-normalised onto the sphere of radius sqrt(L); there is no KL term.  One step makes two encoder and two decoder
+passes: v = spherify(E(x)); a jitter angle per image gives sigma = tan(angle) and sigma_sub = s * sigma; recons = D(spherify(v +
+sigma_sub e)), x_recon_NOISY = D(spherify(v + sigma e)); v_enc_dec = spherify(E(x_recon_NOISY)).  The three objectives
+(pix_recon, pix_con, lat_con) each reach every parameter, so the Jacobian spans them all (`features is None`), as for
+models/recursive_vaes.py, whose plumbing this reuses: every encoder / decoder call runs BatchNorm in training mode (two updates of
+the running statistics per module per step, as in the reference), the decoder's output-activation link stays unused (recons and
+x_recon_NOISY have two readers each), and train pulls the Jacobian rows back from the loss op (autojac.backward_through).
+
+Everything between encoder_proj and the decoder calls is one launch (ops.SphereLatents), the loss_function two (ops.SphereLosses).
+The noise: eager mode draws with torch in the reference's order (rand, [rand, rand], rand, randn); `noise_override` = {"u": [B, 4],
+"e": [B, L]} replaces the draws (parity tests; u's columns are the angle, mix-mask, mix-angle and s uniforms); after
+prepare_for_graph the draws are made inside the SphereLatents launch.  Eval mode draws noise too, like the reference."""
+import math
+from math import sqrt
+
+import torch
+
+from .. import nn as mnn
+from .. import ops
+from ._base import nchw_view
+from .vae import VAE
+
+
+class SphereEncoder(VAE):
+    graph_safe = True
+    #: internal: every loss is an output of ops.SphereLosses, so train can pull the K Jacobian rows back from its inputs
+    _jacobian_from_loss_op = True
+    #: {"u": [B, 4], "e": [B, L]} to replace the draws of forward (parity tests)
+    noise_override = None
+
+    def __init__(self, latent_dim: int = 2048, sigma_max_angle_deg: float = 80.0, sigma_mix_prob: float = 0.0,
+                 sigma_mix_angle_min_deg=None, sigma_mix_angle_max_deg=None, lambda_pix_recon: float = 1.0, lambda_pix_con: float = 0.5,
+                 lambda_lat_con: float = 0.1, pix_recon_smooth_l1_weight: float = 1.0, pix_recon_perceptual_weight: float = 1.0,
+                 pix_con_smooth_l1_weight: float = 0.5, pix_con_perceptual_weight: float = 0.5, use_perceptual: bool = True, **kwargs):
+        if use_perceptual:
+            raise NotImplementedError("SphereEncoder(use_perceptual=True) needs the pretrained VGG16 weights of the reference's "
+                                      "PerceptualLoss, which this build does not carry (DESIGN.md section 7); pass use_perceptual=False")
+        super().__init__(latent_dim=latent_dim, **kwargs)
+        # models/sphere_encoder.py:102-107: the VAE's heads go, decoder_input is replaced in place, encoder_proj is registered last;
+        # the RNG draws follow the VAE's: encoder_proj, then the new decoder_input
+        feat = self.hidden_dims[-1] * (self.input_size // (2 ** len(self.hidden_dims))) ** 2
+        del self.mu
+        del self.log_var
+        self.encoder_proj = mnn.Linear(feat, latent_dim)
+        self.decoder_input = mnn.Linear(latent_dim, feat)
+
+        self.L = latent_dim
+        self.radius = sqrt(latent_dim)
+        self.sigma_max_angle_deg = float(sigma_max_angle_deg)
+        self.sigma_max = math.tan(math.radians(self.sigma_max_angle_deg))
+        self.sigma_mix_prob = float(sigma_mix_prob)
+        self.sigma_mix_angle_min_deg = float(sigma_mix_angle_min_deg) if sigma_mix_angle_min_deg is not None else None
+        self.sigma_mix_angle_max_deg = float(sigma_mix_angle_max_deg) if sigma_mix_angle_max_deg is not None else None
+        self.lambda_pix_recon, self.lambda_pix_con, self.lambda_lat_con = lambda_pix_recon, lambda_pix_con, lambda_lat_con
+        self.pix_recon_smooth_l1_weight, self.pix_recon_perceptual_weight = pix_recon_smooth_l1_weight, pix_recon_perceptual_weight
+        self.pix_con_smooth_l1_weight, self.pix_con_perceptual_weight = pix_con_smooth_l1_weight, pix_con_perceptual_weight
+        self.use_perceptual, self.perceptual_loss = False, None
+        # objectives for MTL / logging (models/sphere_encoder.py:133-137: placeholders; loss_function computes the terms)
+        zero = lambda *_: torch.tensor(0.0, device=next(self.parameters()).device)  # noqa: E731
+        self.objectives = {"pix_recon": zero, "pix_con": zero, "lat_con": zero}
+        self.features = None  # every objective reaches every parameter
+
+    # -- the noise schedule ------------------------------------------------------------------------------------------------------
+    def _mix_enabled(self):
+        lo, hi = self.sigma_mix_angle_min_deg, self.sigma_mix_angle_max_deg
+        return self.sigma_mix_prob > 0 and lo is not None and hi is not None and hi > lo
+
+    def _schedule(self):
+        """(angle_max_deg, mix_prob or 0, mix_min_deg, mix_max_deg) of ops.SphereLatents"""
+        if self._mix_enabled():
+            return (self.sigma_max_angle_deg, self.sigma_mix_prob, self.sigma_mix_angle_min_deg, self.sigma_mix_angle_max_deg)
+        return (self.sigma_max_angle_deg, 0.0, 0.0, 0.0)
+
+    def _draws(self, batch, device, dtype):
+        """(u [B, 4], e [B, L]) from noise_override or from torch in the reference's order (models/sphere_encoder.py:203-218)."""
+        if self.noise_override is not None:
+            return tuple(self.noise_override[k].to(device=device, dtype=dtype) for k in ("u", "e"))
+        zero = torch.zeros(batch, 1, device=device, dtype=dtype)
+        angle = torch.rand(batch, 1, device=device, dtype=dtype)
+        mask, mix = (torch.rand(batch, 1, device=device), torch.rand(batch, 1, device=device, dtype=dtype)) if self._mix_enabled() else (zero, zero)
+        s = torch.rand(batch, 1, device=device, dtype=dtype)
+        e = torch.randn(batch, self.L, device=device, dtype=dtype)
+        return torch.cat([angle, mask.to(dtype), mix, s], dim=1), e
+
+    # -- reference API -----------------------------------------------------------------------------------------------------------
+    def encode_to_vector(self, x):
+        """Encode to the flat vector (before spherify)."""
+        return self.encoder_proj(self.encoder(ops.to_nhwc(x)))
+
+    def spherify(self, z, add_noise=False, sigma=None, e=None):
+        """Project z onto the sphere; with add_noise, sigma and e: spherify(spherify(z) + sigma * e) (the noise is added to the
+        already-spherified v, models/sphere_encoder.py:146-162).  sigma: a number, or a tensor of 1 or B values."""
+        if add_noise and sigma is not None and e is not None:
+            return ops.spherify(z, self.radius, sigma, e)
+        return ops.spherify(z, self.radius)
+
+    def decode_from_sphere(self, v):
+        y = self.final_layer(self.decoder(self.decoder_input(v)))
+        self.final_layer._out_link = None  # the output activation's link stays unused (see the module docstring)
+        self._recons_link = None
+        return nchw_view(y)
+
+    def encode(self, x):
+        """(v,) on the sphere, for compatibility; no mu / log_var."""
+        return (self.spherify(self.encode_to_vector(x)),)
+
+    def reparameterize(self, mu, log_var):
+        return mu
+
+    def decode(self, z):
+        """Decode a latent: taken as it is when it lies on the sphere (norm within 1e-2 of the radius), else spherified first."""
+        if z.dim() == 1:
+            z = z.unsqueeze(0)
+        norm = z.norm(dim=-1, keepdim=True)
+        if not torch.allclose(norm, torch.full_like(norm, self.radius), atol=1e-2):
+            z = self.spherify(z)
+        return self.decode_from_sphere(z)
+
+    def forward(self, x):
+        z = self.encode_to_vector(x)
+        if self.noise_override is None and self.noise_on_device and z.is_cuda:
+            lat = ops.sphere_latents(z, self._schedule(), self.radius, state=self._noise_state(z.device))
+        else:
+            u, e = self._draws(x.size(0), z.device, z.dtype)
+            lat = ops.sphere_latents(z, self._schedule(), self.radius, e=e, u=u)
+        v, v_noisy, v_noisy_small, sigma, sigma_sub = lat[:5]
+        recons = self.decode_from_sphere(v_noisy_small)
+        x_recon_noisy = self.decode_from_sphere(v_noisy)
+        v_enc_dec = self.spherify(self.encode_to_vector(x_recon_noisy))  # (reuses x_recon_NOISY: no third decoder pass)
+        return {"recons": recons, "v": v, "v_noisy": v_noisy, "v_noisy_small": v_noisy_small, "x_recon_NOISY": x_recon_noisy,
+                "x_recon_noisy_small_sg": recons.detach(), "v_enc_dec": v_enc_dec, "sigma": sigma, "sigma_sub": sigma_sub}
+
+    def loss_function(self, inputs, args: dict) -> dict:
+        sg = args["x_recon_noisy_small_sg"]
+        vals = ops.sphere_losses(ops.to_nhwc(args["recons"]), ops.to_nhwc(inputs), ops.to_nhwc(args["x_recon_NOISY"]), args["v"],
+                                 args["v_enc_dec"], (self.lambda_pix_recon, self.lambda_pix_con, self.lambda_lat_con),
+                                 (self.pix_recon_smooth_l1_weight, self.pix_con_smooth_l1_weight), sg=ops.to_nhwc(sg.detach()))
+        return dict(zip(("pix_recon", "pix_con", "lat_con", "total_loss"), vals))
+
+    def sample(self, num_samples=1, device=None, steps=1, share_noise=True):
+        """One-step generation x = D(spherify(e)), e ~ N(0, I); steps > 1 iterates encode / decode at the fixed noise strength
+        sigma_max, with the same e in every step when share_noise (models/sphere_encoder.py:285-308)."""
+        if device is None:
+            device = next(self.parameters()).device
+        self.eval()
+        with torch.no_grad():
+            e = torch.randn(num_samples, self.L, device=device)
+            x = self.decode_from_sphere(self.spherify(e))
+            for _ in range(steps - 1):
+                z = self.encode_to_vector(x)
+                e_step = e if share_noise else torch.randn(num_samples, self.L, device=device)
+                x = self.decode_from_sphere(self.spherify(z, add_noise=True, sigma=self.sigma_max, e=e_step))
+        return x

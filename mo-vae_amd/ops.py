@@ -1650,6 +1650,191 @@ def recursive_losses(recons, inputs, kind, w_rec, mu_hat=None, log_var_hat=None,
     return RecursiveLosses.apply(recons, inputs, kind, w_rec, mu_hat, log_var_hat, w_kl, anneal, z_prior, mu_gen, w_cyc)
 
 
+# ---- the conv Sphere Encoder (models/sphere_encoder.py) ---------------------------------------------------------------------------
+SPHERE_EPS = 1e-6  # rms_norm's eps (models/sphere_encoder.py:23)
+
+
+def _p(t):
+    return t.data_ptr() if t is not None else 0
+
+
+def _sphere_fwd(z, e, u, sigma, state, sched, radius, want):
+    """One movae_sphere_latents_fwd launch on z[B][L].  `sigma`: None (the angle schedule from u, given or drawn), a float or a tensor of
+    1 or B values (given sigma).  `want`: which of (v, v_noisy, v_noisy_small) to produce.  -> dict of the buffers written."""
+    b, l = z.shape
+    new = lambda *shape: torch.empty(shape, dtype=z.dtype, device=z.device)  # noqa: E731
+    o = {"v": new(b, l) if want[0] else None, "vn": new(b, l) if want[1] else None, "vs": new(b, l) if want[2] else None,
+         "inv": new(3, b), "e": e, "u": u, "sigma": None, "sigma_sub": None}
+    fixed = sigma is not None
+    sig_t, sig_val = (sigma, 0.0) if isinstance(sigma, torch.Tensor) else (None, float(sigma) if fixed else 0.0)
+    if sig_t is not None:
+        sig_t = _c(sig_t.to(device=z.device, dtype=z.dtype).reshape(-1))
+        assert sig_t.numel() in (1, b), f"sigma must hold 1 or {b} values, got {sig_t.numel()}"
+    if state is not None:
+        assert state.dtype == torch.int64 and state.numel() == 2 and state.device == z.device
+        o["e"], o["u"] = new(b, l), new(b, 4)
+    if o["e"] is not None:
+        o["sigma"] = new(b, 1)
+        if not fixed:
+            o["sigma_sub"] = new(b, 1)
+            assert o["u"].shape == (b, 4) and o["u"].is_contiguous()
+        assert o["e"].shape == (b, l) and o["e"].is_contiguous()
+    angle_max, mix_prob, mix_min, mix_max = sched
+    _call("movae_sphere_latents_fwd", z.data_ptr(), _p(o["e"]), _p(None if fixed else o["u"]), _p(sig_t),
+          int(sig_t is not None and sig_t.numel() > 1), sig_val, int(fixed), _p(state), 1, b, l, float(angle_max), float(mix_prob),
+          float(mix_min), float(mix_max), float(radius), SPHERE_EPS, _p(o["v"]), _p(o["vn"]), _p(o["vs"]), _p(o["sigma"]),
+          _p(o["sigma_sub"]), o["inv"].data_ptr(), _st(z))
+    return o
+
+
+def _sphere_bwd(v, e, sigma, sigma_sub, inv, g_v, g_n, g_s, radius):
+    g_v, g_n, g_s = (None if g is None else _c(g) for g in (g_v, g_n, g_s))
+    dz = torch.empty_like(v)
+    b, l = v.shape
+    _call("movae_sphere_latents_bwd", v.data_ptr(), _p(e), _p(sigma), _p(sigma_sub), inv.data_ptr(), _p(g_v), _p(g_n), _p(g_s),
+          dz.data_ptr(), b, l, float(radius), _st(v))
+    return dz
+
+
+class SphereLatents(Function):
+    """Everything between SphereEncoder's encoder_proj and its two decoder calls (models/sphere_encoder.py:146-162, 196-220) in one
+    launch forward and one backward: v = spherify(z), the jitter angle per row -> sigma = tan(angle), sigma_sub = s * sigma, v_noisy =
+    spherify(v + sigma e), v_noisy_small = spherify(v + sigma_sub e).  `sched` = (angle_max_deg, mix_prob or 0, mix_min_deg,
+    mix_max_deg).  The draws: e [B, L] ~ N(0, I) and u [B, 4] ~ U[0, 1) (angle, mix mask, mix angle, s) are given, or -- `state`, a
+    device int64[2] = {seed, draws so far} advanced by the launch -- drawn inside it (graph mode; one such call at a time per
+    process, like ReparameterizeRNG).  Returns (v, v_noisy, v_noisy_small, sigma [B, 1], sigma_sub [B, 1], e, u); the last four are
+    constants of the tape.  The backward serves whichever of the three cotangents arrive."""
+
+    @staticmethod
+    def forward(ctx, z, e, u, state, sched, radius):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(z)
+        z = _c(z)
+        assert z.dim() == 2 and ((e is None) == (u is None)) and ((e is None) != (state is None)), "give e and u, or the generator state"
+        o = _sphere_fwd(z, None if e is None else _c(e), None if u is None else _c(u), None, state, sched, radius, (True, True, True))
+        ctx.radius = radius
+        ctx.save_for_backward(o["v"], o["e"], o["sigma"], o["sigma_sub"], o["inv"])
+        drawn = (o["e"], o["u"]) if state is not None else ()  # (given draws are the caller's own tensors: sphere_latents hands them back)
+        ctx.mark_non_differentiable(o["sigma"], o["sigma_sub"], *drawn)
+        return (o["v"], o["vn"], o["vs"], o["sigma"], o["sigma_sub"]) + (drawn or (None, None))
+
+    @staticmethod
+    def backward(ctx, g_v, g_n, g_s, *_):
+        if (g_v is None and g_n is None and g_s is None) or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        v, e, sigma, sigma_sub, inv = ctx.saved_tensors
+        return (_sphere_bwd(v, e, sigma, sigma_sub, inv, g_v, g_n, g_s, ctx.radius),) + (None,) * 5
+
+
+def sphere_latents(z, sched, radius, e=None, u=None, state=None):
+    """-> (v, v_noisy, v_noisy_small, sigma, sigma_sub, e, u)"""
+    out = SphereLatents.apply(z, e, u, state, sched, radius)
+    return out if state is not None else out[:5] + (e, u)
+
+
+class Spherify(Function):
+    """spherify(z) = radius * z / sqrt(mean(z^2) + 1e-6) per row (models/sphere_encoder.py:23-38) and, with `e` and `sigma` (a float, or a
+    tensor of 1 or B values), spherify(spherify(z) + sigma * e) (SphereEncoder.spherify with add_noise): the kernels of SphereLatents
+    in their clean / given-sigma modes.  sigma and e are constants of the tape."""
+
+    @staticmethod
+    def forward(ctx, z, radius, sigma, e):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(z)
+        z = _c(z)
+        assert z.dim() == 2 and (sigma is None) == (e is None)
+        noisy = e is not None
+        keep = noisy and ctx.needs_input_grad[0]  # (the backward recomputes w = v + sigma e from v)
+        o = _sphere_fwd(z, _c(e.to(device=z.device, dtype=z.dtype)) if noisy else None, None, sigma, None, (0.0, 0.0, 0.0, 0.0), radius,
+                        (not noisy or keep, noisy, False))
+        ctx.radius, ctx.noisy = radius, noisy
+        ctx.save_for_backward(o["v"], o["e"], o["sigma"], o["inv"])
+        return o["vn"] if noisy else o["v"]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * 4
+        v, e, sigma, inv = ctx.saved_tensors
+        dz = _sphere_bwd(v, e, sigma, None, inv, None, g, None, ctx.radius) if ctx.noisy else _sphere_bwd(v, None, None, None, inv, g, None, None, ctx.radius)
+        return dz, None, None, None
+
+
+def spherify(z, radius, sigma=None, e=None):
+    return Spherify.apply(z, radius, sigma, e)
+
+
+class SphereLosses(Function):
+    """SphereEncoder.loss_function (models/sphere_encoder.py:249-283, without the perceptual term) in two launches forward and one
+    backward: pix_recon = lam[0] * (w[0] * mean smooth_l1(recons - inputs)), pix_con = lam[1] * (w[1] * mean smooth_l1(x_noisy - sg)),
+    lat_con = lam[2] * mean_b(1 - cos(v, v_enc_dec)) and their fp32 sum, adjacent in one buffer.  `sg` is the reference's detached
+    reconstruction: None, or a tensor that shares recons's memory, means recons itself, which is then read once for both pixel terms.
+    The image tensors share one memory order.  The backward serves whichever cotangents arrive and writes only what they reach;
+    pix_con sends nothing to recons."""
+
+    @staticmethod
+    def forward(ctx, recons, inputs, x_noisy, v, v_enc_dec, sg, lam, w):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(recons)
+        recons, inputs, x_noisy, v, v_enc_dec = _c(recons), _c(inputs), _c(x_noisy), _c(v), _c(v_enc_dec)
+        assert recons.shape == inputs.shape == x_noisy.shape, (recons.shape, inputs.shape, x_noisy.shape)
+        assert v.dim() == 2 and v.shape == v_enc_dec.shape, (v.shape, v_enc_dec.shape)
+        if sg is not None:
+            assert sg.shape == recons.shape and not sg.requires_grad, "sg is the detached reconstruction"
+            sg = None if sg.data_ptr() == recons.data_ptr() and sg.stride() == recons.stride() else _c(sg)
+        out = torch.empty(4, dtype=torch.float32, device=recons.device)
+        b, l = v.shape
+        wsp, wsb = _ws(recons)
+        ctx.scal = tuple(float(t) for t in (lam[0], w[0], lam[1], w[1], lam[2]))
+        _call("movae_sphere_losses_fwd", recons.data_ptr(), inputs.data_ptr(), x_noisy.data_ptr(), _p(sg), recons.numel(), v.data_ptr(),
+              v_enc_dec.data_ptr(), b, l, *ctx.scal, out.data_ptr(), wsp, wsb, _st(recons))
+        ctx.save_for_backward(recons, inputs, x_noisy, v, v_enc_dec, sg)
+        return out[0], out[1], out[2], out[3]
+
+    #: forward-argument positions of the differentiable inputs: recons, x_noisy, v, v_enc_dec
+    _DIFF_ARGS = (0, 2, 3, 4)
+
+    @staticmethod
+    def backward(ctx, g_rec, g_con, g_lat, g_tot):
+        recons, inputs, x_noisy, v, v_enc_dec, sg = ctx.saved_tensors
+        g_rec, g_con, g_lat, g_tot = (None if g is None else _c(g) for g in (g_rec, g_con, g_lat, g_tot))
+        reach = lambda t: t is not None or g_tot is not None  # noqa: E731
+        need = ctx.needs_input_grad
+        dr = torch.empty_like(recons) if reach(g_rec) and need[0] else None
+        dxn = torch.empty_like(x_noisy) if reach(g_con) and need[2] else None
+        dv = torch.empty_like(v) if reach(g_lat) and need[3] else None
+        dve = torch.empty_like(v_enc_dec) if reach(g_lat) and need[4] else None
+        if dr is None and dxn is None and dv is None and dve is None:
+            return (None,) * 8
+        b, l = v.shape
+        _call("movae_sphere_losses_bwd", recons.data_ptr(), inputs.data_ptr(), x_noisy.data_ptr(), _p(sg), recons.numel(), v.data_ptr(),
+              v_enc_dec.data_ptr(), b, l, *ctx.scal, _p(g_rec), _p(g_con), _p(g_lat), _p(g_tot), _p(dr), _p(dxn), _p(dv), _p(dve), _st(recons))
+        return dr, None, dxn, dv, dve, None, None, None
+
+    @staticmethod
+    @torch.no_grad()
+    def input_cotangents(node, outputs):
+        """RecursiveLosses.input_cotangents for this op (autojac.backward_through): the differentiable inputs that need a gradient and,
+        per loss output index, its cotangents of them."""
+        saved = node.saved_tensors
+        by_pos = dict(zip(SphereLosses._DIFF_ARGS, (saved[0], saved[2], saved[3], saved[4])))
+        live = [p for p in SphereLosses._DIFF_ARGS if node.needs_input_grad[p]]
+        roots = [by_pos[p] for p in live]
+        one = torch.ones((), dtype=torch.float32, device=saved[0].device)
+        cots = []
+        for k in outputs:
+            g = [None] * 4
+            g[k] = one
+            res = SphereLosses.backward(node, *g)
+            cots.append([res[p] for p in live])
+        return roots, cots
+
+
+def sphere_losses(recons, inputs, x_noisy, v, v_enc_dec, lam, w, sg=None):
+    """-> (pix_recon, pix_con, lat_con, total_loss)"""
+    return SphereLosses.apply(recons, inputs, x_noisy, v, v_enc_dec, sg, lam, w)
+
+
 class CombineLosses(Function):
     """The scalar arithmetic of a loss_function (models/vq_vae.py:381-391, vq_vae2.py:313-334, betatc_vae.py:298-324) in one
     launch forward and one backward: `inputs` are device tensors of 1..n fp32 scalars each (T scalars in all, in order), `coef`
