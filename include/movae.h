@@ -589,6 +589,48 @@ int movae_causal_attn_bwd(const float* q, const float* k, const float* v, long l
 int movae_causal_attn_dropout_mask(uint8_t* keep, int BH, int L, float p, unsigned long long seed, unsigned long long draw,
                                    movae_stream_t stream);
 
+/* ---- the ViT Sphere Encoder's bidirectional self-attention with RoPE (models/sphere_encoder_vit.py:143-167 AttentionWithRoPE.forward;
+ * :71-89 apply_rotary_pos_emb) -- the kernels above with the causal mask off: every query sees every key j < L.
+ *   q, k, v     [B, L, ld] row-major, head h at channels h*hd .. h*hd+hd-1, read in place.  With the packed qkv projection [B, L, 3C]
+ *               pass q = qkv, k = qkv + C, v = qkv + 2C and ld = 3C; dq / dk / dv likewise into one [B, L, 3C] buffer.
+ *   out, dout   [B, L, heads*hd], element (h, d) at channel h*hd + d: the reference's (attn @ v).transpose(1, 2).reshape(B, N, C)
+ *   rope_cos, rope_sin   [L, hd/2] tables of the rotation angles (both or neither; null: no rotation), built by the host as the
+ *               reference does: outer(arange(L), 1 / base^(arange(0, hd, 2) / hd)), then cos / sin in fp32.  The rotation is
+ *               interleaved, (u[2t], u[2t+1]) -> (u[2t] c - u[2t+1] s, u[2t] s + u[2t+1] c), applied to q and k as they are loaded; dq
+ *               and dk are rotated back before the store; no rotated copy of q or k is written.  RoPE needs an even hd.
+ *   lse         [B*heads, L] as above.  1 <= hd <= 64, any L >= 1.  p must be 0: attention dropout is refused.
+ *   ws >= movae_attn_ws_bytes(B, heads, L).  No float atomics: the gradients are bit-identical from run to run. */
+int movae_attn_fwd(const float* q, const float* k, const float* v, long ld, const float* rope_cos, const float* rope_sin, float* out,
+                   float* lse, int B, int heads, int L, int hd, float p, movae_stream_t stream);
+size_t movae_attn_ws_bytes(int B, int heads, int L);
+int movae_attn_bwd(const float* q, const float* k, const float* v, long ld, const float* rope_cos, const float* rope_sin, const float* out,
+                   const float* dout, const float* lse, float* dq, float* dk, float* dv, int B, int heads, int L, int hd, float p, void* ws,
+                   size_t ws_bytes, movae_stream_t stream);
+
+/* ---- row operators of the ViT Sphere Encoder (csrc/vit.hip): fp32, row-major [rows][d], fixed-order reductions, no float atomics ----
+ * Row norm over the last dimension.  mode 0: LayerNorm (nn.LayerNorm: biased variance; the caller passes eps 1e-5), weight and bias
+ * nullable; mode 1: RMSNorm  x / sqrt(mean(x^2) + eps) * weight  (the reference's models/sphere_encoder.py rms_norm and models/sphere_encoder_vit.py:34-50 RMSNorm; eps
+ * 1e-6), weight nullable, no bias.  pos (nullable) [pos_rows][d] is added after the affine: out = norm(x) * w + b + pos[row % pos_rows].
+ * The forward saves rstd[rows] (and mean[rows] in mode 0) for the backward, which writes whichever of dx, dweight, dbias are given:
+ * dweight / dbias through per-block partial rows in ws (>= movae_rownorm_ws_bytes(rows, d)) folded in order. */
+int movae_rownorm_fwd(const float* x, const float* weight, const float* bias, const float* pos, int pos_rows, float* out, float* mean,
+                      float* rstd, long rows, int d, int mode, float eps, movae_stream_t stream);
+size_t movae_rownorm_ws_bytes(long rows, int d);
+int movae_rownorm_bwd(const float* dy, const float* x, const float* weight, const float* mean, const float* rstd, float* dx, float* dweight,
+                      float* dbias, long rows, int d, int mode, void* ws, size_t ws_bytes, movae_stream_t stream);
+/* y = gelu(x + bias[col]) with the exact erf form (nn.GELU() default) on x[rows][c]; bias nullable.  The backward takes the saved x
+ * WITHOUT the bias (the bias-free output of the linear in front) and the bias, and writes dx = dy * gelu'(x + bias); the bias gradient
+ * is the column sum of dx (movae_colsum). */
+int movae_bias_gelu_fwd(const float* x, const float* bias, float* y, long rows, int c, movae_stream_t stream);
+int movae_bias_gelu_bwd(const float* dy, const float* x, const float* bias, float* dx, long rows, int c, movae_stream_t stream);
+/* Unpatchify + tanh (models/sphere_encoder_vit.py:125-140, :388): x [b][(h/patch)*(w/patch)][patch*patch*c] -> out NHWC [b][h][w][c];
+ * token (i, j), channel (pi*patch + pj)*c + ch goes to pixel (i*patch + pi, j*patch + pj), channel ch.  The backward takes dout and
+ * the saved out: dx = dout * (1 - out^2) at the source position. */
+int movae_unpatchify_act_fwd(const float* x, float* out, int b, int h, int w, int c, int patch, movae_stream_t stream);
+int movae_unpatchify_act_bwd(const float* dout, const float* out, float* dx, int b, int h, int w, int c, int patch, movae_stream_t stream);
+/* y[row][:] = x[row][:] + pos[row % pos_rows][:]  (SinusoidalPosEmbedding.forward, :53-68); rows is a multiple of pos_rows */
+int movae_add_rows_bcast(const float* x, const float* pos, float* y, long rows, int pos_rows, int d, movae_stream_t stream);
+
 /* ---- reconstruction metrics of the final evaluation (main.py:335-373 over utils/metrics.py ssim :14-80, ssnr :108-154,
  * psnr :157-203) ----------------------------------------------------------------------------------------------------------
  * One chunk of n (real, recon) image pairs of c x h x w, each operand given by its element strides (n, c, h, w) -- e.g. NCHW

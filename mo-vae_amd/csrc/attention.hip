@@ -20,6 +20,13 @@
 // Dropout.  keep(bh, i, j) = word (j & 3) of Philox4x32-10 at counter (j >> 2, i, bh, draw_lo), key (seed_lo, seed_hi ^ draw_hi),
 // kept iff the word < thr = (1 - p) * 2^32.  A pure function of (seed, draw, bh, i, j): the forward, both backward passes and
 // movae_causal_attn_dropout_mask regenerate the same mask whatever their tiling.
+//
+// The bidirectional form (movae_attn_*: AttentionWithRoPE of models/sphere_encoder_vit.py:143-167) is the same three kernels with
+// CAUSAL off -- every query sees every key j < L, all tiles in both loops, no dropout instances -- the head-major output order
+// h*hd + d (out strides oh / od), and optionally RoPE: q and k are rotated as they are loaded, pair t of a row at position n by
+// the angle whose cos / sin the host tabulated at [n][t]; (u[2t], u[2t+1]) -> (u[2t] c - u[2t+1] s, u[2t] s + u[2t+1] c).  The pair
+// partner of an element is in the same lane for the g*NS + s loads (NS is even) and in lane c ^ 1 for the cc*16 + c loads; dq / dk
+// come out as gradients of the ROTATED rows and are rotated back (the transpose rotation) in registers before the store.
 #include "common.h"
 
 namespace {
@@ -39,7 +46,10 @@ struct AttnArgs {
     float* dq;
     float* dk;
     float* dv;
+    const float* cos;  // RoPE tables [L][hd / 2] (ROPE instances only)
+    const float* sin;
     long ld;       // row stride of q / k / v / dq / dk / dv (floats)
+    int oh, od;    // out / dout: element (h, d) of a row at h * oh + d * od
     int heads, L, hd, ntiles, nbh;
     float scale;   // 1 / sqrt(hd)
     unsigned thr;  // keep iff Philox word < thr (and p > 0)
@@ -56,6 +66,46 @@ __device__ __forceinline__ void keep4(const AttnArgs& a, int bh, int i, int jq, 
 
 __device__ __forceinline__ float ld_guard(const float* base, long row, int d, bool ok, long ld) { return ok ? base[row * ld + d] : 0.f; }
 
+// RoPE of a run u[0 .. NS) = elements d0 .. d0+NS-1 (d0 even) of the row at position `pos`; ok: the row exists
+template <int NS>
+__device__ __forceinline__ void rope_run(const AttnArgs& a, float (&u)[NS], int pos, int d0, bool ok) {
+    const int hh = a.hd >> 1;
+#pragma unroll
+    for (int t = 0; t < NS / 2; ++t) {
+        const int pr = (d0 >> 1) + t;
+        const bool in = ok && pr < hh;
+        const float cs = in ? a.cos[(long)pos * hh + pr] : 1.f, sn = in ? a.sin[(long)pos * hh + pr] : 0.f;
+        const float x0 = u[2 * t], x1 = u[2 * t + 1];
+        u[2 * t] = x0 * cs - x1 * sn;
+        u[2 * t + 1] = x0 * sn + x1 * cs;
+    }
+}
+
+// RoPE of element d (= cc*16 + c: its pair partner d ^ 1 is lane ^ 1's) of the row at `pos`; every lane of the wave calls this
+__device__ __forceinline__ float rope_col(const AttnArgs& a, float raw, int pos, int d, bool ok) {
+    const float other = __shfl_xor(raw, 1, 64);
+    const int hh = a.hd >> 1;
+    const float cs = ok ? a.cos[(long)pos * hh + (d >> 1)] : 1.f, sn = ok ? a.sin[(long)pos * hh + (d >> 1)] : 0.f;
+    return (d & 1) ? other * sn + raw * cs : raw * cs - other * sn;
+}
+
+// the transpose rotation of an accumulator fragment: reg r of acc[cc] is element cc*16 + 4g + r of the row at `pos` (pairs: r, r ^ 1)
+template <int NC>
+__device__ __forceinline__ void rope_back(const AttnArgs& a, f32x4 (&acc)[NC], int pos, int g) {
+    const int hh = a.hd >> 1;
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int pr = (cc * 16 + 4 * g) / 2 + t;
+            const bool in = pr < hh;
+            const float cs = in ? a.cos[(long)pos * hh + pr] : 1.f, sn = in ? a.sin[(long)pos * hh + pr] : 0.f;
+            const float g0 = acc[cc][2 * t], g1 = acc[cc][2 * t + 1];
+            acc[cc][2 * t] = g0 * cs + g1 * sn;
+            acc[cc][2 * t + 1] = g1 * cs - g0 * sn;
+        }
+}
+
 // wave-level tile order: work group t of the grid handles 4 consecutive 16-row tiles of one (b, h); `rev` maps the earliest
 // dispatched groups to the LAST tiles (the longest causal rows) -- forward and dQ -- and the key passes keep t (key tile 0 sees
 // every query)
@@ -68,11 +118,11 @@ __device__ __forceinline__ bool wave_tile(const AttnArgs& a, bool rev, int& tile
     return tile < a.ntiles;
 }
 
-template <int HDP, bool DROP>
+template <int HDP, bool DROP, bool CAUSAL, bool ROPE>
 __global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
     constexpr int NS = HDP / 4, NC = HDP >= 16 ? HDP / 16 : 1;
     int qt, bh;
-    if (!wave_tile(a, true, qt, bh)) return;  // (no block-level barrier below: whole waves may leave)
+    if (!wave_tile(a, CAUSAL, qt, bh)) return;  // (no block-level barrier below: whole waves may leave)
     const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
     const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd;
     const long row0 = (long)b * L;
@@ -82,25 +132,33 @@ __global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
     float qf[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) qf[s] = ld_guard(qb, i, g * NS + s, i < L && g * NS + s < hd, a.ld);
+    if (ROPE) rope_run<NS>(a, qf, i, g * NS, i < L);
     f32x4 acc[NC];
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc) acc[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;
-    for (int kt = 0; kt <= qt; ++kt) {
+    const int kend = CAUSAL ? qt + 1 : a.ntiles;
+    for (int kt = 0; kt < kend; ++kt) {
         const int j0 = kt * 16, jr = j0 + c;
         f32x4 st = {0.f, 0.f, 0.f, 0.f};
+        float kf[NS];
 #pragma unroll
-        for (int s = 0; s < NS; ++s) st = mfma4(ld_guard(kb, jr, g * NS + s, jr < L && g * NS + s < hd, a.ld), qf[s], st);
+        for (int s = 0; s < NS; ++s) kf[s] = ld_guard(kb, jr, g * NS + s, jr < L && g * NS + s < hd, a.ld);
+        if (ROPE) rope_run<NS>(a, kf, jr, g * NS, jr < L);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) st = mfma4(kf[s], qf[s], st);
         float p[4], mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = j0 + 4 * g + r;
-            p[r] = (j <= i && j < L) ? st[r] * sl2 : -INFINITY;
+            p[r] = ((!CAUSAL || j <= i) && j < L) ? st[r] * sl2 : -INFINITY;
             mx = fmaxf(mx, p[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mn = fmaxf(m, mx), alpha = exp2f(m - mn);  // key 0 is in the first tile: mn is finite from there on
+        // key 0 is in the first tile and visible to every lane (padded query rows included): mn is finite from there on, so a
+        // padded last key tile (all -inf) gives p = 0
+        const float mn = fmaxf(m, mx), alpha = exp2f(m - mn);
         float rs = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -130,34 +188,34 @@ __global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
     if (i >= L) return;
     const float inv_l = 1.f / l;
     const int proj = a.heads * hd;
-    float* ob = a.out + (row0 + i) * proj + h;
+    float* ob = a.out + (row0 + i) * proj + h * a.oh;
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int d = cc * 16 + 4 * g + r;
-            if (d < hd) ob[(long)d * a.heads] = acc[cc][r] * inv_l;
+            if (d < hd) ob[(long)d * a.od] = acc[cc][r] * inv_l;
         }
     if (g == 0) a.lse_out[(long)bh * L + i] = (m + log2f(l)) * LN2;
 }
 
-// delta[bh][i] = sum_d dO[b][i][d*heads+h] * O[b][i][d*heads+h]  (D_i of the FlashAttention-2 backward; holds with dropout too)
+// delta[bh][i] = sum_d dO[b][i][h*oh+d*od] * O[b][i][h*oh+d*od]  (D_i of the FlashAttention-2 backward; holds with dropout too)
 __global__ __launch_bounds__(256) void attn_delta_k(const float* __restrict__ o, const float* __restrict__ dout, float* __restrict__ delta,
-                                                    long rows, int heads, int L, int hd) {
+                                                    long rows, int heads, int L, int hd, int oh, int od) {
     const long n = rows * heads;  // (b, i, h)
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
         const long r = t / heads;
         const int h = (int)(t - r * heads);
-        const float *ob = o + r * heads * hd + h, *gb = dout + r * heads * hd + h;
+        const float *ob = o + r * heads * hd + h * oh, *gb = dout + r * heads * hd + h * oh;
         float s = 0.f;
-        for (int d = 0; d < hd; ++d) s += ob[(long)d * heads] * gb[(long)d * heads];
+        for (int d = 0; d < hd; ++d) s += ob[(long)d * od] * gb[(long)d * od];
         const long b = r / L;
         delta[(b * heads + h) * L + (r - b * L)] = s;
     }
 }
 
 // dK, dV: one wave per 16-key tile, over the query tiles at and below the diagonal
-template <int HDP, bool DROP>
+template <int HDP, bool DROP, bool CAUSAL, bool ROPE>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_k(AttnArgs a) {
     constexpr int NS = HDP / 4, NC = HDP >= 16 ? HDP / 16 : 1;
     int kt, bh;
@@ -166,7 +224,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_k(AttnArgs a) {
     const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd, heads = a.heads;
     const long row0 = (long)b * L, ldo = (long)heads * hd;
     const float *qb = a.q + row0 * a.ld + h * hd, *kb = a.k + row0 * a.ld + h * hd, *vb = a.v + row0 * a.ld + h * hd;
-    const float* gb = a.dout + row0 * ldo + h;  // dO[i][d] at gb[i * ldo + d * heads]
+    const float* gb = a.dout + row0 * ldo + h * a.oh;  // dO[i][d] at gb[i * ldo + d * od]
+    const int od = a.od;
     const float *lseb = a.lse + (long)bh * L, *delb = a.delta + (long)bh * L;
     const int j0 = kt * 16, j = j0 + c;
     const float sl2 = a.scale * LOG2E;
@@ -177,18 +236,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_k(AttnArgs a) {
         kf[s] = ld_guard(kb, j, g * NS + s, ok, a.ld);
         vf[s] = ld_guard(vb, j, g * NS + s, ok, a.ld);
     }
+    if (ROPE) rope_run<NS>(a, kf, j, g * NS, j < L);
     f32x4 adk[NC], adv[NC];
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc) adk[cc] = adv[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int qt = kt; qt < a.ntiles; ++qt) {
+    for (int qt = CAUSAL ? kt : 0; qt < a.ntiles; ++qt) {
         const int i0 = qt * 16, ir = i0 + c;
         f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+        float qr[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) qr[s] = ld_guard(qb, ir, g * NS + s, ir < L && g * NS + s < hd, a.ld);
+        if (ROPE) rope_run<NS>(a, qr, ir, g * NS, ir < L);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int d = g * NS + s;
             const bool ok = ir < L && d < hd;
-            st = mfma4(ld_guard(qb, ir, d, ok, a.ld), kf[s], st);
-            dpt = mfma4(ok ? gb[ir * ldo + (long)d * heads] : 0.f, vf[s], dpt);
+            st = mfma4(qr[s], kf[s], st);
+            dpt = mfma4(ok ? gb[ir * ldo + (long)d * od] : 0.f, vf[s], dpt);
         }
         // keep bits of (query i0+4g+r, key j): lane (c, g) draws the Philox block of query i0+4g+(c&3), keys j0+4(c>>2) .. +3
         // -- the 4 x 4 patch its quad needs -- and the quad transposes it in 4 rotations: in rotation t lane k = c&3 takes from
@@ -212,7 +276,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_k(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = i0 + 4 * g + r;
-            const bool ok = i < L && j <= i;
+            const bool ok = i < L && (CAUSAL ? j <= i : j < L);
             const float p = ok ? exp2f(st[r] * sl2 - lseb[i] * LOG2E) : 0.f;
             float dp = dpt[r], pd = p;
             if (DROP) {
@@ -230,12 +294,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_k(AttnArgs a) {
             for (int cc = 0; cc < NC; ++cc) {
                 const int d = cc * 16 + c;
                 const bool ok = i < L && d < hd;
-                adv[cc] = mfma4(ok ? gb[i * ldo + (long)d * heads] : 0.f, pk[r], adv[cc]);
-                adk[cc] = mfma4(ld_guard(qb, i, d, ok, a.ld), ds[r], adk[cc]);
+                adv[cc] = mfma4(ok ? gb[i * ldo + (long)d * od] : 0.f, pk[r], adv[cc]);
+                float qv = ld_guard(qb, i, d, ok, a.ld);
+                if (ROPE) qv = rope_col(a, qv, i, d, ok);
+                adk[cc] = mfma4(qv, ds[r], adk[cc]);
             }
         }
     }
     if (j >= L) return;
+    if (ROPE) rope_back<NC>(a, adk, j, g);
     float *dkb = a.dk + (row0 + j) * a.ld + h * hd, *dvb = a.dv + (row0 + j) * a.ld + h * hd;
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc)
@@ -250,16 +317,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_k(AttnArgs a) {
 }
 
 // dQ: one wave per 16-query tile, over the key tiles at and left of the diagonal (the forward's orientation)
-template <int HDP, bool DROP>
+template <int HDP, bool DROP, bool CAUSAL, bool ROPE>
 __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
     constexpr int NS = HDP / 4, NC = HDP >= 16 ? HDP / 16 : 1;
     int qt, bh;
-    if (!wave_tile(a, true, qt, bh)) return;
+    if (!wave_tile(a, CAUSAL, qt, bh)) return;
     const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
     const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd, heads = a.heads;
     const long row0 = (long)b * L, ldo = (long)heads * hd;
     const float *qb = a.q + row0 * a.ld + h * hd, *kb = a.k + row0 * a.ld + h * hd, *vb = a.v + row0 * a.ld + h * hd;
-    const float* gb = a.dout + row0 * ldo + h;
+    const float* gb = a.dout + row0 * ldo + h * a.oh;
     const int i0 = qt * 16, i = i0 + c;
     const float sl2 = a.scale * LOG2E;
     float qf[NS], gf[NS];
@@ -268,20 +335,26 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
         const int d = g * NS + s;
         const bool ok = i < L && d < hd;
         qf[s] = ld_guard(qb, i, d, ok, a.ld);
-        gf[s] = ok ? gb[i * ldo + (long)d * heads] : 0.f;
+        gf[s] = ok ? gb[i * ldo + (long)d * a.od] : 0.f;
     }
+    if (ROPE) rope_run<NS>(a, qf, i, g * NS, i < L);
     const float lse2 = i < L ? a.lse[(long)bh * L + i] * LOG2E : 0.f, di = i < L ? a.delta[(long)bh * L + i] : 0.f;
     f32x4 acc[NC];
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc) acc[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt <= qt; ++kt) {
+    const int kend = CAUSAL ? qt + 1 : a.ntiles;
+    for (int kt = 0; kt < kend; ++kt) {
         const int j0 = kt * 16, jr = j0 + c;
         f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+        float kf[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) kf[s] = ld_guard(kb, jr, g * NS + s, jr < L && g * NS + s < hd, a.ld);
+        if (ROPE) rope_run<NS>(a, kf, jr, g * NS, jr < L);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int d = g * NS + s;
             const bool ok = jr < L && d < hd;
-            st = mfma4(ld_guard(kb, jr, d, ok, a.ld), qf[s], st);
+            st = mfma4(kf[s], qf[s], st);
             dpt = mfma4(ld_guard(vb, jr, d, ok, a.ld), gf[s], dpt);
         }
         unsigned w[4] = {0u, 0u, 0u, 0u};
@@ -290,7 +363,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = j0 + 4 * g + r;
-            const bool ok = i < L && j <= i;
+            const bool ok = i < L && (CAUSAL ? j <= i : j < L);
             const float p = ok ? exp2f(st[r] * sl2 - lse2) : 0.f;
             float dp = dpt[r];
             if (DROP) dp = w[r] < a.thr ? dp * a.inv_keep : 0.f;
@@ -300,11 +373,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
         for (int r = 0; r < 4; ++r) {
             const int j = j0 + 4 * g + r;
 #pragma unroll
-            for (int cc = 0; cc < NC; ++cc)
-                acc[cc] = mfma4(ld_guard(kb, j, cc * 16 + c, j < L && cc * 16 + c < hd, a.ld), ds[r], acc[cc]);
+            for (int cc = 0; cc < NC; ++cc) {
+                const int d = cc * 16 + c;
+                const bool okk = j < L && d < hd;
+                float kv = ld_guard(kb, j, d, okk, a.ld);
+                if (ROPE) kv = rope_col(a, kv, j, d, okk);
+                acc[cc] = mfma4(kv, ds[r], acc[cc]);
+            }
         }
     }
     if (i >= L) return;
+    if (ROPE) rope_back<NC>(a, acc, i, g);
     float* dqb = a.dq + (row0 + i) * a.ld + h * hd;
 #pragma unroll
     for (int cc = 0; cc < NC; ++cc)
@@ -341,6 +420,7 @@ int setup(AttnArgs& a, const char* what, long ld, int B, int heads, int L, int h
     MOVAE_CHECK_ARG((long)B * heads <= (1L << 30) && L <= (1 << 28), "%s: sizes out of range", what);
     a = AttnArgs{};
     a.ld = ld;
+    a.oh = 1, a.od = heads;  // PixelSNAIL's channel order d * heads + h
     a.heads = heads, a.L = L, a.hd = hd;
     a.ntiles = (L + 15) / 16;
     a.nbh = B * heads;
@@ -361,19 +441,51 @@ dim3 tile_grid(const AttnArgs& a) { return dim3((unsigned)(((a.ntiles + 3) / 4) 
         const dim3 grid_ = tile_grid(a);                                                                  \
         const int hdp_ = hdp_of((a).hd);                                                                  \
         if (hdp_ == 8) {                                                                                  \
-            if (drop) hipLaunchKernelGGL((KERNEL<8, true>), grid_, dim3(256), 0, stream, a);              \
-            else hipLaunchKernelGGL((KERNEL<8, false>), grid_, dim3(256), 0, stream, a);                  \
+            if (drop) hipLaunchKernelGGL((KERNEL<8, true, true, false>), grid_, dim3(256), 0, stream, a);  \
+            else hipLaunchKernelGGL((KERNEL<8, false, true, false>), grid_, dim3(256), 0, stream, a);      \
         } else if (hdp_ == 16) {                                                                          \
-            if (drop) hipLaunchKernelGGL((KERNEL<16, true>), grid_, dim3(256), 0, stream, a);             \
-            else hipLaunchKernelGGL((KERNEL<16, false>), grid_, dim3(256), 0, stream, a);                 \
+            if (drop) hipLaunchKernelGGL((KERNEL<16, true, true, false>), grid_, dim3(256), 0, stream, a);             \
+            else hipLaunchKernelGGL((KERNEL<16, false, true, false>), grid_, dim3(256), 0, stream, a);                 \
         } else if (hdp_ == 32) {                                                                          \
-            if (drop) hipLaunchKernelGGL((KERNEL<32, true>), grid_, dim3(256), 0, stream, a);             \
-            else hipLaunchKernelGGL((KERNEL<32, false>), grid_, dim3(256), 0, stream, a);                 \
+            if (drop) hipLaunchKernelGGL((KERNEL<32, true, true, false>), grid_, dim3(256), 0, stream, a);             \
+            else hipLaunchKernelGGL((KERNEL<32, false, true, false>), grid_, dim3(256), 0, stream, a);                 \
         } else {                                                                                          \
-            if (drop) hipLaunchKernelGGL((KERNEL<64, true>), grid_, dim3(256), 0, stream, a);             \
-            else hipLaunchKernelGGL((KERNEL<64, false>), grid_, dim3(256), 0, stream, a);                 \
+            if (drop) hipLaunchKernelGGL((KERNEL<64, true, true, false>), grid_, dim3(256), 0, stream, a);             \
+            else hipLaunchKernelGGL((KERNEL<64, false, true, false>), grid_, dim3(256), 0, stream, a);                 \
         }                                                                                                 \
     } while (0)
+
+// the bidirectional instances: no dropout, RoPE on / off
+#define ATTN_LAUNCH_BIDIR(KERNEL, a, rope, stream)                                                                 \
+    do {                                                                                                           \
+        const dim3 grid_ = tile_grid(a);                                                                           \
+        const int hdp_ = hdp_of((a).hd);                                                                           \
+        if (hdp_ == 8) {                                                                                           \
+            if (rope) hipLaunchKernelGGL((KERNEL<8, false, false, true>), grid_, dim3(256), 0, stream, a);         \
+            else hipLaunchKernelGGL((KERNEL<8, false, false, false>), grid_, dim3(256), 0, stream, a);             \
+        } else if (hdp_ == 16) {                                                                                   \
+            if (rope) hipLaunchKernelGGL((KERNEL<16, false, false, true>), grid_, dim3(256), 0, stream, a);        \
+            else hipLaunchKernelGGL((KERNEL<16, false, false, false>), grid_, dim3(256), 0, stream, a);            \
+        } else if (hdp_ == 32) {                                                                                   \
+            if (rope) hipLaunchKernelGGL((KERNEL<32, false, false, true>), grid_, dim3(256), 0, stream, a);        \
+            else hipLaunchKernelGGL((KERNEL<32, false, false, false>), grid_, dim3(256), 0, stream, a);            \
+        } else {                                                                                                   \
+            if (rope) hipLaunchKernelGGL((KERNEL<64, false, false, true>), grid_, dim3(256), 0, stream, a);        \
+            else hipLaunchKernelGGL((KERNEL<64, false, false, false>), grid_, dim3(256), 0, stream, a);            \
+        }                                                                                                          \
+    } while (0)
+
+// argument checks of the bidirectional entry points beyond setup()'s
+int setup_bidir(AttnArgs& a, const char* what, long ld, const float* cs, const float* sn, int B, int heads, int L, int hd, float p) {
+    MOVAE_CHECK_ARG(p == 0.f, "%s: attention dropout is not supported (p must be 0, got %g)", what, (double)p);
+    MOVAE_CHECK_ARG((cs == nullptr) == (sn == nullptr), "%s: give both RoPE tables (cos and sin) or neither", what);
+    MOVAE_CHECK_ARG(!cs || (hd > 0 && hd % 2 == 0), "%s: RoPE needs an even head_dim, got %d", what, hd);
+    const int rc = setup(a, what, ld, B, heads, L, hd, 0.f, 0ull, 0ull);
+    if (rc != MOVAE_OK) return rc;
+    a.cos = cs, a.sin = sn;
+    a.oh = hd, a.od = 1;  // head-major: (attn @ v).transpose(1, 2).reshape(B, N, C)
+    return MOVAE_OK;
+}
 
 }  // namespace
 
@@ -410,7 +522,8 @@ int movae_causal_attn_bwd(const float* q, const float* k, const float* v, long l
     const long n = rows * heads;
     long g = (n + 255) / 256;
     g = g > 8192 ? 8192 : g;
-    hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, out, dout, delta, rows, heads, L, hd);
+    hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, out, dout, delta, rows, heads, L, hd,
+                       a.oh, a.od);
     MOVAE_CHECK_LAUNCH("causal_attn_delta");
     a.q = q, a.k = k, a.v = v, a.dout = dout, a.lse = lse, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
     const bool drop = p > 0.f;
@@ -418,6 +531,46 @@ int movae_causal_attn_bwd(const float* q, const float* k, const float* v, long l
     MOVAE_CHECK_LAUNCH("causal_attn_bwd_dkdv");
     ATTN_LAUNCH(attn_bwd_dq_k, a, drop, (hipStream_t)stream);
     MOVAE_CHECK_LAUNCH("causal_attn_bwd_dq");
+    return MOVAE_OK;
+}
+
+int movae_attn_fwd(const float* q, const float* k, const float* v, long ld, const float* rope_cos, const float* rope_sin, float* out,
+                   float* lse, int B, int heads, int L, int hd, float p, movae_stream_t stream) {
+    MOVAE_CHECK_ARG(q && k && v && out && lse, "movae_attn_fwd: null pointer");
+    AttnArgs a;
+    const int rc = setup_bidir(a, "movae_attn_fwd", ld, rope_cos, rope_sin, B, heads, L, hd, p);
+    if (rc != MOVAE_OK) return rc;
+    a.q = q, a.k = k, a.v = v, a.out = out, a.lse_out = lse;
+    const bool rope = rope_cos != nullptr;
+    ATTN_LAUNCH_BIDIR(attn_fwd_k, a, rope, (hipStream_t)stream);
+    MOVAE_CHECK_LAUNCH("attn_fwd");
+    return MOVAE_OK;
+}
+
+size_t movae_attn_ws_bytes(int B, int heads, int L) { return movae_causal_attn_ws_bytes(B, heads, L); }
+
+int movae_attn_bwd(const float* q, const float* k, const float* v, long ld, const float* rope_cos, const float* rope_sin, const float* out,
+                   const float* dout, const float* lse, float* dq, float* dk, float* dv, int B, int heads, int L, int hd, float p, void* ws,
+                   size_t ws_bytes, movae_stream_t stream) {
+    MOVAE_WS_SCRATCH(ws, ws_bytes);
+    MOVAE_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv, "movae_attn_bwd: null pointer");
+    AttnArgs a;
+    const int rc = setup_bidir(a, "movae_attn_bwd", ld, rope_cos, rope_sin, B, heads, L, hd, p);
+    if (rc != MOVAE_OK) return rc;
+    MOVAE_CHECK_ARG(ws && ws_bytes >= (size_t)B * heads * L * sizeof(float), "movae_attn_bwd: workspace too small");
+    float* delta = static_cast<float*>(ws);
+    const long rows = (long)B * L;
+    const long n = rows * heads;
+    long g = (n + 255) / 256;
+    g = g > 8192 ? 8192 : g;
+    hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, out, dout, delta, rows, heads, L, hd, a.oh, a.od);
+    MOVAE_CHECK_LAUNCH("attn_delta");
+    a.q = q, a.k = k, a.v = v, a.dout = dout, a.lse = lse, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
+    const bool rope = rope_cos != nullptr;
+    ATTN_LAUNCH_BIDIR(attn_bwd_dkdv_k, a, rope, (hipStream_t)stream);
+    MOVAE_CHECK_LAUNCH("attn_bwd_dkdv");
+    ATTN_LAUNCH_BIDIR(attn_bwd_dq_k, a, rope, (hipStream_t)stream);
+    MOVAE_CHECK_LAUNCH("attn_bwd_dq");
     return MOVAE_OK;
 }
 

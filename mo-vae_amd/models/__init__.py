@@ -8,6 +8,7 @@ from .gg_vq_vae2 import GGVQVAE2
 from .pixelcnn_prior import HierarchicalPixelCNN, HierarchicalPixelSNAIL, PixelCNN, PixelSNAIL
 from .recursive_vaes import CycleVAE, RecursiveCyclicVAE, RecursiveKLVAE
 from .sphere_encoder import SphereEncoder
+from .sphere_encoder_vit import SphereEncoderViT
 from .vae import VAE
 from .vq_vae import VQVAE, VectorQuantizer
 from .vq_vae2 import VQVAE2
@@ -136,5 +137,26 @@ def build_sphere_encoder(input_size, num_channels=3, args=None, device=None, use
         use_perceptual=use_perceptual, device=device)
 
 
+def build_sphere_encoder_vit(input_size, num_channels=3, args=None, device=None, use_perceptual=False):
+    """The ViT Sphere Encoder from the arguments the reference's factory reads for `--arch sphere_encoder_vit` (models/__init__.py:107-146):
+    latent_dim is L, the total spherical dimension, and must divide into the patches.  get_network still refuses the architecture, for
+    the reason given at build_sphere_encoder."""
+    patch_size = getattr(args, "patch_size", 2 if input_size <= 32 else 8)
+    num_patches = (input_size // patch_size) ** 2
+    L = getattr(args, "latent_dim", 128)
+    latent_channels = L // num_patches
+    if L != latent_channels * num_patches:
+        raise ValueError(f"sphere_encoder_vit: latent_dim {L} must be divisible by num_patches {num_patches}")
+    return SphereEncoderViT(
+        img_size=input_size, patch_size=patch_size, in_channels=num_channels, embed_dim=getattr(args, "vit_embed_dim", 1024),
+        depth=getattr(args, "vit_depth", 24), num_heads=getattr(args, "vit_num_heads", 16), mlp_ratio=4.0,
+        mixer_depth=getattr(args, "vit_mixer_depth", 2), latent_channels=latent_channels, num_classes=getattr(args, "num_classes", 0),
+        sigma_max_angle_deg=getattr(args, "sigma_max_angle_deg", 80.0), sigma_mix_prob=getattr(args, "sigma_mix_prob", 0.0),
+        sigma_mix_angle_min_deg=getattr(args, "sigma_mix_angle_min_deg", None),
+        sigma_mix_angle_max_deg=getattr(args, "sigma_mix_angle_max_deg", None), lambda_pix_recon=getattr(args, "lambda_pix_recon", 1.0),
+        lambda_pix_con=getattr(args, "lambda_pix_con", 0.5), lambda_lat_con=getattr(args, "lambda_lat_con", 0.1),
+        use_perceptual=use_perceptual, device=device)
+
+
 __all__ = ["VAE", "VQVAE", "VQVAE2", "BetaTCVAE", "GGVAE", "GGVQVAE", "GGVQVAE2", "VectorQuantizer", "RecursiveKLVAE", "CycleVAE",
-           "RecursiveCyclicVAE", "SphereEncoder", "build_sphere_encoder", "PixelCNN", "HierarchicalPixelCNN", "PixelSNAIL", "HierarchicalPixelSNAIL", "get_network"]
+           "RecursiveCyclicVAE", "SphereEncoder", "build_sphere_encoder", "SphereEncoderViT", "build_sphere_encoder_vit", "PixelCNN", "HierarchicalPixelCNN", "PixelSNAIL", "HierarchicalPixelSNAIL", "get_network"]

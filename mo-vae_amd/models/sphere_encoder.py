@@ -25,31 +25,21 @@ from ._base import nchw_view
 from .vae import VAE
 
 
-class SphereEncoder(VAE):
+class SphereCommon:
+    """What the conv and the ViT Sphere Encoder share (mixed in ahead of a HotPathModel): the hyperparameters, the noise schedule and
+    its draws, spherify, forward, loss_function and sample.  The class supplies encode_to_vector(x) -> [B, L] and
+    decode_from_sphere(v) -> a logical NCHW view of an NHWC buffer."""
     graph_safe = True
     #: internal: every loss is an output of ops.SphereLosses, so train can pull the K Jacobian rows back from its inputs
     _jacobian_from_loss_op = True
     #: {"u": [B, 4], "e": [B, L]} to replace the draws of forward (parity tests)
     noise_override = None
 
-    def __init__(self, latent_dim: int = 2048, sigma_max_angle_deg: float = 80.0, sigma_mix_prob: float = 0.0,
-                 sigma_mix_angle_min_deg=None, sigma_mix_angle_max_deg=None, lambda_pix_recon: float = 1.0, lambda_pix_con: float = 0.5,
-                 lambda_lat_con: float = 0.1, pix_recon_smooth_l1_weight: float = 1.0, pix_recon_perceptual_weight: float = 1.0,
-                 pix_con_smooth_l1_weight: float = 0.5, pix_con_perceptual_weight: float = 0.5, use_perceptual: bool = True, **kwargs):
-        if use_perceptual:
-            raise NotImplementedError("SphereEncoder(use_perceptual=True) needs the pretrained VGG16 weights of the reference's "
-                                      "PerceptualLoss, which this build does not carry (DESIGN.md section 7); pass use_perceptual=False")
-        super().__init__(latent_dim=latent_dim, **kwargs)
-        # models/sphere_encoder.py:102-107: the VAE's heads go, decoder_input is replaced in place, encoder_proj is registered last;
-        # the RNG draws follow the VAE's: encoder_proj, then the new decoder_input
-        feat = self.hidden_dims[-1] * (self.input_size // (2 ** len(self.hidden_dims))) ** 2
-        del self.mu
-        del self.log_var
-        self.encoder_proj = mnn.Linear(feat, latent_dim)
-        self.decoder_input = mnn.Linear(latent_dim, feat)
-
-        self.L = latent_dim
-        self.radius = sqrt(latent_dim)
+    def _init_sphere(self, L, sigma_max_angle_deg, sigma_mix_prob, sigma_mix_angle_min_deg, sigma_mix_angle_max_deg, lambda_pix_recon,
+                     lambda_pix_con, lambda_lat_con, pix_recon_smooth_l1_weight, pix_recon_perceptual_weight, pix_con_smooth_l1_weight,
+                     pix_con_perceptual_weight):
+        self.L = L
+        self.radius = sqrt(L)
         self.sigma_max_angle_deg = float(sigma_max_angle_deg)
         self.sigma_max = math.tan(math.radians(self.sigma_max_angle_deg))
         self.sigma_mix_prob = float(sigma_mix_prob)
@@ -87,38 +77,12 @@ class SphereEncoder(VAE):
         return torch.cat([angle, mask.to(dtype), mix, s], dim=1), e
 
     # -- reference API -----------------------------------------------------------------------------------------------------------
-    def encode_to_vector(self, x):
-        """Encode to the flat vector (before spherify)."""
-        return self.encoder_proj(self.encoder(ops.to_nhwc(x)))
-
     def spherify(self, z, add_noise=False, sigma=None, e=None):
         """Project z onto the sphere; with add_noise, sigma and e: spherify(spherify(z) + sigma * e) (the noise is added to the
         already-spherified v, models/sphere_encoder.py:146-162).  sigma: a number, or a tensor of 1 or B values."""
         if add_noise and sigma is not None and e is not None:
             return ops.spherify(z, self.radius, sigma, e)
         return ops.spherify(z, self.radius)
-
-    def decode_from_sphere(self, v):
-        y = self.final_layer(self.decoder(self.decoder_input(v)))
-        self.final_layer._out_link = None  # the output activation's link stays unused (see the module docstring)
-        self._recons_link = None
-        return nchw_view(y)
-
-    def encode(self, x):
-        """(v,) on the sphere, for compatibility; no mu / log_var."""
-        return (self.spherify(self.encode_to_vector(x)),)
-
-    def reparameterize(self, mu, log_var):
-        return mu
-
-    def decode(self, z):
-        """Decode a latent: taken as it is when it lies on the sphere (norm within 1e-2 of the radius), else spherified first."""
-        if z.dim() == 1:
-            z = z.unsqueeze(0)
-        norm = z.norm(dim=-1, keepdim=True)
-        if not torch.allclose(norm, torch.full_like(norm, self.radius), atol=1e-2):
-            z = self.spherify(z)
-        return self.decode_from_sphere(z)
 
     def forward(self, x):
         z = self.encode_to_vector(x)
@@ -155,3 +119,51 @@ class SphereEncoder(VAE):
                 e_step = e if share_noise else torch.randn(num_samples, self.L, device=device)
                 x = self.decode_from_sphere(self.spherify(z, add_noise=True, sigma=self.sigma_max, e=e_step))
         return x
+
+
+class SphereEncoder(SphereCommon, VAE):
+    def __init__(self, latent_dim: int = 2048, sigma_max_angle_deg: float = 80.0, sigma_mix_prob: float = 0.0,
+                 sigma_mix_angle_min_deg=None, sigma_mix_angle_max_deg=None, lambda_pix_recon: float = 1.0, lambda_pix_con: float = 0.5,
+                 lambda_lat_con: float = 0.1, pix_recon_smooth_l1_weight: float = 1.0, pix_recon_perceptual_weight: float = 1.0,
+                 pix_con_smooth_l1_weight: float = 0.5, pix_con_perceptual_weight: float = 0.5, use_perceptual: bool = True, **kwargs):
+        if use_perceptual:
+            raise NotImplementedError("SphereEncoder(use_perceptual=True) needs the pretrained VGG16 weights of the reference's "
+                                      "PerceptualLoss, which this build does not carry (DESIGN.md section 7); pass use_perceptual=False")
+        super().__init__(latent_dim=latent_dim, **kwargs)
+        # models/sphere_encoder.py:102-107: the VAE's heads go, decoder_input is replaced in place, encoder_proj is registered last;
+        # the RNG draws follow the VAE's: encoder_proj, then the new decoder_input
+        feat = self.hidden_dims[-1] * (self.input_size // (2 ** len(self.hidden_dims))) ** 2
+        del self.mu
+        del self.log_var
+        self.encoder_proj = mnn.Linear(feat, latent_dim)
+        self.decoder_input = mnn.Linear(latent_dim, feat)
+
+        self._init_sphere(latent_dim, sigma_max_angle_deg, sigma_mix_prob, sigma_mix_angle_min_deg, sigma_mix_angle_max_deg, lambda_pix_recon,
+                          lambda_pix_con, lambda_lat_con, pix_recon_smooth_l1_weight, pix_recon_perceptual_weight, pix_con_smooth_l1_weight,
+                          pix_con_perceptual_weight)
+
+    def encode_to_vector(self, x):
+        """Encode to the flat vector (before spherify)."""
+        return self.encoder_proj(self.encoder(ops.to_nhwc(x)))
+
+    def decode_from_sphere(self, v):
+        y = self.final_layer(self.decoder(self.decoder_input(v)))
+        self.final_layer._out_link = None  # the output activation's link stays unused (see the module docstring)
+        self._recons_link = None
+        return nchw_view(y)
+
+    def encode(self, x):
+        """(v,) on the sphere, for compatibility; no mu / log_var."""
+        return (self.spherify(self.encode_to_vector(x)),)
+
+    def reparameterize(self, mu, log_var):
+        return mu
+
+    def decode(self, z):
+        """Decode a latent: taken as it is when it lies on the sphere (norm within 1e-2 of the radius), else spherified first."""
+        if z.dim() == 1:
+            z = z.unsqueeze(0)
+        norm = z.norm(dim=-1, keepdim=True)
+        if not torch.allclose(norm, torch.full_like(norm, self.radius), atol=1e-2):
+            z = self.spherify(z)
+        return self.decode_from_sphere(z)

@@ -277,3 +277,59 @@ class Codebook(tnn.Module):
 
     def forward(self, code):
         return self.weight[code]  # index gather for decode_code / sampling (outside the training path)
+
+
+class TokenLinear(tnn.Module):
+    """nn.Linear (same parameter names, shapes and init draws) on the last dimension of [..., in]: a 1x1 convolution over the rows.
+    gelu=True: the linear runs without its bias and ops.bias_gelu adds it under the exact GELU (one pass; the bias gradient is the
+    column sum of that op's dx)."""
+
+    def __init__(self, fin, fout):
+        super().__init__()
+        ref = tnn.Linear(fin, fout)
+        self.weight = tnn.Parameter(ref.weight.detach().clone())
+        self.bias = tnn.Parameter(ref.bias.detach().clone())
+        self.in_features, self.out_features = fin, fout
+
+    def forward(self, x, gelu=False):
+        if gelu:
+            return ops.bias_gelu(ops.token_linear(x, self.weight), self.bias)
+        return ops.token_linear(x, self.weight, self.bias)
+
+    def extra_repr(self):
+        return f"{self.in_features}, {self.out_features}"
+
+
+class LayerNorm(tnn.Module):
+    """nn.LayerNorm(dim) over the last dimension: eps 1e-5, weight ones, bias zeros (no init draws)."""
+
+    def __init__(self, dim, eps=1e-5):
+        super().__init__()
+        self.weight = tnn.Parameter(torch.ones(dim))
+        self.bias = tnn.Parameter(torch.zeros(dim))
+        self.eps, self.dim = eps, dim
+
+    def forward(self, x):
+        return ops.layer_norm(x, self.weight, self.bias, self.eps)
+
+    def extra_repr(self):
+        return f"{self.dim}"
+
+
+class RMSNorm(tnn.Module):
+    """The reference's RMSNorm (models/sphere_encoder_vit.py:34-50): x / sqrt(mean(x^2) + eps) * weight.  `pos`: a constant [N, D]
+    table added to the result in the same launch."""
+
+    def __init__(self, dim, eps=1e-6, elementwise_affine=True):
+        super().__init__()
+        self.eps, self.elementwise_affine, self.dim = eps, elementwise_affine, dim
+        if elementwise_affine:
+            self.weight = tnn.Parameter(torch.ones(dim))
+        else:
+            self.register_parameter("weight", None)
+
+    def forward(self, x, pos=None):
+        return ops.rms_norm(x, self.weight, self.eps, pos)
+
+    def extra_repr(self):
+        return f"{self.dim}"

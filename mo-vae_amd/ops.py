@@ -2091,7 +2091,7 @@ def cross_entropy(logits, target):
 
 # ---------------------------------------------------------------------------------------------
 # PixelSNAIL's causal self-attention (models/pixelcnn_prior.py:95-135; csrc/attention.hip)
-def _attn_ws(device, nbytes):
+def _ws_at_least(device, nbytes):
     """The shared workspace when it is large enough, else a buffer of this call's own (the first 4 KiB header stays zero)."""
     w = L.workspace(device)
     if w.numel() >= nbytes:
@@ -2132,7 +2132,7 @@ class CausalAttention(Function):
         B, heads, n, hd, p, seed, draw = ctx.cfg
         do = _c(do)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        ws = _attn_ws(q.device, L.load().movae_causal_attn_ws_bytes(B, heads, n))
+        ws = _ws_at_least(q.device, L.load().movae_causal_attn_ws_bytes(B, heads, n))
         _call("movae_causal_attn_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), heads * hd, o.data_ptr(), do.data_ptr(), lse.data_ptr(),
               dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, heads, n, hd, p, seed, draw, ws.data_ptr(), ws.numel(), _st(q))
         return dq, dk, dv, None, None, None, None
@@ -2149,3 +2149,240 @@ def causal_attention_dropout_mask(bh, n, p, seed, draw, device):
     keep = torch.empty((bh, n, n), dtype=torch.uint8, device=device)
     _call("movae_causal_attn_dropout_mask", keep.data_ptr(), bh, n, float(p), int(seed), int(draw), L.stream_ptr(keep.device))
     return keep
+
+
+# ---------------------------------------------------------------------------------------------
+# The transformer operator set of the ViT Sphere Encoder (models/sphere_encoder_vit.py; csrc/attention.hip, csrc/vit.hip).  The
+# batched full-Jacobian walker (autojac._batched_pullback) does not cover these ops: their backward_batched says so, and
+# autojac.backward_through then takes one autograd pass per loss.
+def _no_walker(name):
+    def backward_batched(ctx, G, *dy):
+        raise NotImplementedError(f"{name}: the batched Jacobian walker does not cover this op; one autograd pass per loss instead")
+
+    return staticmethod(backward_batched)
+
+
+class Attention(Function):
+    """softmax(rope(Q) rope(K)^T / sqrt(hd)) V over the packed projection qkv [B, N, 3C] (q at channel 0, k at C, v at 2C; head h at
+    h*hd), read in place; the result is [B, N, C] head-major (AttentionWithRoPE.forward, sphere_encoder_vit.py:157-167).  cos / sin:
+    the RoPE tables [N, hd/2] (rope_tables), or None for no rotation.  dqkv comes back as one [B, N, 3C] buffer."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, cos, sin):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(qkv)
+        qkv = _c(qkv)
+        assert qkv.dim() == 3 and qkv.dtype == torch.float32, "attention: qkv is the packed fp32 projection [B, N, 3C]"
+        B, n, c3 = qkv.shape
+        if c3 % 3 or (c3 // 3) % heads:
+            raise ValueError(f"attention: {c3} channels do not split into q, k, v of {heads} heads")
+        c = c3 // 3
+        hd = c // heads
+        assert (cos is None) == (sin is None), "attention: give both RoPE tables or neither"
+        if cos is not None:
+            cos, sin = _c(cos), _c(sin)
+            assert cos.shape == sin.shape == (n, hd // 2) and cos.dtype == sin.dtype == torch.float32 and cos.device == qkv.device, \
+                f"attention: RoPE tables must be fp32 [{n}, {hd // 2}] on the input's device"
+        o = torch.empty((B, n, c), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((B * heads, n), dtype=qkv.dtype, device=qkv.device)
+        base = qkv.data_ptr()
+        _call("movae_attn_fwd", base, base + 4 * c, base + 8 * c, c3, _p(cos), _p(sin), o.data_ptr(), lse.data_ptr(), B, heads, n, hd, 0.0,
+              _st(qkv))
+        ctx.save_for_backward(qkv, o, lse, cos, sin)
+        ctx.cfg = (B, heads, n, hd)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        if do is None or not ctx.needs_input_grad[0]:
+            return (None,) * 4
+        qkv, o, lse, cos, sin = ctx.saved_tensors
+        B, heads, n, hd = ctx.cfg
+        c = heads * hd
+        do = _c(do)
+        dqkv = torch.empty_like(qkv)
+        ws = _ws_at_least(qkv.device, L.load().movae_attn_ws_bytes(B, heads, n))
+        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
+        _call("movae_attn_bwd", base, base + 4 * c, base + 8 * c, 3 * c, _p(cos), _p(sin), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dbase,
+              dbase + 4 * c, dbase + 8 * c, B, heads, n, hd, 0.0, ws.data_ptr(), ws.numel(), _st(qkv))
+        return dqkv, None, None, None
+
+    backward_batched = _no_walker("Attention")
+
+
+def attention(qkv, heads, cos=None, sin=None):
+    return Attention.apply(qkv, int(heads), cos, sin)
+
+
+def rope_tables(n, inv_freq, device):
+    """(cos, sin) [n, hd/2] of RotaryEmbedding.forward / apply_rotary_pos_emb (sphere_encoder_vit.py:71-106), formed on the CPU in fp32
+    with the reference's own expressions -- the kernels' parity with it then rests on no device sincosf -- and moved to `device`."""
+    freqs = torch.outer(torch.arange(n, dtype=torch.float32), inv_freq.detach().to(device="cpu", dtype=torch.float32))
+    return freqs.cos().contiguous().to(device), freqs.sin().contiguous().to(device)
+
+
+ROWNORM = {"layer": 0, "rms": 1}
+
+
+class RowNorm(Function):
+    """LayerNorm ("layer": biased variance, weight and bias) or RMSNorm ("rms": x / sqrt(mean(x^2) + eps) * weight) over the last
+    dimension of x [..., D]; weight / bias may be None.  `pos` [N, D] (a constant of the tape; the leading dimensions of x flatten to a
+    multiple of N rows) is added after the affine: out = norm(x) * w + b + pos[row % N]."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pos, mode, eps):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(x)
+        x = _c(x)
+        d = x.shape[-1]
+        rows = x.numel() // d
+        assert x.dtype == torch.float32 and (weight is None or weight.shape == (d,)) and (bias is None or bias.shape == (d,))
+        assert mode in ROWNORM and not (mode == "rms" and bias is not None), "RMSNorm has no bias"
+        if pos is not None:
+            pos = _c(pos)
+            assert pos.dim() == 2 and pos.shape[1] == d and rows % pos.shape[0] == 0 and not pos.requires_grad, "pos is a constant [N, D] table"
+        y = torch.empty_like(x)
+        rstd = torch.empty(rows, dtype=x.dtype, device=x.device)
+        mean = torch.empty(rows, dtype=x.dtype, device=x.device) if mode == "layer" else None
+        _call("movae_rownorm_fwd", x.data_ptr(), _p(weight), _p(bias), _p(pos), pos.shape[0] if pos is not None else 0, y.data_ptr(), _p(mean),
+              rstd.data_ptr(), rows, d, ROWNORM[mode], float(eps), _st(x))
+        ctx.mode = mode
+        ctx.save_for_backward(x, weight, bias, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 6
+        x, weight, bias, mean, rstd = ctx.saved_tensors
+        dy = _c(dy)
+        d = x.shape[-1]
+        rows = x.numel() // d
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[0] else None
+        dw = _sink(0, weight, (d,)) if weight is not None and need[1] else None
+        db = _sink(0, bias, (d,)) if bias is not None and need[2] else None
+        if dx is None and dw is None and db is None:
+            return (None,) * 6
+        ws = _ws_at_least(x.device, L.load().movae_rownorm_ws_bytes(rows, d))
+        _call("movae_rownorm_bwd", dy.data_ptr(), x.data_ptr(), _p(weight), _p(mean), rstd.data_ptr(), _p(dx), _p(dw), _p(db), rows, d,
+              ROWNORM[ctx.mode], ws.data_ptr(), ws.numel(), _st(x))
+        return dx, dw, db, None, None, None
+
+    backward_batched = _no_walker("RowNorm")
+
+
+def layer_norm(x, weight=None, bias=None, eps=1e-5, pos=None):
+    return RowNorm.apply(x, weight, bias, pos, "layer", eps)
+
+
+def rms_norm(x, weight=None, eps=1e-6, pos=None):
+    return RowNorm.apply(x, weight, None, pos, "rms", eps)
+
+
+class BiasGelu(Function):
+    """gelu(x + bias) with the exact erf form (nn.GELU()), on the BIAS-FREE output x [..., C] of the linear in front; bias [C] or None.
+    The backward recomputes x + bias from the saved x, writes dx and -- the bias gradient of that linear -- the column sums of dx."""
+
+    @staticmethod
+    def forward(ctx, x, bias):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(x)
+        x = _c(x)
+        c = x.shape[-1]
+        assert x.dtype == torch.float32 and (bias is None or bias.shape == (c,))
+        y = torch.empty_like(x)
+        _call("movae_bias_gelu_fwd", x.data_ptr(), _p(bias), y.data_ptr(), x.numel() // c, c, _st(x))
+        ctx.save_for_backward(x, bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 2
+        x, bias = ctx.saved_tensors
+        dy = _c(dy)
+        c = x.shape[-1]
+        rows = x.numel() // c
+        dx = torch.empty_like(x)
+        _call("movae_bias_gelu_bwd", dy.data_ptr(), x.data_ptr(), _p(bias), dx.data_ptr(), rows, c, _st(x))
+        db = None
+        if bias is not None and ctx.needs_input_grad[1]:
+            db = _sink(0, bias, (c,))
+            wsp, wsb = _ws(x)
+            _call("movae_colsum", dx.data_ptr(), db.data_ptr(), rows, c, 0, wsp, wsb, _st(x))
+        return (dx if ctx.needs_input_grad[0] else None), db
+
+    backward_batched = _no_walker("BiasGelu")
+
+
+def bias_gelu(x, bias=None):
+    return BiasGelu.apply(x, bias)
+
+
+class UnpatchifyAct(Function):
+    """tanh(Unpatchify(x)) (sphere_encoder_vit.py:125-140, :388): x [B, N, p*p*C] -> the NHWC image [B, H, W, C]."""
+
+    @staticmethod
+    def forward(ctx, x, h, w, c, patch):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(x)
+        x = _c(x)
+        b = x.shape[0]
+        assert x.dtype == torch.float32 and h % patch == 0 and w % patch == 0 and x.numel() == b * h * w * c, \
+            f"unpatchify: {tuple(x.shape)} is not {h}x{w}x{c} in patches of {patch}"
+        y = torch.empty((b, h, w, c), dtype=x.dtype, device=x.device)
+        _call("movae_unpatchify_act_fwd", x.data_ptr(), y.data_ptr(), b, h, w, c, patch, _st(x))
+        ctx.geom = (b, h, w, c, patch)
+        ctx.xshape = tuple(x.shape)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None or not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        (y,) = ctx.saved_tensors
+        dy = _c(dy)
+        dx = torch.empty(ctx.xshape, dtype=y.dtype, device=y.device)
+        _call("movae_unpatchify_act_bwd", dy.data_ptr(), y.data_ptr(), dx.data_ptr(), *ctx.geom, _st(y))
+        return (dx,) + (None,) * 4
+
+    backward_batched = _no_walker("UnpatchifyAct")
+
+
+def unpatchify_act(x, h, w, c, patch):
+    return UnpatchifyAct.apply(x, int(h), int(w), int(c), int(patch))
+
+
+class AddRowsBcast(Function):
+    """x [..., N, D] + pos [N, D] (SinusoidalPosEmbedding.forward); pos is a constant of the tape, the backward the identity."""
+
+    @staticmethod
+    def forward(ctx, x, pos):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(x)
+        x, pos = _c(x), _c(pos)
+        n, d = pos.shape
+        assert x.shape[-1] == d and (x.numel() // d) % n == 0 and not pos.requires_grad
+        y = torch.empty_like(x)
+        _call("movae_add_rows_bcast", x.data_ptr(), pos.data_ptr(), y.data_ptr(), x.numel() // d, n, d, _st(x))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, None
+
+    backward_batched = _no_walker("AddRowsBcast")
+
+
+def add_rows_bcast(x, pos):
+    return AddRowsBcast.apply(x, pos)
+
+
+def token_linear(x, w, b=None):
+    """x [..., in], w [out, in] -> [..., out]: a 1x1 convolution over the flattened rows, as `linear` is for two dimensions."""
+    fin = x.shape[-1]
+    rows = x.numel() // fin
+    y = Conv.apply(x.reshape(rows, 1, 1, fin), w.view(w.shape[0], fin, 1, 1), b, 1, 0, 0, False, None, 0.01)
+    return y.reshape(*x.shape[:-1], w.shape[0])
