@@ -384,8 +384,10 @@ int movae_scale_by_clip(float* g, size_t n, const float* sumsq_dev, float max_no
  * MOVAE_DTYPE_BF16: the 128x128 implicit-GEMM convolution kernels (forward, input gradient, weight gradient -- the layers that
  * are MFMA-bound at the C3-C5 shapes) round their two operands to bf16 on the way into LDS and multiply on
  * v_mfma_f32_32x32x16_bf16 with fp32 accumulation; tensors in memory, master weights, BatchNorm, losses, aggregation and the
- * optimizer stay fp32.  Process-wide, returns the previous setting.  The default, MOVAE_DTYPE_F32, is the parity path: results
- * under bf16 are held to their own, looser tolerance (tests/test_hip_bf16.py), never to the fp32 oracle's. */
+ * optimizer stay fp32.  The attention entry points (movae_attn_*, movae_causal_attn_*) take their bf16-operand instances in this
+ * mode too: q and k after RoPE, v, dO, the dropout-scaled probabilities and dS are rounded, everything else stays fp32; a backward
+ * must run under the dtype of its forward (the saved lse carries the forward's rounding).  Process-wide, returns the previous setting.  The default, MOVAE_DTYPE_F32, is the parity path: results
+ * under bf16 are held to their own, looser tolerance (tests/test_hip_bf16.py, tests/test_hip_bf16_attention.py), never to the fp32 oracle's. */
 #define MOVAE_DTYPE_F32 0
 #define MOVAE_DTYPE_BF16 1
 int movae_set_compute_dtype(int dtype);

@@ -222,10 +222,18 @@ DTYPES = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 
 def set_compute_dtype(name):
     """"fp32" (default, the parity path) | "bf16": bf16 operands / fp32 accumulation in the 128x128 implicit-GEMM kernels
-    (include/movae.h: movae_set_compute_dtype).  Returns the previous setting's name."""
+    and the attention kernels (include/movae.h: movae_set_compute_dtype).  Returns the previous setting's name."""
     if name not in DTYPES:
         raise ValueError(f"compute dtype must be one of {sorted(set(DTYPES))}, got {name!r}")
     prev = load().movae_set_compute_dtype(DTYPES[name])
+    return "bf16" if prev == 1 else "fp32"
+
+
+def compute_dtype():
+    """The current setting's name.  The library has one setter and no getter: set fp32, read what that replaced, put it back."""
+    lib = load()
+    prev = lib.movae_set_compute_dtype(DTYPES["fp32"])
+    lib.movae_set_compute_dtype(prev)
     return "bf16" if prev == 1 else "fp32"
 
 

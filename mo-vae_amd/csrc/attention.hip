@@ -27,6 +27,21 @@
 // the angle whose cos / sin the host tabulated at [n][t]; (u[2t], u[2t+1]) -> (u[2t] c - u[2t+1] s, u[2t] s + u[2t+1] c).  The pair
 // partner of an element is in the same lane for the g*NS + s loads (NS is even) and in lane c ^ 1 for the cc*16 + c loads; dq / dk
 // come out as gradients of the ROTATED rows and are rotated back (the transpose rotation) in registers before the store.
+//
+// bf16 operands (movae_set_compute_dtype(MOVAE_DTYPE_BF16): attn_fwd_bf_k, attn_bwd_dkdv_bf_k, attn_bwd_dq_bf_k; every hd <= 64 and
+// every causal / dropout / RoPE combination takes them in that mode -- no shape stays on the fp32 instances).  Same entry points, HBM
+// layouts, workspace, tile-to-wave map, orientation and masks; v_mfma_f32_16x16x32_bf16, whose C/D map is the fp32 form's.  Rounded
+// to bf16 (RNE, __builtin_convertvector): q and k AFTER RoPE, v, dO, the probabilities after the dropout scaling, and dS with its
+// 1 / sqrt(hd).  fp32: accumulation, the logits' scale, the running max, the row sum (of the UNROUNDED probabilities), lse, delta
+// (attn_delta_k as it is), dP - delta and the rotation back of dq / dk.  The loop step is 32 keys (queries in dK / dV): two 16-row
+// first products whose 2 x 4 accumulator registers, converted pairwise, are the B operand of ONE 32-deep second product.  k slot
+// (g, e) of that step is position 16 (e >> 2) + 4 g + (e & 3), so the A operand (V^T, K^T; dO^T, Q^T) is read from a TRANSPOSED
+// LDS image [d][position] as the two 4-position runs at 4 g and 16 + 4 g.  Each step's tiles are staged once per block, as bf16,
+// and shared by the four waves: a row image [32][HDP + 8] (d contiguous; the A operand of the first products, one ds_read_b128 per
+// lane) and a transposed image [16 NC][36] (the second products), both written from registers that were loaded a step ahead.
+// RoPE is applied between the global load and the LDS store.  Every wave reaches both barriers of every step: waves whose tile lies
+// beyond L, or (causal) beyond the diagonal for this step, skip only the arithmetic.  The head dim is covered by NC = 1 / 2 / 4
+// chunks of 16 output columns and padded to HDP = 32 / 32 / 64 in the reduction.
 #include "common.h"
 
 namespace {
@@ -409,6 +424,419 @@ __global__ __launch_bounds__(256) void attn_mask_k(AttnArgs a, uint8_t* __restri
     }
 }
 
+// ---- bf16-operand instances (movae_set_compute_dtype(MOVAE_DTYPE_BF16); see the header) --------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+constexpr int BF_STEP = 32;  // keys (queries in dK / dV) per loop step: one 32-deep MFMA step of the second product
+constexpr int BF_LDT = 36;   // halfs per row of a transposed image: 32 positions + 4 of padding (72-byte rows)
+
+__device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// A tensor as the staging code sees it: element (row, d) of this (b, h) at p[row * ld + d * ds]
+struct BfSrc {
+    const float* p;
+    long ld;
+    int ds;
+    bool v4;  // every aligned group of 4 consecutive d of a row is one aligned 16-byte run (block-uniform)
+};
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ BfSrc bf_src(const float* p, long ld, int ds, int hd) {
+    return BfSrc{p, ld, ds, ds == 1 && (ld & 3) == 0 && (hd & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0};
+}
+
+// Row image R[32][HDP + 8] (bf16, d contiguous): rows r0 .. r0+31 of `src`, rotated if ROPE, zero beyond L / hd.  Item = (row,
+// 4 consecutive d); a thread holds HDP / 32 of them between its global loads and its LDS stores.
+template <int HDP, bool ROPE>
+__device__ __forceinline__ void row_load(const AttnArgs& a, const BfSrc& src, int r0, f32x4 (&v)[HDP / 32]) {
+#pragma unroll
+    for (int n = 0; n < HDP / 32; ++n) {
+        const int it = threadIdx.x + 256 * n, row = r0 + it / (HDP / 4), d0 = (it % (HDP / 4)) * 4;
+        float u[4];
+        if (src.v4) {
+            const f32x4 t = (row < a.L && d0 < a.hd) ? *reinterpret_cast<const f32x4*>(src.p + row * src.ld + d0) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) u[e] = t[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) u[e] = (row < a.L && d0 + e < a.hd) ? src.p[row * src.ld + (long)(d0 + e) * src.ds] : 0.f;
+        }
+        if (ROPE) rope_run<4>(a, u, row, d0, row < a.L);
+        v[n] = f32x4{u[0], u[1], u[2], u[3]};
+    }
+}
+template <int HDP>
+__device__ __forceinline__ void row_store(__bf16* __restrict__ R, const f32x4 (&v)[HDP / 32]) {
+#pragma unroll
+    for (int n = 0; n < HDP / 32; ++n) {
+        const int it = threadIdx.x + 256 * n;
+        *reinterpret_cast<bf16x4*>(R + (it / (HDP / 4)) * (HDP + 8) + (it % (HDP / 4)) * 4) = __builtin_convertvector(v[n], bf16x4);
+    }
+}
+
+// Transposed image T[NC * 16][BF_LDT] (bf16, position contiguous) of the same rows.  Item = (4 consecutive rows, one RoPE pair of
+// d): 64 * NC items, one for each of the first 64 * NC threads; u[2e + x] = element 2 * pair + x of row 4 * quad + e.
+template <int NC, bool ROPE>
+__device__ __forceinline__ void tr_load(const AttnArgs& a, const BfSrc& src, int r0, float (&u)[8]) {
+    const int it = threadIdx.x;
+    if (it >= 64 * NC) return;
+    const int pr = it % (NC * 8), kq = it / (NC * 8), hh = a.hd >> 1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int row = r0 + 4 * kq + e;
+        float x0, x1;
+        if (src.v4) {
+            const f32x2 t = (row < a.L && 2 * pr < a.hd) ? *reinterpret_cast<const f32x2*>(src.p + row * src.ld + 2 * pr) : f32x2{0.f, 0.f};
+            x0 = t[0], x1 = t[1];
+        } else {
+            x0 = (row < a.L && 2 * pr < a.hd) ? src.p[row * src.ld + (long)(2 * pr) * src.ds] : 0.f;
+            x1 = (row < a.L && 2 * pr + 1 < a.hd) ? src.p[row * src.ld + (long)(2 * pr + 1) * src.ds] : 0.f;
+        }
+        if (ROPE && row < a.L && pr < hh) {
+            const float cs = a.cos[(long)row * hh + pr], sn = a.sin[(long)row * hh + pr], y0 = x0;
+            x0 = y0 * cs - x1 * sn;
+            x1 = y0 * sn + x1 * cs;
+        }
+        u[2 * e] = x0, u[2 * e + 1] = x1;
+    }
+}
+template <int NC>
+__device__ __forceinline__ void tr_store(__bf16* __restrict__ T, const float (&u)[8]) {
+    const int it = threadIdx.x;
+    if (it >= 64 * NC) return;
+    const int pr = it % (NC * 8), kq = it / (NC * 8);
+    *reinterpret_cast<bf16x4*>(T + (2 * pr) * BF_LDT + 4 * kq) = __builtin_convertvector((f32x4{u[0], u[2], u[4], u[6]}), bf16x4);
+    *reinterpret_cast<bf16x4*>(T + (2 * pr + 1) * BF_LDT + 4 * kq) = __builtin_convertvector((f32x4{u[1], u[3], u[5], u[7]}), bf16x4);
+}
+
+// The wave's own 16 rows as the B operand of the first product: lane (c, g) holds elements 32 ks + 8 g .. + 7 of row `row`
+template <int HDP, bool ROPE>
+__device__ __forceinline__ void own_frag(const AttnArgs& a, const BfSrc& src, int row, int g, bf16x8 (&f)[HDP / 32]) {
+#pragma unroll
+    for (int ks = 0; ks < HDP / 32; ++ks) {
+        const int d0 = 32 * ks + 8 * g;
+        float u[8];
+        if (src.v4) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const f32x4 t = (row < a.L && d0 + 4 * q < a.hd) ? *reinterpret_cast<const f32x4*>(src.p + row * src.ld + d0 + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) u[4 * q + e] = t[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) u[e] = (row < a.L && d0 + e < a.hd) ? src.p[row * src.ld + (long)(d0 + e) * src.ds] : 0.f;
+        }
+        if (ROPE) rope_run<8>(a, u, row, d0, row < a.L);
+        f[ks] = __builtin_convertvector((f32x8{u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7]}), bf16x8);
+    }
+}
+
+// first product of a pair: rows 16 s + c of a row image against the wave's own fragment
+template <int HDP>
+__device__ __forceinline__ f32x4 mma_rows(const __bf16* __restrict__ R, int s, int c, int g, const bf16x8 (&own)[HDP / 32]) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < HDP / 32; ++ks)
+        acc = mfma32(*reinterpret_cast<const bf16x8*>(R + (16 * s + c) * (HDP + 8) + 32 * ks + 8 * g), own[ks], acc);
+    return acc;
+}
+
+// second product of a pair: acc[cc] (row d = cc * 16 + 4 g + r, column = the wave's row c) += T[d][pos] * x[pos], x the first
+// product's two accumulators.  k slot (g, e) of the 32-deep step is position 16 (e >> 2) + 4 g + (e & 3) on BOTH operands: x packs
+// its registers in that order and T is read as the two 4-position runs at 4 g and 16 + 4 g.
+template <int NC>
+__device__ __forceinline__ void mma_cols(const __bf16* __restrict__ T, int c, int g, const float (&x0)[4], const float (&x1)[4], f32x4 (&acc)[NC]) {
+    const bf16x8 xb = __builtin_convertvector((f32x8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]}), bf16x8);
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) {
+        const __bf16* t = T + (cc * 16 + c) * BF_LDT + 4 * g;
+        const bf16x4 lo = *reinterpret_cast<const bf16x4*>(t), hi = *reinterpret_cast<const bf16x4*>(t + 16);
+        acc[cc] = mfma32(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7), xb, acc[cc]);
+    }
+}
+
+// block-level tile order: work group t handles 4 consecutive 16-row tiles of one (b, h), one per wave (wave_tile's order)
+__device__ __forceinline__ void block_tile(const AttnArgs& a, bool rev, int& grp, int& bh) {
+    const int ngrp = (a.ntiles + 3) >> 2;
+    const int t = blockIdx.x / a.nbh;
+    bh = blockIdx.x - t * a.nbh;
+    grp = rev ? ngrp - 1 - t : t;
+}
+
+// NC: 16-wide chunks of the head dim that exist (1, 2 or 4); the reduction over d is padded to HDP = 32 or 64
+template <int NC, bool DROP, bool CAUSAL, bool ROPE>
+__global__ __launch_bounds__(256) void attn_fwd_bf_k(AttnArgs a) {
+    constexpr int HDP = NC <= 2 ? 32 : 64, KS = HDP / 32;
+    __shared__ __attribute__((aligned(16))) __bf16 Ks[BF_STEP * (HDP + 8)];
+    __shared__ __attribute__((aligned(16))) __bf16 Vt[NC * 16 * BF_LDT];
+    int grp, bh;
+    block_tile(a, CAUSAL, grp, bh);
+    const int qt = grp * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd;
+    const long row0 = (long)b * L;
+    const BfSrc qs = bf_src(a.q + row0 * a.ld + h * hd, a.ld, 1, hd), ks = bf_src(a.k + row0 * a.ld + h * hd, a.ld, 1, hd),
+                vs = bf_src(a.v + row0 * a.ld + h * hd, a.ld, 1, hd);
+    const int i0 = qt * 16, i = i0 + c;
+    const float sl2 = a.scale * LOG2E;
+    bf16x8 qf[KS];
+    own_frag<HDP, ROPE>(a, qs, i, g, qf);
+    f32x4 acc[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) acc[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+    const int kend = CAUSAL ? min(L, (grp * 4 + 4) * 16) : L;  // keys the block's last query tile sees
+    const int nsteps = (kend + BF_STEP - 1) / BF_STEP;
+    f32x4 kreg[KS];
+    float vreg[8];
+    row_load<HDP, ROPE>(a, ks, 0, kreg);
+    tr_load<NC, false>(a, vs, 0, vreg);
+    for (int step = 0; step < nsteps; ++step) {
+        __syncthreads();  // every wave is done with the previous tile
+        row_store<HDP>(Ks, kreg);
+        tr_store<NC>(Vt, vreg);
+        __syncthreads();
+        if (step + 1 < nsteps) {
+            row_load<HDP, ROPE>(a, ks, (step + 1) * BF_STEP, kreg);
+            tr_load<NC, false>(a, vs, (step + 1) * BF_STEP, vreg);
+        }
+        const int j0 = step * BF_STEP;
+        if (qt >= a.ntiles || (CAUSAL && j0 > i0 + 15)) continue;  // (wave-uniform; the barriers are above)
+        float p[2][4], mx = -INFINITY;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f32x4 st = mma_rows<HDP>(Ks, s, c, g, qf);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = j0 + 16 * s + 4 * g + r;
+                p[s][r] = ((!CAUSAL || j <= i) && j < L) ? st[r] * sl2 : -INFINITY;
+                mx = fmaxf(mx, p[s][r]);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        // key 0 is in the first step and visible to every lane (padded query rows included): mn is finite from there on
+        const float mn = fmaxf(m, mx), alpha = exp2f(m - mn);
+        float rs = 0.f;
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                p[s][r] = exp2f(p[s][r] - mn);
+                rs += p[s][r];  // the row sum takes the unrounded probabilities
+            }
+        rs += __shfl_xor(rs, 16, 64);
+        rs += __shfl_xor(rs, 32, 64);
+        l = l * alpha + rs;
+        m = mn;
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc) acc[cc] *= alpha;
+        if (DROP) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                unsigned w[4];
+                keep4(a, bh, i, (j0 >> 2) + 4 * s + g, w);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) p[s][r] = w[r] < a.thr ? p[s][r] * a.inv_keep : 0.f;
+            }
+        }
+        mma_cols<NC>(Vt, c, g, p[0], p[1], acc);
+    }
+    if (i >= L) return;
+    const float inv_l = 1.f / l;
+    const int proj = a.heads * hd;
+    float* ob = a.out + (row0 + i) * proj + h * a.oh;
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = cc * 16 + 4 * g + r;
+            if (d < hd) ob[(long)d * a.od] = acc[cc][r] * inv_l;
+        }
+    if (g == 0) a.lse_out[(long)bh * L + i] = (m + log2f(l)) * LN2;
+}
+
+// keep bits of (query iq0 + r, key j0 + c), r = 0 .. 3, as bits of the result: attn_bwd_dkdv_k's quad transpose
+__device__ __forceinline__ unsigned keep_quad(const AttnArgs& a, int bh, int iq0, int j0, int lane) {
+    const int c = lane & 15, k = c & 3;
+    unsigned w[4];
+    keep4(a, bh, iq0 + k, (j0 >> 2) + (c >> 2), w);
+    unsigned kmask = 0u;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int sw = (k - t) & 3;
+        const unsigned x = sw == 0 ? w[0] : sw == 1 ? w[1] : sw == 2 ? w[2] : w[3];
+        const int src = (lane & ~3) | ((k + t) & 3);
+        const int bit = __shfl((int)(x < a.thr), src, 64);
+        kmask |= (unsigned)bit << ((k + t) & 3);
+    }
+    return kmask;
+}
+
+template <int NC, bool DROP, bool CAUSAL, bool ROPE>
+__global__ __launch_bounds__(256) void attn_bwd_dkdv_bf_k(AttnArgs a) {
+    constexpr int HDP = NC <= 2 ? 32 : 64, KS = HDP / 32;
+    __shared__ __attribute__((aligned(16))) __bf16 Qs[BF_STEP * (HDP + 8)];
+    __shared__ __attribute__((aligned(16))) __bf16 Gs[BF_STEP * (HDP + 8)];
+    __shared__ __attribute__((aligned(16))) __bf16 Qt[NC * 16 * BF_LDT];
+    __shared__ __attribute__((aligned(16))) __bf16 Gt[NC * 16 * BF_LDT];
+    int grp, bh;
+    block_tile(a, false, grp, bh);
+    const int kt = grp * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd, heads = a.heads;
+    const long row0 = (long)b * L;
+    const BfSrc qs = bf_src(a.q + row0 * a.ld + h * hd, a.ld, 1, hd), ks = bf_src(a.k + row0 * a.ld + h * hd, a.ld, 1, hd),
+                vs = bf_src(a.v + row0 * a.ld + h * hd, a.ld, 1, hd);
+    const BfSrc gs = bf_src(a.dout + row0 * heads * hd + h * a.oh, (long)heads * hd, a.od, hd);
+    const float *lseb = a.lse + (long)bh * L, *delb = a.delta + (long)bh * L;
+    const int j0 = kt * 16, j = j0 + c;
+    const float sl2 = a.scale * LOG2E;
+    bf16x8 kf[KS], vf[KS];
+    own_frag<HDP, ROPE>(a, ks, j, g, kf);
+    own_frag<HDP, false>(a, vs, j, g, vf);
+    f32x4 adk[NC], adv[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) adk[cc] = adv[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int ibeg = CAUSAL ? grp * 64 : 0;  // the block's first key tile starts here: no earlier query sees any of its keys
+    const int nsteps = (L - ibeg + BF_STEP - 1) / BF_STEP;
+    f32x4 qreg[KS], greg[KS];
+    float qtr[8], gtr[8];
+    row_load<HDP, ROPE>(a, qs, ibeg, qreg);
+    row_load<HDP, false>(a, gs, ibeg, greg);
+    tr_load<NC, ROPE>(a, qs, ibeg, qtr);
+    tr_load<NC, false>(a, gs, ibeg, gtr);
+    for (int step = 0; step < nsteps; ++step) {
+        __syncthreads();
+        row_store<HDP>(Qs, qreg);
+        row_store<HDP>(Gs, greg);
+        tr_store<NC>(Qt, qtr);
+        tr_store<NC>(Gt, gtr);
+        __syncthreads();
+        const int i0 = ibeg + step * BF_STEP;
+        if (step + 1 < nsteps) {
+            row_load<HDP, ROPE>(a, qs, i0 + BF_STEP, qreg);
+            row_load<HDP, false>(a, gs, i0 + BF_STEP, greg);
+            tr_load<NC, ROPE>(a, qs, i0 + BF_STEP, qtr);
+            tr_load<NC, false>(a, gs, i0 + BF_STEP, gtr);
+        }
+        if (kt >= a.ntiles || (CAUSAL && i0 + BF_STEP - 1 < j0)) continue;  // (wave-uniform)
+        float pk[2][4], ds[2][4];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f32x4 st = mma_rows<HDP>(Qs, s, c, g, kf), dpt = mma_rows<HDP>(Gs, s, c, g, vf);
+            unsigned kmask = 0xFu;
+            if (DROP) kmask = keep_quad(a, bh, i0 + 16 * s + 4 * g, j0, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = i0 + 16 * s + 4 * g + r;
+                const bool ok = i < L && (CAUSAL ? j <= i : j < L);
+                const float p = ok ? exp2f(st[r] * sl2 - lseb[i] * LOG2E) : 0.f;
+                float dp = dpt[r], pd = p;
+                if (DROP) {
+                    const bool kp = (kmask >> r) & 1u;
+                    dp = kp ? dp * a.inv_keep : 0.f;
+                    pd = kp ? p * a.inv_keep : 0.f;
+                }
+                pk[s][r] = pd;
+                ds[s][r] = ok ? p * (dp - delb[i]) * a.scale : 0.f;
+            }
+        }
+        mma_cols<NC>(Gt, c, g, pk[0], pk[1], adv);
+        mma_cols<NC>(Qt, c, g, ds[0], ds[1], adk);
+    }
+    if (kt >= a.ntiles || j >= L) return;
+    if (ROPE) rope_back<NC>(a, adk, j, g);
+    float *dkb = a.dk + (row0 + j) * a.ld + h * hd, *dvb = a.dv + (row0 + j) * a.ld + h * hd;
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = cc * 16 + 4 * g + r;
+            if (d < hd) {
+                dkb[d] = adk[cc][r];  // (1 / sqrt(hd) is inside dS)
+                dvb[d] = adv[cc][r];
+            }
+        }
+}
+
+template <int NC, bool DROP, bool CAUSAL, bool ROPE>
+__global__ __launch_bounds__(256) void attn_bwd_dq_bf_k(AttnArgs a) {
+    constexpr int HDP = NC <= 2 ? 32 : 64, KS = HDP / 32;
+    __shared__ __attribute__((aligned(16))) __bf16 Ks[BF_STEP * (HDP + 8)];
+    __shared__ __attribute__((aligned(16))) __bf16 Vs[BF_STEP * (HDP + 8)];
+    __shared__ __attribute__((aligned(16))) __bf16 Kt[NC * 16 * BF_LDT];
+    int grp, bh;
+    block_tile(a, CAUSAL, grp, bh);
+    const int qt = grp * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int b = bh / a.heads, h = bh - b * a.heads, L = a.L, hd = a.hd, heads = a.heads;
+    const long row0 = (long)b * L;
+    const BfSrc qs = bf_src(a.q + row0 * a.ld + h * hd, a.ld, 1, hd), ks = bf_src(a.k + row0 * a.ld + h * hd, a.ld, 1, hd),
+                vs = bf_src(a.v + row0 * a.ld + h * hd, a.ld, 1, hd);
+    const BfSrc gs = bf_src(a.dout + row0 * heads * hd + h * a.oh, (long)heads * hd, a.od, hd);
+    const int i0 = qt * 16, i = i0 + c;
+    const float sl2 = a.scale * LOG2E;
+    bf16x8 qf[KS], gf[KS];
+    own_frag<HDP, ROPE>(a, qs, i, g, qf);
+    own_frag<HDP, false>(a, gs, i, g, gf);
+    const float lse2 = i < L ? a.lse[(long)bh * L + i] * LOG2E : 0.f, di = i < L ? a.delta[(long)bh * L + i] : 0.f;
+    f32x4 acc[NC];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc) acc[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int kend = CAUSAL ? min(L, (grp * 4 + 4) * 16) : L;
+    const int nsteps = (kend + BF_STEP - 1) / BF_STEP;
+    f32x4 kreg[KS], vreg[KS];
+    float ktr[8];
+    row_load<HDP, ROPE>(a, ks, 0, kreg);
+    row_load<HDP, false>(a, vs, 0, vreg);
+    tr_load<NC, ROPE>(a, ks, 0, ktr);
+    for (int step = 0; step < nsteps; ++step) {
+        __syncthreads();
+        row_store<HDP>(Ks, kreg);
+        row_store<HDP>(Vs, vreg);
+        tr_store<NC>(Kt, ktr);
+        __syncthreads();
+        const int j0 = step * BF_STEP;
+        if (step + 1 < nsteps) {
+            row_load<HDP, ROPE>(a, ks, j0 + BF_STEP, kreg);
+            row_load<HDP, false>(a, vs, j0 + BF_STEP, vreg);
+            tr_load<NC, ROPE>(a, ks, j0 + BF_STEP, ktr);
+        }
+        if (qt >= a.ntiles || (CAUSAL && j0 > i0 + 15)) continue;  // (wave-uniform)
+        float ds[2][4];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f32x4 st = mma_rows<HDP>(Ks, s, c, g, qf), dpt = mma_rows<HDP>(Vs, s, c, g, gf);
+            unsigned w[4] = {0u, 0u, 0u, 0u};
+            if (DROP) keep4(a, bh, i, (j0 >> 2) + 4 * s + g, w);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = j0 + 16 * s + 4 * g + r;
+                const bool ok = i < L && (CAUSAL ? j <= i : j < L);
+                const float p = ok ? exp2f(st[r] * sl2 - lse2) : 0.f;
+                float dp = dpt[r];
+                if (DROP) dp = w[r] < a.thr ? dp * a.inv_keep : 0.f;
+                ds[s][r] = p * (dp - di) * a.scale;
+            }
+        }
+        mma_cols<NC>(Kt, c, g, ds[0], ds[1], acc);
+    }
+    if (i >= L) return;
+    if (ROPE) rope_back<NC>(a, acc, i, g);
+    float* dqb = a.dq + (row0 + i) * a.ld + h * hd;
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int d = cc * 16 + 4 * g + r;
+            if (d < hd) dqb[d] = acc[cc][r];  // (1 / sqrt(hd) is inside dS)
+        }
+}
+
 int hdp_of(int hd) { return hd <= 8 ? 8 : hd <= 16 ? 16 : hd <= 32 ? 32 : 64; }
 
 // common argument checks and the per-call constants; rc != MOVAE_OK: error already set
@@ -475,6 +903,26 @@ dim3 tile_grid(const AttnArgs& a) { return dim3((unsigned)(((a.ntiles + 3) / 4) 
         }                                                                                                          \
     } while (0)
 
+// the bf16-operand instances: one per count of 16-wide head-dim chunks (1 / 2 / 4) and, causal: dropout on / off; bidirectional:
+// RoPE on / off (`flag`)
+#define ATTN_BF_ONE(KERNEL, NC, a, causal, flag, stream)                                                                   \
+    do {                                                                                                                   \
+        if (causal) {                                                                                                      \
+            if (flag) hipLaunchKernelGGL((KERNEL<NC, true, true, false>), grid_, dim3(256), 0, stream, a);                 \
+            else hipLaunchKernelGGL((KERNEL<NC, false, true, false>), grid_, dim3(256), 0, stream, a);                     \
+        } else {                                                                                                           \
+            if (flag) hipLaunchKernelGGL((KERNEL<NC, false, false, true>), grid_, dim3(256), 0, stream, a);                \
+            else hipLaunchKernelGGL((KERNEL<NC, false, false, false>), grid_, dim3(256), 0, stream, a);                    \
+        }                                                                                                                  \
+    } while (0)
+#define ATTN_LAUNCH_BF(KERNEL, a, causal, flag, stream)                    \
+    do {                                                                   \
+        const dim3 grid_ = tile_grid(a);                                   \
+        if ((a).hd <= 16) ATTN_BF_ONE(KERNEL, 1, a, causal, flag, stream); \
+        else if ((a).hd <= 32) ATTN_BF_ONE(KERNEL, 2, a, causal, flag, stream); \
+        else ATTN_BF_ONE(KERNEL, 4, a, causal, flag, stream);              \
+    } while (0)
+
 // argument checks of the bidirectional entry points beyond setup()'s
 int setup_bidir(AttnArgs& a, const char* what, long ld, const float* cs, const float* sn, int B, int heads, int L, int hd, float p) {
     MOVAE_CHECK_ARG(p == 0.f, "%s: attention dropout is not supported (p must be 0, got %g)", what, (double)p);
@@ -499,7 +947,8 @@ int movae_causal_attn_fwd(const float* q, const float* k, const float* v, long l
     if (rc != MOVAE_OK) return rc;
     a.q = q, a.k = k, a.v = v, a.out = out, a.lse_out = lse;
     const bool drop = p > 0.f;
-    ATTN_LAUNCH(attn_fwd_k, a, drop, (hipStream_t)stream);
+    if (g_movae_compute_bf16) ATTN_LAUNCH_BF(attn_fwd_bf_k, a, true, drop, (hipStream_t)stream);
+    else ATTN_LAUNCH(attn_fwd_k, a, drop, (hipStream_t)stream);
     MOVAE_CHECK_LAUNCH("causal_attn_fwd");
     return MOVAE_OK;
 }
@@ -527,9 +976,11 @@ int movae_causal_attn_bwd(const float* q, const float* k, const float* v, long l
     MOVAE_CHECK_LAUNCH("causal_attn_delta");
     a.q = q, a.k = k, a.v = v, a.dout = dout, a.lse = lse, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
     const bool drop = p > 0.f;
-    ATTN_LAUNCH(attn_bwd_dkdv_k, a, drop, (hipStream_t)stream);
+    if (g_movae_compute_bf16) ATTN_LAUNCH_BF(attn_bwd_dkdv_bf_k, a, true, drop, (hipStream_t)stream);
+    else ATTN_LAUNCH(attn_bwd_dkdv_k, a, drop, (hipStream_t)stream);
     MOVAE_CHECK_LAUNCH("causal_attn_bwd_dkdv");
-    ATTN_LAUNCH(attn_bwd_dq_k, a, drop, (hipStream_t)stream);
+    if (g_movae_compute_bf16) ATTN_LAUNCH_BF(attn_bwd_dq_bf_k, a, true, drop, (hipStream_t)stream);
+    else ATTN_LAUNCH(attn_bwd_dq_k, a, drop, (hipStream_t)stream);
     MOVAE_CHECK_LAUNCH("causal_attn_bwd_dq");
     return MOVAE_OK;
 }
@@ -542,7 +993,8 @@ int movae_attn_fwd(const float* q, const float* k, const float* v, long ld, cons
     if (rc != MOVAE_OK) return rc;
     a.q = q, a.k = k, a.v = v, a.out = out, a.lse_out = lse;
     const bool rope = rope_cos != nullptr;
-    ATTN_LAUNCH_BIDIR(attn_fwd_k, a, rope, (hipStream_t)stream);
+    if (g_movae_compute_bf16) ATTN_LAUNCH_BF(attn_fwd_bf_k, a, false, rope, (hipStream_t)stream);
+    else ATTN_LAUNCH_BIDIR(attn_fwd_k, a, rope, (hipStream_t)stream);
     MOVAE_CHECK_LAUNCH("attn_fwd");
     return MOVAE_OK;
 }
@@ -567,9 +1019,11 @@ int movae_attn_bwd(const float* q, const float* k, const float* v, long ld, cons
     MOVAE_CHECK_LAUNCH("attn_delta");
     a.q = q, a.k = k, a.v = v, a.dout = dout, a.lse = lse, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
     const bool rope = rope_cos != nullptr;
-    ATTN_LAUNCH_BIDIR(attn_bwd_dkdv_k, a, rope, (hipStream_t)stream);
+    if (g_movae_compute_bf16) ATTN_LAUNCH_BF(attn_bwd_dkdv_bf_k, a, false, rope, (hipStream_t)stream);
+    else ATTN_LAUNCH_BIDIR(attn_bwd_dkdv_k, a, rope, (hipStream_t)stream);
     MOVAE_CHECK_LAUNCH("attn_bwd_dkdv");
-    ATTN_LAUNCH_BIDIR(attn_bwd_dq_k, a, rope, (hipStream_t)stream);
+    if (g_movae_compute_bf16) ATTN_LAUNCH_BF(attn_bwd_dq_bf_k, a, false, rope, (hipStream_t)stream);
+    else ATTN_LAUNCH_BIDIR(attn_bwd_dq_k, a, rope, (hipStream_t)stream);
     MOVAE_CHECK_LAUNCH("attn_bwd_dq");
     return MOVAE_OK;
 }

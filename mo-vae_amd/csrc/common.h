@@ -15,6 +15,10 @@
 
 void movae_set_error(const char* fmt, ...);
 
+// movae_set_compute_dtype(): 1 = bf16 MFMA operands (fp32 accumulate) in the 128x128 implicit-GEMM kernels (conv_igemm.hip, which
+// defines it) and in the attention kernels (attention.hip); 0 = fp32, the default and the parity path
+extern int g_movae_compute_bf16;
+
 #define MOVAE_CHECK_ARG(cond, ...)            \
     do {                                      \
         if (!(cond)) {                        \

@@ -1359,7 +1359,7 @@ int launch_fwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     dim3 grid(gx, gy, S);
     int gz;
     const RSide sd = defer_take_3d(st, &grid, &gz);
-    if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_fwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
+    if (BM == 128 && BN == 128 && g_movae_compute_bf16) hipLaunchKernelGGL((igemm2_fwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
     else hipLaunchKernelGGL((igemm2_fwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_fwd");
     return finish_splitk(a, S, rbb, rbb_rpb, ram, want_stats, st);
@@ -1486,7 +1486,7 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     dim3 grid(gx, gy, zsum);
     int gz;
     const RSide sd = defer_take_3d(st, &grid, &gz);
-    if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_bwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
+    if (BM == 128 && BN == 128 && g_movae_compute_bf16) hipLaunchKernelGGL((igemm2_bwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
     else hipLaunchKernelGGL((igemm2_bwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_bwd");
     return finish_splitk(a, Sreal, rbb, rbb_rpb, ram, want_stats, st);
@@ -1552,7 +1552,7 @@ int launch_wgrad2(const float* Sm, const float* Bg, float* const* dW, int G, lon
         dim3 grid(gx, gy, Sp * G);
         int gz;
         const RSide sd = defer_take_3d(st, &grid, &gz);
-        if (BM == 128 && BN == 128 && g_compute_bf16) hipLaunchKernelGGL((igemm2_wgrad<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
+        if (BM == 128 && BN == 128 && g_movae_compute_bf16) hipLaunchKernelGGL((igemm2_wgrad<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
         else hipLaunchKernelGGL((igemm2_wgrad<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
         MOVAE_CHECK_LAUNCH("igemm2_wgrad");
     }

@@ -2099,6 +2099,14 @@ def _ws_at_least(device, nbytes):
     return torch.zeros(nbytes, dtype=torch.uint8, device=device)
 
 
+def _same_compute_dtype(name, fwd_dtype):
+    """The saved lse carries the forward's rounding: a backward under the other compute dtype would recompute other probabilities."""
+    now = L.compute_dtype()
+    if now != fwd_dtype:
+        raise RuntimeError(f"{name}: the forward ran under compute dtype {fwd_dtype} and the backward finds {now}; "
+                           "keep movae_set_compute_dtype unchanged between the two")
+
+
 class CausalAttention(Function):
     """softmax(mask(Q K^T / sqrt(hd))) with dropout, times V, over the [..., proj] NHWC outputs of the three 1x1 projections; the
     result is [..., proj] in the reference's channel order d * heads + h (pixelcnn_prior.py:130).  The backward regenerates the
@@ -2122,6 +2130,7 @@ class CausalAttention(Function):
               proj // heads, p, seed, draw, _st(q))
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.cfg = (B, heads, n, proj // heads, p, seed, draw)
+        ctx.compute_dtype = L.compute_dtype()
         return o
 
     @staticmethod
@@ -2130,6 +2139,7 @@ class CausalAttention(Function):
             return (None,) * 7
         q, k, v, o, lse = ctx.saved_tensors
         B, heads, n, hd, p, seed, draw = ctx.cfg
+        _same_compute_dtype("causal_attention", ctx.compute_dtype)
         do = _c(do)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         ws = _ws_at_least(q.device, L.load().movae_causal_attn_ws_bytes(B, heads, n))
@@ -2190,6 +2200,7 @@ class Attention(Function):
               _st(qkv))
         ctx.save_for_backward(qkv, o, lse, cos, sin)
         ctx.cfg = (B, heads, n, hd)
+        ctx.compute_dtype = L.compute_dtype()
         return o
 
     @staticmethod
@@ -2198,6 +2209,7 @@ class Attention(Function):
             return (None,) * 4
         qkv, o, lse, cos, sin = ctx.saved_tensors
         B, heads, n, hd = ctx.cfg
+        _same_compute_dtype("attention", ctx.compute_dtype)
         c = heads * hd
         do = _c(do)
         dqkv = torch.empty_like(qkv)

@@ -11,7 +11,7 @@ bytes / 8 TB/s (HBM), `frac_of_floor` = floor / measured.
 Prior step: main.py's defaults (K 512, D 64, hidden 128; PixelSNAIL 8 blocks x 2 residual blocks, 8 heads, dropout 0.1; PixelCNN
 15 layers) -- zero_grad, loss, backward, clip_grad_norm_(1.0), FusedAdam -- on 8x8 codes at B=128 and 32x32 codes at B=32.
 
-Usage:  python tools/pixelsnail_bench.py [--steps 20] [--warmup 5] [--prior-step-only]
+Usage:  python tools/pixelsnail_bench.py [--steps 20] [--warmup 5] [--prior-step-only] [--attention-only] [--dtype fp32|bf16]
 """
 import argparse
 import json
@@ -137,18 +137,24 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--prior-step-only", action="store_true", help="only the PixelSNAIL prior steps (for a profiler run)")
+    ap.add_argument("--attention-only", action="store_true", help="only the attention rows")
+    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
+                    help="compute dtype of the fused attention rows and the prior steps (movae_set_compute_dtype); the torch side and "
+                         "the floor (fp32 MFMA peak) stay as they are")
     a = ap.parse_args()
 
     import torch
 
     import movae_amd  # noqa: F401
+    from movae_amd import _lib as L
 
     assert torch.cuda.is_available(), "needs an MI355X"
-    out = {"tool": "pixelsnail_bench", "steps": a.steps, "warmup": a.warmup}
+    L.set_compute_dtype(a.dtype)
+    out = {"tool": "pixelsnail_bench", "steps": a.steps, "warmup": a.warmup, "dtype": a.dtype}
     if not a.prior_step_only:
         out["attention"] = [attention_case(B, h, hd, n, 0.1, a.steps, a.warmup) for B, h, hd, n in ATTN]
     out["prior_step"] = []
-    for B, s in PRIOR:
+    for B, s in ([] if a.attention_only else PRIOR):
         rec = {"B": B, "codes": f"{s}x{s}", "pixelsnail_ms": prior_step_case("pixelsnail", B, s, a.steps, a.warmup)}
         if not a.prior_step_only:
             rec["pixelcnn_ms"] = prior_step_case("pixelcnn", B, s, a.steps, a.warmup)

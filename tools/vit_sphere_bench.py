@@ -8,7 +8,7 @@ on [B * N, embed], bias + GELU on [B * N, 4 * embed] -- each against the same ex
 (median of --repeats windows, alternating the two).  The default 24 x 1024 model of the reference is a 600 M-parameter network and is
 not what this measures.  Prints one JSON line.  bench.py's fixed configurations are not touched.
 
-Usage:  python tools/vit_sphere_bench.py [--steps 20] [--warmup 5] [--repeats 7]
+Usage:  python tools/vit_sphere_bench.py [--steps 20] [--warmup 5] [--repeats 7] [--dtype fp32|bf16]
 """
 import argparse
 import json
@@ -39,24 +39,28 @@ def main():
     ap.add_argument("--mixer_depth", type=int, default=2)
     ap.add_argument("--agg", default="upgrad")
     ap.add_argument("--skip_model", action="store_true")
+    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
+                    help="compute dtype of the model steps and the attention rows (movae_set_compute_dtype); the torch side stays fp32")
     a = ap.parse_args()
 
     import torch
     import torch.nn.functional as F
 
     import movae_amd  # noqa: F401
+    from movae_amd import _lib as L
     from movae_amd import aggregation, ops
     from movae_amd.models import build_sphere_encoder_vit
     from movae_amd.train import GraphedTrainStep, make_optimizer, train_step
 
     dev = torch.device("cuda:0")
+    L.set_compute_dtype(a.dtype)
     B, N = a.batch, 256
     args = Args(latent_dim=N * 8, vit_embed_dim=a.embed, vit_depth=a.depth, vit_num_heads=a.heads, vit_mixer_depth=a.mixer_depth,
                 aggregator=a.agg, agg_norm_eps=1e-4, agg_reg_eps=1e-4, mgda_epsilon=1e-5, mgda_max_iters=250, pref_weights=None,
                 optimizer="adam", lr=1e-4, wd=0, momentum=0.9, max_grad_norm=None)
     x = (torch.rand(B, 3, 32, 32, generator=torch.Generator().manual_seed(0)) * 2 - 1).to(dev)
-    res = {"arch": "sphere_encoder_vit", "batch": B, "agg": a.agg,
-           "shape": f"CIFAR (32x32, patch 2, N {N}, embed {a.embed}, depth {a.depth}, heads {a.heads}, mixer depth {a.mixer_depth}, fp32)"}
+    res = {"arch": "sphere_encoder_vit", "batch": B, "agg": a.agg, "dtype": a.dtype,
+           "shape": f"CIFAR (32x32, patch 2, N {N}, embed {a.embed}, depth {a.depth}, heads {a.heads}, mixer depth {a.mixer_depth}, {a.dtype})"}
 
     def fresh():
         torch.manual_seed(0)
