@@ -650,6 +650,25 @@ int movae_recon_metrics(const float* real, long long rs_n, long long rs_c, long 
                         int n, int c, int h, int w, int window_size, float max_val, float* out, void* ws, size_t ws_bytes,
                         movae_stream_t stream);
 
+/* ---- the perceptual (VGG16 feature) loss around its convolutions (csrc/perceptual.hip; utils/objectives.py:53-79 PerceptualLoss) ----
+ * PerceptualLoss._norm_input (:66-72) on g (1..8) same-shape fp32 NHWC tensors of n elements each with C = 3 (channel = index % 3):
+ * per tensor, x -> (x + 1) / 2 if ANY of its elements is negative, then clamp to [0, 1], then (x - mean_c) / std_c with the ImageNet
+ * mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225).  The decision stays on the device: two launches for the whole group (block
+ * partials in ws, folded by the normalise launch), no atomics.  x, y, dy, dx are HOST arrays of g device pointers; flags is a device
+ * int[g], written by the forward (1 = rescaled) and read by the backward.  ws >= movae_vgg_prep_ws_bytes(g).
+ * Backward: dx = dy * (flag ? 0.5 : 1) / std_c where 0 <= x' <= 1 (x' the value before the clamp, recomputed from x; the interval is
+ * inclusive, like torch.clamp's backward), else 0.  A null dy[i] skips member i (its dx[i] is not written); one launch. */
+size_t movae_vgg_prep_ws_bytes(int g);
+int movae_vgg_prep_fwd(int g, const float* const* x, float* const* y, int* flags, size_t n, void* ws, size_t ws_bytes,
+                       movae_stream_t stream);
+int movae_vgg_prep_bwd(int g, const float* const* dy, const float* const* x, const int* flags, float* const* dx, size_t n,
+                       movae_stream_t stream);
+/* 2x2 / stride-2 / floor-mode max-pool, NHWC fp32, c % 4 == 0, 16-byte aligned tensors: x [n][h][w][c] -> y [n][h/2][w/2][c]; an odd h
+ * or w drops the last row / column.  The backward writes EVERY element of dx (zeros in a dropped row / column; no memset, no
+ * atomics): dy goes to the first element of the window in the order (0,0), (0,1), (1,0), (1,1) that equals y, the others get 0. */
+int movae_maxpool2x2_fwd(const float* x, float* y, int n, int h, int w, int c, movae_stream_t stream);
+int movae_maxpool2x2_bwd(const float* dy, const float* x, const float* y, float* dx, int n, int h, int w, int c, movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,11 @@ SIGNATURES = {
     "movae_unpatchify_act_fwd": ([_p, _p, _i, _i, _i, _i, _i, _p], _i),
     "movae_unpatchify_act_bwd": ([_p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "movae_add_rows_bcast": ([_p, _p, _p, _l, _i, _i, _p], _i),
+    "movae_vgg_prep_ws_bytes": ([_i], _z),
+    "movae_vgg_prep_fwd": ([_i, _p, _p, _p, _z, _p, _z, _p], _i),
+    "movae_vgg_prep_bwd": ([_i, _p, _p, _p, _p, _z, _p], _i),
+    "movae_maxpool2x2_fwd": ([_p, _p, _i, _i, _i, _i, _p], _i),
+    "movae_maxpool2x2_bwd": ([_p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "movae_recon_metrics_ws_bytes": ([_i, _i, _i, _i], _z),
     "movae_recon_metrics": ([_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, C.c_longlong, C.c_longlong,
                              C.c_longlong, _i, _i, _i, _i, _i, _f, _p, _p, _z, _p], _i),
@@ -253,7 +258,8 @@ DEFER_PASS = frozenset(
      "movae_nchw_to_nhwc", "movae_nhwc_to_nchw", "movae_reparam_bwd", "movae_kl_bwd", "movae_recon_loss_bwd", "movae_recon_loss_bwd_act", "movae_recursive_losses_bwd",
      "movae_tc_decomp_bwd", "movae_sphere_latents_bwd", "movae_sphere_losses_bwd",
      "movae_combine_losses_bwd", "movae_vq_bwd", "movae_linear_pair_bwd", "movae_edge_weighted_mse_bwd", "movae_edge_match_bwd",
-     "movae_gated_residual_bwd", "movae_attn_bwd", "movae_rownorm_bwd", "movae_bias_gelu_bwd", "movae_unpatchify_act_bwd"])
+     "movae_gated_residual_bwd", "movae_attn_bwd", "movae_rownorm_bwd", "movae_bias_gelu_bwd", "movae_unpatchify_act_bwd",
+     "movae_vgg_prep_bwd", "movae_maxpool2x2_bwd"])
 _defer_arena = [0]
 
 

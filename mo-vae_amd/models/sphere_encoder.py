@@ -1,6 +1,8 @@
 """The conv Sphere Encoder on the HIP kernels -- drop-in for the reference's models/sphere_encoder.py, class SphereEncoder (same
-constructor signature and defaults, state_dict keys and order, init RNG order, forward / loss_function dictionaries), without its
-optional perceptual term: that one needs pretrained VGG16 weights, so `use_perceptual=True` raises.
+constructor signature and defaults, state_dict keys and order, init RNG order, forward / loss_function dictionaries).  Its perceptual
+term (`use_perceptual=True`, the reference's default) is perceptual.PerceptualLoss on VGG16 weights the caller has registered
+(perceptual.use_vgg16_weights, or $MOVAE_VGG16_WEIGHTS): this build fetches none, so with nothing registered
+`use_perceptual=True` raises.
 
 The latent is RMS-normalised onto the sphere of radius sqrt(L); there is no KL term.  One step makes two encoder and two decoder
 passes: v = spherify(E(x)); a jitter angle per image gives sigma = tan(angle) and sigma_sub = s * sigma; recons = D(spherify(v +
@@ -10,10 +12,13 @@ models/recursive_vaes.py, whose plumbing this reuses: every encoder / decoder ca
 the running statistics per module per step, as in the reference), the decoder's output-activation link stays unused (recons and
 x_recon_NOISY have two readers each), and train pulls the Jacobian rows back from the loss op (autojac.backward_through).
 
-Everything between encoder_proj and the decoder calls is one launch (ops.SphereLatents), the loss_function two (ops.SphereLosses).
+Everything between encoder_proj and the decoder calls is one launch (ops.SphereLatents), the loss_function two (ops.SphereLosses); with
+the perceptual term the three images are normalised in two launches, each goes through the VGG stack once (the features of `recons`
+serve as the prediction of pix_recon and, detached, as the target of pix_con), and one ops.CombineLosses launch forms the four values.
 The noise: eager mode draws with torch in the reference's order (rand, [rand, rand], rand, randn); `noise_override` = {"u": [B, 4],
 "e": [B, L]} replaces the draws (parity tests; u's columns are the angle, mix-mask, mix-angle and s uniforms); after
 prepare_for_graph the draws are made inside the SphereLatents launch.  Eval mode draws noise too, like the reference."""
+import contextlib
 import math
 from math import sqrt
 
@@ -21,6 +26,7 @@ import torch
 
 from .. import nn as mnn
 from .. import ops
+from .. import perceptual
 from ._base import nchw_view
 from .vae import VAE
 
@@ -30,14 +36,26 @@ class SphereCommon:
     its draws, spherify, forward, loss_function and sample.  The class supplies encode_to_vector(x) -> [B, L] and
     decode_from_sphere(v) -> a logical NCHW view of an NHWC buffer."""
     graph_safe = True
-    #: internal: every loss is an output of ops.SphereLosses, so train can pull the K Jacobian rows back from its inputs
+    #: internal: every loss is an output of ops.SphereLosses, so train can pull the K Jacobian rows back from its inputs.  With the
+    #: perceptual term the losses come out of ops.CombineLosses, which has no `input_cotangents`: autojac.backward_through then takes
+    #: one autograd pass per loss, its fallback
     _jacobian_from_loss_op = True
     #: {"u": [B, 4], "e": [B, L]} to replace the draws of forward (parity tests)
     noise_override = None
 
+    @staticmethod
+    def _vgg16_weights_or_refuse(name, use_perceptual):
+        """The registered VGG16 weights for use_perceptual=True (None otherwise); nothing registered: the refusal."""
+        weights = perceptual.registered_vgg16_weights() if use_perceptual else None
+        if use_perceptual and weights is None:
+            raise NotImplementedError(f"{name}(use_perceptual=True) needs the pretrained VGG16 weights of the reference's "
+                                      "PerceptualLoss, which this build does not carry (DESIGN.md section 7); register yours with "
+                                      f"movae_amd.perceptual.use_vgg16_weights(path) or ${perceptual.ENV_VAR}, or pass use_perceptual=False")
+        return weights
+
     def _init_sphere(self, L, sigma_max_angle_deg, sigma_mix_prob, sigma_mix_angle_min_deg, sigma_mix_angle_max_deg, lambda_pix_recon,
                      lambda_pix_con, lambda_lat_con, pix_recon_smooth_l1_weight, pix_recon_perceptual_weight, pix_con_smooth_l1_weight,
-                     pix_con_perceptual_weight):
+                     pix_con_perceptual_weight, vgg16_weights=None):
         self.L = L
         self.radius = sqrt(L)
         self.sigma_max_angle_deg = float(sigma_max_angle_deg)
@@ -48,7 +66,9 @@ class SphereCommon:
         self.lambda_pix_recon, self.lambda_pix_con, self.lambda_lat_con = lambda_pix_recon, lambda_pix_con, lambda_lat_con
         self.pix_recon_smooth_l1_weight, self.pix_recon_perceptual_weight = pix_recon_smooth_l1_weight, pix_recon_perceptual_weight
         self.pix_con_smooth_l1_weight, self.pix_con_perceptual_weight = pix_con_smooth_l1_weight, pix_con_perceptual_weight
-        self.use_perceptual, self.perceptual_loss = False, None
+        # models/sphere_encoder.py:126-130: the last submodule registered, so its keys close the state_dict
+        self.use_perceptual = vgg16_weights is not None
+        self.perceptual_loss = perceptual.PerceptualLoss(vgg16_weights) if self.use_perceptual else None
         # objectives for MTL / logging (models/sphere_encoder.py:133-137: placeholders; loss_function computes the terms)
         zero = lambda *_: torch.tensor(0.0, device=next(self.parameters()).device)  # noqa: E731
         self.objectives = {"pix_recon": zero, "pix_con": zero, "lat_con": zero}
@@ -99,11 +119,32 @@ class SphereCommon:
                 "x_recon_noisy_small_sg": recons.detach(), "v_enc_dec": v_enc_dec, "sigma": sigma, "sigma_sub": sigma_sub}
 
     def loss_function(self, inputs, args: dict) -> dict:
-        sg = args["x_recon_noisy_small_sg"]
-        vals = ops.sphere_losses(ops.to_nhwc(args["recons"]), ops.to_nhwc(inputs), ops.to_nhwc(args["x_recon_NOISY"]), args["v"],
-                                 args["v_enc_dec"], (self.lambda_pix_recon, self.lambda_pix_con, self.lambda_lat_con),
-                                 (self.pix_recon_smooth_l1_weight, self.pix_con_smooth_l1_weight), sg=ops.to_nhwc(sg.detach()))
-        return dict(zip(("pix_recon", "pix_con", "lat_con", "total_loss"), vals))
+        sg = ops.to_nhwc(args["x_recon_noisy_small_sg"].detach())
+        r, x, xn = ops.to_nhwc(args["recons"]), ops.to_nhwc(inputs), ops.to_nhwc(args["x_recon_NOISY"])
+        lam = (self.lambda_pix_recon, self.lambda_pix_con, self.lambda_lat_con)
+        w_sl1 = (self.pix_recon_smooth_l1_weight, self.pix_con_smooth_l1_weight)
+        names = ("pix_recon", "pix_con", "lat_con", "total_loss")
+        w_rec, w_con = self.pix_recon_perceptual_weight, self.pix_con_perceptual_weight
+        pl = self.perceptual_loss if self.use_perceptual else None
+        if pl is None or (w_rec <= 0 and w_con <= 0):  # (_pixel_loss, models/sphere_encoder.py:243-247: the term needs a positive weight)
+            return dict(zip(names, ops.sphere_losses(r, x, xn, args["v"], args["v_enc_dec"], lam, w_sl1, sg=sg)))
+        # pix = lambda * (w_sl1 * smooth_l1 + w_perc * perceptual): the unweighted sums' terms, then one launch for the four values
+        sl1_rec, sl1_con, lat, _ = ops.sphere_losses(r, x, xn, args["v"], args["v_enc_dec"], (1.0, 1.0, 1.0), w_sl1, sg=sg)
+        images = [r] + ([x] if w_rec > 0 else []) + ([xn] if w_con > 0 else [])
+        normed = list(ops.vgg_prep(*images))
+        # the features of recons: the prediction of pix_recon and, detached, the target of pix_con (the reference computes them twice)
+        with contextlib.nullcontext() if w_rec > 0 else torch.no_grad():
+            f_r = pl.features(normed.pop(0))
+        terms, rows = [sl1_rec, sl1_con, lat], [[lam[0], 0.0, 0.0], [0.0, lam[1], 0.0], [0.0, 0.0, lam[2]]]
+        if w_rec > 0:
+            with torch.no_grad():
+                f_x = pl.features(normed.pop(0))
+            terms.append(pl.feature_mse(f_r, f_x, w_rec))
+            rows = [row + [lam[0] if k == 0 else 0.0] for k, row in enumerate(rows)]
+        if w_con > 0:
+            terms.append(pl.feature_mse(pl.features(normed.pop(0)), f_r, w_con))
+            rows = [row + [lam[1] if k == 1 else 0.0] for k, row in enumerate(rows)]
+        return dict(zip(names, ops.combine_losses(terms, rows)))
 
     def sample(self, num_samples=1, device=None, steps=1, share_noise=True):
         """One-step generation x = D(spherify(e)), e ~ N(0, I); steps > 1 iterates encode / decode at the fixed noise strength
@@ -126,9 +167,7 @@ class SphereEncoder(SphereCommon, VAE):
                  sigma_mix_angle_min_deg=None, sigma_mix_angle_max_deg=None, lambda_pix_recon: float = 1.0, lambda_pix_con: float = 0.5,
                  lambda_lat_con: float = 0.1, pix_recon_smooth_l1_weight: float = 1.0, pix_recon_perceptual_weight: float = 1.0,
                  pix_con_smooth_l1_weight: float = 0.5, pix_con_perceptual_weight: float = 0.5, use_perceptual: bool = True, **kwargs):
-        if use_perceptual:
-            raise NotImplementedError("SphereEncoder(use_perceptual=True) needs the pretrained VGG16 weights of the reference's "
-                                      "PerceptualLoss, which this build does not carry (DESIGN.md section 7); pass use_perceptual=False")
+        vgg16_weights = self._vgg16_weights_or_refuse("SphereEncoder", use_perceptual)
         super().__init__(latent_dim=latent_dim, **kwargs)
         # models/sphere_encoder.py:102-107: the VAE's heads go, decoder_input is replaced in place, encoder_proj is registered last;
         # the RNG draws follow the VAE's: encoder_proj, then the new decoder_input
@@ -140,7 +179,7 @@ class SphereEncoder(SphereCommon, VAE):
 
         self._init_sphere(latent_dim, sigma_max_angle_deg, sigma_mix_prob, sigma_mix_angle_min_deg, sigma_mix_angle_max_deg, lambda_pix_recon,
                           lambda_pix_con, lambda_lat_con, pix_recon_smooth_l1_weight, pix_recon_perceptual_weight, pix_con_smooth_l1_weight,
-                          pix_con_perceptual_weight)
+                          pix_con_perceptual_weight, vgg16_weights)
 
     def encode_to_vector(self, x):
         """Encode to the flat vector (before spherify)."""

@@ -2,8 +2,8 @@
 paper architecture: ViT + MLP-Mixer + RoPE + sinusoidal positions): same constructor signature and defaults, state_dict keys, shapes
 and order (the `pe` buffers of both positional embeddings and every block's `rotary.inv_freq` included), init RNG order, forward /
 loss_function dictionaries, encode_to_vector / spherify / decode_from_sphere / sample.  Like the conv class (models/sphere_encoder.py,
-whose sphere plumbing -- SphereCommon -- this shares) it carries no perceptual term: `use_perceptual=True` raises; a non-zero
-`dropout` raises as well (the attention kernels have no dropout instances in their bidirectional form).
+whose sphere plumbing -- SphereCommon -- this shares) its perceptual term runs on VGG16 weights the caller registered
+(perceptual.use_vgg16_weights) and `use_perceptual=True` raises with none registered; a non-zero `dropout` raises as well (the attention kernels have no dropout instances in their bidirectional form).
 
 Data path, all [B, N, D] token tensors, every step a launch of libmovae_hip.so and no [N, N] matrix anywhere:
   patch embedding   a k = stride = patch convolution on the NHWC image, whose output [B, h, w, D] IS [B, N, D]; + pos (add_rows_bcast)
@@ -156,9 +156,7 @@ class SphereEncoderViT(SphereCommon, HotPathModel):
                  lambda_pix_con: float = 0.5, lambda_lat_con: float = 0.1, pix_recon_smooth_l1_weight: float = 1.0,
                  pix_recon_perceptual_weight: float = 1.0, pix_con_smooth_l1_weight: float = 0.5, pix_con_perceptual_weight: float = 0.5,
                  use_perceptual: bool = True, dropout: float = 0.0, device=None):
-        if use_perceptual:
-            raise NotImplementedError("SphereEncoderViT(use_perceptual=True) needs the pretrained VGG16 weights of the reference's "
-                                      "PerceptualLoss, which this build does not carry (DESIGN.md section 7); pass use_perceptual=False")
+        vgg16_weights = self._vgg16_weights_or_refuse("SphereEncoderViT", use_perceptual)
         if dropout != 0:
             raise NotImplementedError(f"SphereEncoderViT(dropout={dropout}): dropout in the attention and MLP paths is not built (the "
                                       "reference's factory never sets it; DESIGN.md section 7); pass dropout=0.0")
@@ -186,7 +184,7 @@ class SphereEncoderViT(SphereCommon, HotPathModel):
         self.head_dec = mnn.TokenLinear(embed_dim, patch_size * patch_size * in_channels)
         self._init_sphere(self.num_patches * latent_channels, sigma_max_angle_deg, sigma_mix_prob, sigma_mix_angle_min_deg,
                           sigma_mix_angle_max_deg, lambda_pix_recon, lambda_pix_con, lambda_lat_con, pix_recon_smooth_l1_weight,
-                          pix_recon_perceptual_weight, pix_con_smooth_l1_weight, pix_con_perceptual_weight)
+                          pix_recon_perceptual_weight, pix_con_smooth_l1_weight, pix_con_perceptual_weight, vgg16_weights)
 
     def _rope(self, n, device, enc=True):
         """The tables of the first block's rotary module, which the reference hands to every block (:338-340)."""

@@ -1,6 +1,6 @@
 """Host-side mirror of the reference's utils/objectives.py (same function names, argument order
 `fn(inputs, recons)`, error behaviour) on the HIP loss kernels (csrc/losses.hip)."""
-from . import ops
+from . import ops, perceptual
 
 _VALID = {"mse", "bce", "l1", "smooth_l1", "perceptual"}
 
@@ -72,5 +72,22 @@ def get_recon_obj_and_activation(recons_objective, recons_activation="tanh", mod
         return laplacian_per_pixel_mean, recons_activation or "tanh"
     if recons_objective == "smooth_l1":
         return smooth_l1_per_pixel_mean, recons_activation or "tanh"
-    raise NotImplementedError(
-        "recons_objective='perceptual' needs pretrained VGG16 weights (network fetch) and is outside the hot path")
+    if model is None:
+        raise ValueError("model required for recons_objective='perceptual' to register PerceptualLoss")
+    weights = perceptual.registered_vgg16_weights()
+    if weights is None:
+        raise NotImplementedError(
+            "recons_objective='perceptual' needs pretrained VGG16 weights, which this build does not fetch: register yours with "
+            f"movae_amd.perceptual.use_vgg16_weights(path) or ${perceptual.ENV_VAR}")
+    pl = perceptual.PerceptualLoss(weights, device=getattr(model, "device", None))
+    model.perceptual_loss = pl  # (utils/objectives.py:40: a submodule, so it moves with the model)
+    return make_perceptual_recon_fn(pl), recons_activation or "tanh"
+
+
+def make_perceptual_recon_fn(perceptual_loss_module):
+    """utils/objectives.py:46-50 -> fn(inputs, recons, scale=1.0) = scale * perceptual_loss(recons, inputs)."""
+    def fn(inputs, recons, scale=1.0):
+        return perceptual_loss_module(recons, inputs, scale)
+
+    fn.kind = "perceptual"
+    return fn

@@ -2398,3 +2398,88 @@ def token_linear(x, w, b=None):
     rows = x.numel() // fin
     y = Conv.apply(x.reshape(rows, 1, 1, fin), w.view(w.shape[0], fin, 1, 1), b, 1, 0, 0, False, None, 0.01)
     return y.reshape(*x.shape[:-1], w.shape[0])
+
+
+# ---- the perceptual loss around its convolutions (csrc/perceptual.hip) ---------------------------------------------------------------
+class VggPrep(Function):
+    """PerceptualLoss._norm_input (utils/objectives.py:66-72) on G same-shape NHWC images [B, H, W, 3] in two launches for the whole
+    group and without a host sync: per tensor, (x + 1) / 2 if any of its elements is negative, clamp to [0, 1], ImageNet mean / std.
+    Returns G tensors.  The backward recomputes the clamp mask from the saved x and the saved per-tensor flags (a device int[G]) and
+    serves whichever cotangents arrive, in one launch."""
+
+    @staticmethod
+    def forward(ctx, *xs):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(xs[0])
+        xs = [_c(x) for x in xs]
+        G, first = len(xs), xs[0]
+        assert all(x.dtype == torch.float32 and x.shape == first.shape for x in xs) and first.shape[-1] == 3, \
+            f"vgg_prep: same-shape fp32 NHWC tensors with 3 channels, got {[tuple(x.shape) for x in xs]}"
+        ys = [torch.empty_like(x) for x in xs]
+        flags = torch.empty(G, dtype=torch.int32, device=first.device)
+        wsp, wsb = _ws(first)
+        arr = C.c_void_p * G
+        _call("movae_vgg_prep_fwd", G, arr(*[x.data_ptr() for x in xs]), arr(*[y.data_ptr() for y in ys]), flags.data_ptr(),
+              first.numel(), wsp, wsb, _st(first))
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(flags, *[x if need else None for x, need in zip(xs, ctx.needs_input_grad)])
+            # a member that needs no gradient (the input image next to two reconstructions) stays a constant of the tape
+            ctx.mark_non_differentiable(*[y for y, need in zip(ys, ctx.needs_input_grad) if not need])
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        live = [dy is not None and need for dy, need in zip(dys, ctx.needs_input_grad)]
+        if not any(live):
+            return (None,) * len(dys)
+        flags, *xs = ctx.saved_tensors
+        G = len(dys)
+        dys = [_c(dy) if ok else None for dy, ok in zip(dys, live)]
+        dxs = [torch.empty_like(x) if ok else None for x, ok in zip(xs, live)]
+        arr = C.c_void_p * G
+        _call("movae_vgg_prep_bwd", G, arr(*[_p(t) for t in dys]), arr(*[_p(x) if ok else 0 for x, ok in zip(xs, live)]), flags.data_ptr(),
+              arr(*[_p(t) for t in dxs]), next(x for x in xs if x is not None).numel(), _st(flags))
+        return tuple(dxs)
+
+    backward_batched = _no_walker("VggPrep")
+
+
+def vgg_prep(*xs):
+    """One NHWC image tensor -> its normalised tensor; several -> a tuple, normalised in the same two launches."""
+    out = VggPrep.apply(*xs)
+    return out[0] if len(xs) == 1 else out
+
+
+class MaxPool2x2(Function):
+    """nn.MaxPool2d(kernel_size=2, stride=2) (floor mode) on NHWC [N, H, W, C], C % 4 == 0.  The backward writes every element of dx
+    in one launch: dy to the first maximum of each window in scan order (torch's tie rule), zeros elsewhere and in the row / column
+    an odd size drops."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.set_materialize_grads(False)
+        L.require_gpu(x)
+        x = _c(x)
+        n, h, w, c = x.shape
+        assert x.dtype == torch.float32 and c % 4 == 0 and h >= 2 and w >= 2, f"max_pool2x2: fp32 NHWC with C % 4 == 0, got {tuple(x.shape)}"
+        y = torch.empty((n, h // 2, w // 2, c), dtype=x.dtype, device=x.device)
+        _call("movae_maxpool2x2_fwd", x.data_ptr(), y.data_ptr(), n, h, w, c, _st(x))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None or not ctx.needs_input_grad[0]:
+            return None
+        x, y = ctx.saved_tensors
+        dy = _c(dy)
+        dx = torch.empty_like(x)
+        _call("movae_maxpool2x2_bwd", dy.data_ptr(), x.data_ptr(), y.data_ptr(), dx.data_ptr(), *x.shape, _st(x))
+        return dx
+
+    backward_batched = _no_walker("MaxPool2x2")
+
+
+def max_pool2x2(x):
+    return MaxPool2x2.apply(x)
