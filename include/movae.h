@@ -426,6 +426,10 @@ int movae_bench_kgemm_bn_fin(int mode);
  * the size heuristic says; mode < 0: none does; 0: the heuristic (small, latency-bound problems only).  Lets the parity tests run
  * the whole conv test matrix through either family.  Returns the previous mode. */
 int movae_bench_force_kgemm(int mode);
+/* n > 0 pins the fewest 128x128 work items from which the conv dispatcher prefers its big tiles (igemm2_*<128,128>,
+ * igemm2_wgrad<64,128>), whatever MOVAE_BIG_TILE_MIN says: n = 1 lets a test reach them at shapes of a few tiles.  0 restores
+ * the environment's value or the default (256).  Returns the previous pin (0: none).  Never set by the product path. */
+int movae_bench_big_tile_min(int n);
 
 /* ---- BatchNorm fused into its neighbouring convolutions -----------------------------------------
  * models/vae.py:119-126,149-158: Conv2d / ConvTranspose2d -> BatchNorm2d (training statistics) -> LeakyReLU chains.  Instead of

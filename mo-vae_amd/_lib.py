@@ -171,6 +171,7 @@ SIGNATURES = {
     "movae_bench_force_split": ([_i], _i),
     "movae_bench_kgemm_bn_fin": ([_i], _i),
     "movae_bench_force_kgemm": ([_i], _i),
+    "movae_bench_big_tile_min": ([_i], _i),
     "movae_set_compute_dtype": ([_i], _i),
 }
 

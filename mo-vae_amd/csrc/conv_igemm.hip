@@ -901,6 +901,7 @@ const char* g_last_kernel = "";  // movae_bench_last_kernel(): main kernel chose
 int g_force_split = 0;           // movae_bench_force_split(): > 0 pins the split-K factor (tuning sweeps)
 bool g_bench_main_only = false;  // movae_bench_main_kernel_only(): time the MFMA kernel without its epilogue launches
 int g_force_kgemm = 0;           // movae_bench_force_kgemm(): 1 = every shape kgemm.h can serve takes it, -1 = none does (tests, A/B)
+int g_big_tile_min = 0;          // movae_bench_big_tile_min(): > 0 pins big_tile_min() (tests), 0 = MOVAE_BIG_TILE_MIN / the default
 
 inline long reduce_vec_min() {  // outputs from which the 16-byte reduce serves 8 <= S < 64 (tuning knob)
     static const long v = env_long("MOVAE_REDUCE_VEC_MIN", 1L << 19);
@@ -1135,7 +1136,7 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 inline long big_tile_min() {  // minimum number of 128x128 work items before the big tile is preferred
     static const long v = env_long("MOVAE_BIG_TILE_MIN", 256);
-    return v;
+    return g_big_tile_min > 0 ? g_big_tile_min : v;
 }
 
 template <int BM, int BN>
@@ -1542,6 +1543,12 @@ int movae_set_compute_dtype(int dtype) {
 int movae_bench_force_kgemm(int mode) {
     const int prev = g_force_kgemm;
     g_force_kgemm = mode > 0 ? 1 : (mode < 0 ? -1 : 0);
+    return prev;
+}
+
+int movae_bench_big_tile_min(int n) {
+    const int prev = g_big_tile_min;
+    g_big_tile_min = n > 0 ? n : 0;
     return prev;
 }
 

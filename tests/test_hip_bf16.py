@@ -33,7 +33,7 @@ def _rel(got, want):
     return float((got - want).norm() / want.norm().clamp_min(1e-30))
 
 
-def _conv_pair(gpu_device, transposed=False):
+def _conv_pair(gpu_device):
     from movae_amd import ops
 
     g = torch.Generator().manual_seed(3)

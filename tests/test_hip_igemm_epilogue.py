@@ -4,7 +4,11 @@ the bias or bn_y is not 16-byte aligned, next to the through-LDS epilogue with o
 get.  Both must store the same bits, and their BatchNorm side products must be the column sums of what was stored.
 
 Bounds: a partial is a float32 sum of at most R = BM terms (BM: rows of the tile), so it is off by at most R * 2^-24 * sum|term|
-(the squares and the d * y products enter their sums through fmaf, i.e. unrounded); the partials are folded in float64 here."""
+(the squares and the d * y products enter their sums through fmaf, i.e. unrounded); the partials are folded in float64 here.
+
+The 128x128 tile (and its bf16-operand instantiation) is reached through movae_bench_big_tile_min(1) by the cases with 160
+channels; the side products are sums of what was stored, so the same bounds hold in either compute dtype."""
+import contextlib
 import ctypes as C
 
 import pytest
@@ -38,6 +42,20 @@ def tiled(L):
         lib.movae_bench_force_kgemm(kgemm)
 
 
+@contextlib.contextmanager
+def compute(L, dtype, channels):
+    """The compute dtype; for 128 or more columns also the 128x128 tile from one work item on.  The cases below that keep the
+    dispatcher's own threshold."""
+    prev = L.set_compute_dtype(dtype)
+    big = L.load().movae_bench_big_tile_min(1) if channels >= 128 else None
+    try:
+        yield
+    finally:
+        if big is not None:
+            L.load().movae_bench_big_tile_min(big)
+        L.set_compute_dtype(prev)
+
+
 def rnd(gen, *shape):
     return torch.randn(*shape, generator=gen).cuda()
 
@@ -51,8 +69,22 @@ def off4(t):
     return v
 
 
-def tile_of(channels):  # the dispatcher's choice for these small shapes: (BM, BN, WM)
+def tile_of(channels):  # the dispatcher's choice for these small shapes under `tiled` and `compute`: (BM, BN, WM)
+    if channels >= 128:
+        return (128, 128, 2)
     return (128, 32, 4) if channels <= 32 else (64, 64, 2)
+
+
+def kernel_of(form, channels, dtype="f32"):
+    BM, BN, _ = tile_of(channels)
+    return f"igemm2_{form}<{BM},{BN}{',true' if dtype == 'bf16' and BM == BN == 128 else ''}>"
+
+
+BIG_BOTH = [pytest.param((160, "f32"), id="160"), pytest.param((160, "bf16"), id="160-bf16")]  # the 128x128 tile, both compute dtypes
+
+
+def channels_dtype(p):  # a channel count alone: fp32 (the small tiles have no bf16 form)
+    return p if isinstance(p, tuple) else (p, "f32")
 
 
 def last_kernel(lib):
@@ -69,11 +101,21 @@ STATS_CASES = [  # (transposed, n, hi, wi, ci, ho, wo, co)
     (False, 5, 8, 8, 16, 4, 4, 64),  # FWD form <64,64>: two row blocks, the second ragged
     (True, 5, 4, 4, 32, 8, 8, 16),   # BWD form <128,32>: four parity classes of 80 rows (output_padding 1)
     (True, 5, 4, 4, 32, 8, 8, 64),   # BWD form <64,64>: two row blocks per class
+    (False, 5, 12, 12, 16, 6, 6, 160),  # FWD form <128,128>: M = 180, N = 160, both ragged
+    (True, 5, 6, 6, 32, 12, 12, 160),   # BWD form <128,128>: four parity classes of 180 rows
+    (False, 5, 12, 12, 16, 6, 6, 160, "bf16"),  # the same two with bf16 operands: <128,128,true>
+    (True, 5, 6, 6, 32, 12, 12, 160, "bf16"),
 ]
 
 
 @pytest.mark.parametrize("case", STATS_CASES)
 def test_statistics_are_the_column_sums_of_what_was_stored(L, tiled, case):
+    dtype = case[8] if len(case) > 8 else "f32"
+    with compute(L, dtype, case[7]):
+        _statistics(L, tiled, case[:8], dtype)
+
+
+def _statistics(L, tiled, case, dtype):
     tr, n, hi, wi, ci, ho, wo, co = case
     gen = torch.Generator().manual_seed(11)
     x, bias = rnd(gen, n, hi, wi, ci), rnd(gen, co)
@@ -90,7 +132,7 @@ def test_statistics_are_the_column_sums_of_what_was_stored(L, tiled, case):
         L.call(name, x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), n, hi, wi, ci, ho, wo, co, K, K, STRIDE, PAD, 0, 0.0,
                ws.data_ptr(), ws.numel(), st, C.byref(f))
         torch.cuda.synchronize()
-        assert last_kernel(tiled) == f"igemm2_{'bwd' if tr else 'fwd'}<{BM},{BN}>"
+        assert last_kernel(tiled) == kernel_of("bwd" if tr else "fwd", co, dtype)
         assert f.stats_parts > 0
         return y, stats[:f.stats_parts * 2 * co].view(f.stats_parts, 2, co).double().sum(0).cpu(), f.stats_parts
 
@@ -105,8 +147,9 @@ def test_statistics_are_the_column_sums_of_what_was_stored(L, tiled, case):
 
 
 def dgrad_operands(tr, groups, ci, seed):
-    """An input-gradient problem whose dx is [groups * 8][8][8][ci]: whole row blocks per group and parity class."""
-    n, hi, wi, co = 8, 8, 8, 16
+    """An input-gradient problem whose dx is [groups * n][8][8][ci]: whole row blocks per group and parity class (n = 8; 16 for
+    the 128-row tile: two row blocks per group and class)."""
+    n, hi, wi, co = (16 if ci >= 128 else 8), 8, 8, 16
     ho, wo = (16, 16) if tr else (4, 4)
     gen = torch.Generator().manual_seed(seed)
     dy = rnd(gen, groups * n, ho, wo, co)
@@ -115,9 +158,15 @@ def dgrad_operands(tr, groups, ci, seed):
 
 
 @pytest.mark.parametrize("groups", [1, 2])
-@pytest.mark.parametrize("ci", [32, 64])
+@pytest.mark.parametrize("ci", [32, 64] + BIG_BOTH)
 @pytest.mark.parametrize("tr", [True, False], ids=["fwd_form", "bwd_form"])
 def test_batchnorm_backward_sums_match_the_stored_gradient(L, tiled, tr, ci, groups):
+    ci, dtype = channels_dtype(ci)
+    with compute(L, dtype, ci):
+        _batchnorm_backward_sums(L, tiled, tr, ci, dtype, groups)
+
+
+def _batchnorm_backward_sums(L, tiled, tr, ci, dtype, groups):
     dy, w, geom, gen = dgrad_operands(tr, groups, ci, 23)
     n, hi, wi = geom[0] // groups, geom[1], geom[2]
     slope = 0.01
@@ -139,7 +188,7 @@ def test_batchnorm_backward_sums_match_the_stored_gradient(L, tiled, tr, ci, gro
         L.call("movae_convT2d_dgrad_f" if tr else "movae_conv2d_dgrad_f", dy.data_ptr(), w.data_ptr(), dx.data_ptr(), *geom,
                ws.data_ptr(), ws.numel(), st, C.byref(f), groups)
         torch.cuda.synchronize()
-        assert last_kernel(tiled) == f"igemm2_{'fwd' if tr else 'bwd'}<{BM},{BN}>"
+        assert last_kernel(tiled) == kernel_of("fwd" if tr else "bwd", ci, dtype)
         assert f.bn_ppg > 0
         return dx, part[:groups * f.bn_ppg * 2 * ci].view(groups, f.bn_ppg, 2, ci).double().sum(1).cpu(), f.bn_ppg
 
@@ -157,13 +206,25 @@ def test_batchnorm_backward_sums_match_the_stored_gradient(L, tiled, tr, ci, gro
 
 @pytest.mark.parametrize("tr", [True, False], ids=["fwd_form", "bwd_form"])
 def test_activation_derivative_and_residual_in_the_epilogue(L, tiled, tr):
-    groups, ci, slope = 2, 32, 0.2
+    _activation_derivative_and_residual(L, tiled, tr, 32, "f32")
+
+
+@pytest.mark.parametrize("ci", BIG_BOTH)
+@pytest.mark.parametrize("tr", [True, False], ids=["fwd_form", "bwd_form"])
+def test_activation_derivative_and_residual_in_the_big_tile_epilogue(L, tiled, tr, ci):
+    ci, dtype = ci
+    with compute(L, dtype, ci):
+        _activation_derivative_and_residual(L, tiled, tr, ci, dtype)
+
+
+def _activation_derivative_and_residual(L, tiled, tr, ci, dtype):
+    groups, slope = 2, 0.2
     dy, w, geom, gen = dgrad_operands(tr, groups, ci, 37)
     n, hi, wi = geom[0] // groups, geom[1], geom[2]
     act_y, res = rnd(gen, n, hi, wi, ci), rnd(gen, groups * n, hi, wi, ci)
     ws, st = L.workspace(dy.device), torch.cuda.current_stream().cuda_stream
     pre = "movae_convT2d_dgrad" if tr else "movae_conv2d_dgrad"
-    kernel = f"igemm2_{'fwd' if tr else 'bwd'}<128,32>"
+    kernel = kernel_of("fwd" if tr else "bwd", ci, dtype)
     plain = torch.full((groups * n, hi, wi, ci), float("nan"), device=dy.device)
     L.call(pre, dy.data_ptr(), w.data_ptr(), plain.data_ptr(), *geom, ws.data_ptr(), ws.numel(), st)
     assert last_kernel(tiled) == kernel
