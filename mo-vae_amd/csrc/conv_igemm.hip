@@ -920,7 +920,7 @@ struct DeferredReduce {
     RSide r{};
     hipStream_t st = nullptr;
 };
-// PROCESS-wide, not thread_local like the per-call plans (g_pending, g_kpend): the reduce is parked by one library call and taken
+// PROCESS-wide, not thread_local like the per-call plan (pair.h: g_stash): the reduce is parked by one library call and taken
 // by a later one, and torch runs a backward's nodes on its autograd thread while the caller that flushes sits on another.  The
 // calls themselves are sequential (one stream, one step); the arming flag travels with the thread that makes the armed call.
 static DeferredReduce g_defer;
@@ -1120,10 +1120,17 @@ inline int choose_split(int form, int tile_area, int bk, long tiles, int nk, siz
 // ------------------------------------------------------------------------------------------------
 // host dispatch
 // ------------------------------------------------------------------------------------------------
+// pair.h: the stash of a dgrad + wgrad call, as the launchers of the kernel families see it -- is the call collecting its input
+// gradient, hand a planned one over, launch whatever waits on its own
+inline bool pair_collecting();
+template <class Plan>
+inline void pair_stash(const Plan& p);
+inline int pair_flush(hipStream_t st);
 #include "igemm_v2.h"
 #include "conv_thin.h"
 #include "linear_small.h"
 #include "kgemm.h"
+#include "pair.h"
 namespace kg {
 inline bool g_force_kgemm_on() { return g_force_kgemm > 0; }
 }
@@ -1271,10 +1278,8 @@ int launch_bwd(const float* X, const float* W, float* Y, const Geom& g, const Ep
     if (is_linear(g) && lin::linear_small_ok(Ml, g.Nn, g.Cr) && g.Nn % 4 == 0 && aligned16(X) && aligned16(W)) {
         MOVAE_NO_NORM("linear (bwd form)");
         float* ys[1] = {Y};
-        if (v2::g_pair_collect) {  // inside a dgrad + wgrad call: planned, launched together with the weight gradient (linear_bwd_k)
-            lin::g_lin_pend.d = lin::make_prob<1>(X, nullptr, W, nullptr, ys, nullptr, 1, 1, 0, ep.bias, nullptr, (int)Ml, g.Nn, g.Cr, ep.act,
-                                                  ep.slope, 0);
-            lin::g_lin_pend.active = true;
+        if (g_stash.collect) {  // inside a dgrad + wgrad call: planned, launched together with the weight gradient (linear_bwd_k)
+            g_stash.put(lin::make_prob<1>(X, nullptr, W, nullptr, ys, nullptr, 1, 1, 0, ep.bias, nullptr, (int)Ml, g.Nn, g.Cr, ep.act, ep.slope, 0));
             g_last_kernel = "linear_small_k<NN>";
             return MOVAE_OK;
         }
@@ -1370,12 +1375,12 @@ int launch_wgrad(const float* S, const float* Bg, float* const* dW, int G, long 
         lin::linear_small_ok(g.Cs, g.Cb, (Kl + 3) / 4 * 4) && !g_bench_main_only) {  // reduction = batch rows, any count
         MOVAE_NO_NORM("linear (wgrad)");
         if (colsum_done) *colsum_done = colsum_S != nullptr;
-        if (lin::g_lin_pend.active) {  // the layer's input gradient waits: one launch for both
-            lin::g_lin_pend.active = false;
+        if (g_stash.kind == PairStash::LINEAR) {  // the layer's input gradient waits: one launch for both
+            g_stash.kind = PairStash::NONE, g_stash.paired = true;
             const lin::LinProb wp = lin::make_prob<2>(S, nullptr, Bg, nullptr, dW, colsum_S, G, 1, s_gs, nullptr, nullptr, g.Cs, g.Cb, (int)Kl, 0,
                                                       0.f, accumulate);
             g_last_kernel = "linear_bwd_k<false>";
-            return lin::launch_linear_bwd<false>(lin::g_lin_pend.d, wp, st);
+            return lin::launch_linear_bwd<false>(g_stash.lin, wp, st);
         }
         return (g_last_kernel = "linear_small_k<TN>",
                 lin::launch_linear_small<2>(S, Bg, dW, colsum_S, G, s_gs, nullptr, g.Cs, g.Cb, (int)Kl, 0, 0.f, accumulate, st));
@@ -1398,18 +1403,18 @@ int launch_wgrad(const float* S, const float* Bg, float* const* dW, int G, long 
                 if (!colsum_S[i]) cs = nullptr;
         }
         if (colsum_done) *colsum_done = cs != nullptr;
-        if (N <= 32) return (g_last_kernel = "igemm2_wgrad<128,32>", v2::launch_wgrad2<128, 32>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
+        if (N <= 32) return (g_last_kernel = "igemm2_wgrad<128,32>", launch_wgrad2<128, 32>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
         // <= 32 rows of dW (32-channel layers): a 64-row tile would multiply half a tile of padding
-        if (g.Cs <= 32 && N >= 128) return (g_last_kernel = "igemm2_wgrad<32,128>", v2::launch_wgrad2<32, 128>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
+        if (g.Cs <= 32 && N >= 128) return (g_last_kernel = "igemm2_wgrad<32,128>", launch_wgrad2<32, 128>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
         if (g.Cs >= 128 && (long)(g.Cs / 128) * (N / 128) * (Kl / 512) * G >= big_tile_min())
-            return (g_last_kernel = g_movae_compute_bf16 ? "igemm2_wgrad<128,128,true>" : "igemm2_wgrad<128,128>", v2::launch_wgrad2<128, 128>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
+            return (g_last_kernel = g_movae_compute_bf16 ? "igemm2_wgrad<128,128,true>" : "igemm2_wgrad<128,128>", launch_wgrad2<128, 128>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
         // 64 rows of dW with a long reduction (C5: 32 -> 64 channels on 64 x 64 images, four cotangent groups): a 64-wide tile moves
         // 16 KiB of operands per 64 x 64 x 32 MACs -- 16 flop per byte from L2, bandwidth-bound near 0.6 of the MFMA peak; twice the
         // width reads the S operand half as often.  Unpaired (work of this size fills the chip on its own).
         static const bool wide64 = !getenv("MOVAE_NO_WGRAD_64x128");
         if (wide64 && g.Cs > 32 && g.Cs <= 64 && N >= 256 && (long)(N / 128) * (Kl / 512) * G >= big_tile_min())
-            return (g_last_kernel = "igemm2_wgrad<64,128>", v2::launch_wgrad2<64, 128>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
-        return (g_last_kernel = "igemm2_wgrad<64,64>", v2::launch_wgrad2<64, 64>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
+            return (g_last_kernel = "igemm2_wgrad<64,128>", launch_wgrad2<64, 128>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
+        return (g_last_kernel = "igemm2_wgrad<64,64>", launch_wgrad2<64, 64>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
     }
     if (thin::thin_wgrad_ok(g) && ws)
         return (g_last_kernel = "thin_wgrad",
@@ -1478,30 +1483,134 @@ struct FuseScope {
     }
 };
 
-// the BatchNorm-backward request of an input-gradient pass (movae_fuse_t::bn_*): installed for the dgrad dispatch only
-inline void fuse_bn_install(movae_fuse_t* f, int groups) {
-    if (!f) return;
-    f->bn_ppg = 0;
-    f->ep_act_done = 0;
-    const bool want_act = f->ep_act_y && f->ep_act != MOVAE_ACT_NONE;
-    if ((want_act || f->ep_res) && groups >= 1 &&
-        ((reinterpret_cast<uintptr_t>(f->ep_act_y) | reinterpret_cast<uintptr_t>(f->ep_res)) & 15) == 0)
-        g_fuse.am = ActMul{want_act ? f->ep_act_y : nullptr, f->ep_act, f->ep_slope, 0, 0, f->ep_res}, g_fuse.am_groups = groups,
-        g_fuse.am_done = false;
-    if (f->bn_y && f->bn_scale && f->bn_shift && f->bn_part && f->bn_cap > 0 && groups >= 1) {
-        g_fuse.bn_y = f->bn_y, g_fuse.bn_scale = f->bn_scale, g_fuse.bn_shift = f->bn_shift, g_fuse.bn_slope = f->bn_slope;
-        g_fuse.bn_part = f->bn_part, g_fuse.bn_cap = f->bn_cap, g_fuse.bn_groups = groups;
+// the requests of an input-gradient pass (movae_fuse_t::bn_*, ep_*): installed for the dgrad dispatch made inside the scope; on exit
+// reports what the dispatched kernel honoured and clears them
+struct DgradFuseScope {
+    movae_fuse_t* f;
+    DgradFuseScope(movae_fuse_t* fuse, int groups) : f(fuse) {
+        g_fuse = FuseCtx();
+        if (!f) return;
+        f->bn_ppg = 0;
+        f->ep_act_done = 0;
+        const bool want_act = f->ep_act_y && f->ep_act != MOVAE_ACT_NONE;
+        if ((want_act || f->ep_res) && groups >= 1 &&
+            ((reinterpret_cast<uintptr_t>(f->ep_act_y) | reinterpret_cast<uintptr_t>(f->ep_res)) & 15) == 0)
+            g_fuse.am = ActMul{want_act ? f->ep_act_y : nullptr, f->ep_act, f->ep_slope, 0, 0, f->ep_res}, g_fuse.am_groups = groups,
+            g_fuse.am_done = false;
+        if (f->bn_y && f->bn_scale && f->bn_shift && f->bn_part && f->bn_cap > 0 && groups >= 1) {
+            g_fuse.bn_y = f->bn_y, g_fuse.bn_scale = f->bn_scale, g_fuse.bn_shift = f->bn_shift, g_fuse.bn_slope = f->bn_slope;
+            g_fuse.bn_part = f->bn_part, g_fuse.bn_cap = f->bn_cap, g_fuse.bn_groups = groups;
+        }
     }
-}
-inline void fuse_bn_collect(movae_fuse_t* f) {
-    if (f) f->bn_ppg = g_fuse.bn_ppg, f->ep_act_done = g_fuse.am_done ? 1 : 0;
-    g_fuse.bn_y = nullptr, g_fuse.bn_part = nullptr, g_fuse.bn_ppg = 0, g_fuse.bn_groups = 1;
-    g_fuse.am.y = nullptr, g_fuse.am.res = nullptr, g_fuse.am_groups = 1, g_fuse.am_done = false;
-}
+    ~DgradFuseScope() {
+        if (f) f->bn_ppg = g_fuse.bn_ppg, f->ep_act_done = g_fuse.am_done ? 1 : 0;
+        g_fuse.bn_y = nullptr, g_fuse.bn_part = nullptr, g_fuse.bn_ppg = 0, g_fuse.bn_groups = 1;
+        g_fuse.am.y = nullptr, g_fuse.am.res = nullptr, g_fuse.am_groups = 1, g_fuse.am_done = false;
+    }
+};
 #define MOVAE_CHECK_FUSE(f, c)                                                                                                   \
     MOVAE_CHECK_ARG(!(f) || !(f)->in_scale ||                                                                                    \
                         ((f)->in_shift && (c) % 4 == 0 && ((reinterpret_cast<uintptr_t>((f)->in_scale) | reinterpret_cast<uintptr_t>((f)->in_shift)) & 15) == 0), \
                     "fused input transform: needs scale AND shift, 16-byte aligned, channels %% 4 == 0")
+
+// The bodies of the conv / transposed-conv entry points (include/movae.h).  A transposed conv is the conv with the gather forms
+// swapped: its forward is the BWD form, its input gradient the FWD form, and its weight gradient has x as the small-side operand.
+static int conv_fwd(bool transposed, const float* x, const float* w, const float* bias, float* y, int n, int hi, int wi, int ci, int ho,
+                    int wo, int co, int kh, int kw, int stride, int pad, int act, float slope, void* ws, size_t ws_bytes,
+                    movae_stream_t stream, movae_fuse_t* fuse) {
+    const char* who = transposed ? "movae_convT2d_fwd" : "movae_conv2d_fwd";
+    unsigned* const ws_header = ws && ws_bytes > (size_t)MOVAE_WS_HEADER_BYTES ? static_cast<unsigned*>(ws) : nullptr;
+    MOVAE_WS_SCRATCH(ws, ws_bytes);
+    MOVAE_CHECK_ARG(x && w && y, "%s: null pointer", who);
+    if (int rc = check_conv_shape(who, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, transposed)) return rc;
+    MOVAE_CHECK_FUSE(fuse, ci);
+    FuseScope scope(fuse, 0);
+    g_fuse.fin.counter = ws_header ? ws_header + 64 : nullptr;  // words 64 .. 127 of the header: one arrival counter per column tile
+    Geom g{n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad};
+    return transposed ? launch_bwd(x, w, y, g, Epilogue{bias, act, slope}, ws, ws_bytes, (hipStream_t)stream)
+                      : launch_fwd(x, w, y, g, Epilogue{bias, act, slope}, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// n counts the images of ALL `groups` cotangents (dy / dx stacked); fuse->bn_* / ep_* as in include/movae.h (null: none)
+static int conv_dgrad(bool transposed, const float* dy, const float* w, float* dx, int n, int hi, int wi, int ci, int ho, int wo, int co,
+                      int kh, int kw, int stride, int pad, void* ws, size_t ws_bytes, movae_stream_t stream, movae_fuse_t* fuse, int groups) {
+    const char* who = transposed ? "movae_convT2d_dgrad" : "movae_conv2d_dgrad";
+    DgradFuseScope scope(fuse, groups);
+    MOVAE_WS_SCRATCH(ws, ws_bytes);
+    MOVAE_CHECK_ARG(dy && w && dx, "%s: null pointer", who);
+    if (int rc = check_conv_shape(who, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, transposed)) return rc;
+    // gathered tensor = dy (ho x wo x co), output grid = dx (hi x wi x ci).  conv: W[co][tap][ci] is the [Cr][tap][Nn] image of the
+    // BWD form; transposed: dx[p][ci] = sum dy[p*s - pad + tap][co] * W[ci][tap][co], the FWD form with W as [Nn=ci][tap][Cr=co]
+    Geom g{n, ho, wo, co, hi, wi, ci, kh, kw, stride, pad};
+    return transposed ? launch_fwd(dy, w, dx, g, Epilogue{nullptr, MOVAE_ACT_NONE, 0.f}, ws, ws_bytes, (hipStream_t)stream)
+                      : launch_bwd(dy, w, dx, g, Epilogue{nullptr, MOVAE_ACT_NONE, 0.f}, ws, ws_bytes, (hipStream_t)stream);
+}
+
+static int conv_wgrad_grouped(bool transposed, int groups, const float* dy, const float* x, float* const* dw, float* const* dbias, int n,
+                              int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride, int pad, int accumulate, void* ws,
+                              size_t ws_bytes, movae_stream_t stream, const movae_fuse_t* fuse) {
+    const char* who = transposed ? "movae_convT2d_wgrad" : "movae_conv2d_wgrad";
+    DeferArmScope defer_scope;  // (movae_reduce_defer arms ONE weight-gradient call)
+    MOVAE_CHECK_FUSE(fuse, ci);
+    FuseScope scope(const_cast<movae_fuse_t*>(fuse), transposed ? 1 : 2);
+    void* ws_full = ws;
+    const size_t ws_full_bytes = ws_bytes;
+    MOVAE_WS_SCRATCH(ws, ws_bytes);
+    MOVAE_CHECK_ARG(dy && x && dw && groups >= 1 && groups <= 8, "%s: null pointer / bad group count", who);
+    for (int i = 0; i < groups; ++i) MOVAE_CHECK_ARG(dw[i], "%s: null dw", who);
+    if (int rc = check_conv_shape(who, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, transposed)) return rc;
+    const long dy_gs = (long)n * ho * wo * co;  // dy is stacked [groups][n][ho][wo][co]; x is shared
+    // conv: dy is the small side, and its column sums (the bias gradient) may ride on the weight gradient; transposed: x is
+    bool bias_done = false;
+    const int rc = transposed ? launch_wgrad(x, dy, dw, groups, 0, dy_gs, WGeom{n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad}, accumulate, ws,
+                                             ws_bytes, (hipStream_t)stream)
+                              : launch_wgrad(dy, x, dw, groups, dy_gs, 0, WGeom{n, ho, wo, co, hi, wi, ci, kh, kw, stride, pad}, accumulate, ws,
+                                             ws_bytes, (hipStream_t)stream, dbias, &bias_done);
+    if (rc) return rc;
+    if (dbias && !bias_done && !g_bench_main_only && g_defer.pending && g_defer.serial != defer_scope.serial)
+        if (int rc2 = defer_flush()) return rc2;  // the column sums below use the arena the parked reduce's slabs lie in
+    if (dbias && !bias_done && !g_bench_main_only)
+        for (int i = 0; i < groups; ++i)
+            if (dbias[i])
+                if (int rc2 = movae_colsum(dy + i * dy_gs, dbias[i], n * ho * wo, co, accumulate, ws_full, ws_full_bytes, stream)) return rc2;
+    return MOVAE_OK;
+}
+
+// dgrad (over groups * n images) and the grouped wgrad of one layer through ONE main launch where both land on kernels with a paired
+// form (pair.h); otherwise exactly the two calls, in that order.
+static int conv_dgrad_wgrad_grouped(bool transposed, int groups, const float* dy, const float* w, const float* x, float* dx, float* const* dw,
+                                    float* const* dbias, int n, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,
+                                    int pad, int accumulate, void* ws, size_t ws_bytes, movae_stream_t stream, const movae_fuse_t* fuse) {
+    static const bool enabled = !getenv("MOVAE_NO_PAIR");
+    MOVAE_CHECK_ARG(dx && w, "%s: null pointer", transposed ? "movae_convT2d_dgrad_wgrad" : "movae_conv2d_dgrad_wgrad");
+    g_stash.clear();
+    g_stash.collect = enabled;
+    // (the dgrad's plan -- also a stashed one -- keeps what it claimed of fuse->bn_* / ep_*)
+    int rc = conv_dgrad(transposed, dy, w, dx, groups * n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream,
+                        const_cast<movae_fuse_t*>(fuse), groups);
+    g_stash.collect = false;
+    const char* dgrad_kernel = g_last_kernel;
+    if (rc) {
+        g_stash.clear();
+        return rc;
+    }
+    size_t used = (g_stash.ws_used + 255) / 256 * 256;
+    if (g_stash.kind == PairStash::TILE && (!ws || used + (32u << 20) > ws_bytes)) {  // no room left for the wgrad's slabs next to the dgrad's
+        if ((rc = g_stash.flush((hipStream_t)stream))) return rc;
+        used = 0;
+    }
+    // (`fuse` describes the activation operand x, which only the weight gradient reads)
+    rc = conv_wgrad_grouped(transposed, groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate,
+                            ws ? static_cast<char*>(ws) + used : nullptr, ws_bytes - used, stream, fuse);
+    const int rc2 = g_stash.flush((hipStream_t)stream);  // the wgrad took a kernel that does not pair: the input gradient goes alone
+    if (!rc) rc = rc2;
+    if (!g_stash.paired) {  // two main launches: movae_bench_last_kernel() names both
+        static thread_local char both[128];
+        snprintf(both, sizeof(both), "%s + %s", dgrad_kernel, g_last_kernel);
+        g_last_kernel = both;
+    }
+    return rc;
+}
 
 extern "C" {
 
@@ -1567,73 +1676,36 @@ int movae_bench_main_kernel_only(int on) {
 int movae_conv2d_fwd_f(const float* x, const float* w, const float* bias, float* y, int n, int hi, int wi, int ci, int ho,
                        int wo, int co, int kh, int kw, int stride, int pad, int act, float slope, void* ws, size_t ws_bytes,
                        movae_stream_t stream, movae_fuse_t* fuse) {
-    unsigned* const ws_header = ws && ws_bytes > (size_t)MOVAE_WS_HEADER_BYTES ? static_cast<unsigned*>(ws) : nullptr;
-    MOVAE_WS_SCRATCH(ws, ws_bytes);
-    MOVAE_CHECK_ARG(x && w && y, "movae_conv2d_fwd: null pointer");
-    if (int rc = check_conv_shape("movae_conv2d_fwd", n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, false)) return rc;
-    MOVAE_CHECK_FUSE(fuse, ci);
-    FuseScope scope(fuse, 0);
-    g_fuse.fin.counter = ws_header ? ws_header + 64 : nullptr;  // words 64 .. 127 of the header: one arrival counter per column tile
-    Geom g{n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad};
-    return launch_fwd(x, w, y, g, Epilogue{bias, act, slope}, ws, ws_bytes, (hipStream_t)stream);
+    return conv_fwd(false, x, w, bias, y, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, act, slope, ws, ws_bytes, stream, fuse);
 }
 
 int movae_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int n, int hi, int wi, int ci, int ho,
                      int wo, int co, int kh, int kw, int stride, int pad, int act, float slope, void* ws, size_t ws_bytes,
                      movae_stream_t stream) {
-    return movae_conv2d_fwd_f(x, w, bias, y, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, act, slope, ws, ws_bytes, stream, nullptr);
+    return conv_fwd(false, x, w, bias, y, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, act, slope, ws, ws_bytes, stream, nullptr);
 }
 
 int movae_conv2d_dgrad(const float* dy, const float* w, float* dx, int n, int hi, int wi, int ci, int ho, int wo, int co,
                        int kh, int kw, int stride, int pad, void* ws, size_t ws_bytes, movae_stream_t stream) {
-    MOVAE_WS_SCRATCH(ws, ws_bytes);
-    MOVAE_CHECK_ARG(dy && w && dx, "movae_conv2d_dgrad: null pointer");
-    if (int rc = check_conv_shape("movae_conv2d_dgrad", n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, false)) return rc;
-    // gathered tensor = dy (ho x wo x co), output grid = dx (hi x wi x ci); W[co][tap][ci] is the [Cr][tap][Nn] image
-    Geom g{n, ho, wo, co, hi, wi, ci, kh, kw, stride, pad};
-    return launch_bwd(dy, w, dx, g, Epilogue{nullptr, MOVAE_ACT_NONE, 0.f}, ws, ws_bytes, (hipStream_t)stream);
+    return conv_dgrad(false, dy, w, dx, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream, nullptr, 1);
 }
 
-// n counts the images of ALL `groups` cotangents (dy / dx stacked); fuse->bn_* as in include/movae.h
 int movae_conv2d_dgrad_f(const float* dy, const float* w, float* dx, int n, int hi, int wi, int ci, int ho, int wo, int co,
                          int kh, int kw, int stride, int pad, void* ws, size_t ws_bytes, movae_stream_t stream, movae_fuse_t* fuse,
                          int groups) {
-    g_fuse = FuseCtx();
-    fuse_bn_install(fuse, groups);
-    const int rc = movae_conv2d_dgrad(dy, w, dx, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream);
-    fuse_bn_collect(fuse);
-    return rc;
+    return conv_dgrad(false, dy, w, dx, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream, fuse, groups);
 }
 
 int movae_conv2d_wgrad_grouped_f(int groups, const float* dy, const float* x, float* const* dw, float* const* dbias, int n, int hi,
                                int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride, int pad, int accumulate,
                                void* ws, size_t ws_bytes, movae_stream_t stream, const movae_fuse_t* fuse) {
-    DeferArmScope defer_scope;  // (movae_reduce_defer arms ONE weight-gradient call)
-    MOVAE_CHECK_FUSE(fuse, ci);
-    FuseScope scope(const_cast<movae_fuse_t*>(fuse), 2);
-    void* ws_full = ws;
-    const size_t ws_full_bytes = ws_bytes;
-    MOVAE_WS_SCRATCH(ws, ws_bytes);
-    MOVAE_CHECK_ARG(dy && x && dw && groups >= 1 && groups <= 8, "movae_conv2d_wgrad: null pointer / bad group count");
-    for (int i = 0; i < groups; ++i) MOVAE_CHECK_ARG(dw[i], "movae_conv2d_wgrad: null dw");
-    if (int rc = check_conv_shape("movae_conv2d_wgrad", n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, false)) return rc;
-    WGeom g{n, ho, wo, co, hi, wi, ci, kh, kw, stride, pad};
-    const long dy_gs = (long)n * ho * wo * co;  // dy is stacked [groups][n][ho][wo][co]; x is shared
-    bool bias_done = false;
-    if (int rc = launch_wgrad(dy, x, dw, groups, dy_gs, 0, g, accumulate, ws, ws_bytes, (hipStream_t)stream, dbias, &bias_done)) return rc;
-    if (dbias && !bias_done && !g_bench_main_only && g_defer.pending && g_defer.serial != defer_scope.serial)
-        if (int rc = defer_flush()) return rc;  // the column sums below use the arena the parked reduce's slabs lie in
-    if (dbias && !bias_done && !g_bench_main_only)
-        for (int i = 0; i < groups; ++i)
-            if (dbias[i])
-                if (int rc = movae_colsum(dy + i * dy_gs, dbias[i], n * ho * wo, co, accumulate, ws_full, ws_full_bytes, stream)) return rc;
-    return MOVAE_OK;
+    return conv_wgrad_grouped(false, groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, fuse);
 }
 
 int movae_conv2d_wgrad_grouped(int groups, const float* dy, const float* x, float* const* dw, float* const* dbias, int n, int hi,
                                int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride, int pad, int accumulate,
                                void* ws, size_t ws_bytes, movae_stream_t stream) {
-    return movae_conv2d_wgrad_grouped_f(groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
+    return conv_wgrad_grouped(false, groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
 }
 
 int movae_conv2d_wgrad(const float* dy, const float* x, float* dw, float* dbias, int n, int hi, int wi, int ci, int ho,
@@ -1641,78 +1713,42 @@ int movae_conv2d_wgrad(const float* dy, const float* x, float* dw, float* dbias,
                        movae_stream_t stream) {
     float* dws[1] = {dw};
     float* dbs[1] = {dbias};
-    return movae_conv2d_wgrad_grouped(1, dy, x, dws, dbias ? dbs : nullptr, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate,
-                                      ws, ws_bytes, stream);
+    return conv_wgrad_grouped(false, 1, dy, x, dws, dbias ? dbs : nullptr, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
 }
 
 int movae_convT2d_fwd_f(const float* x, const float* w, const float* bias, float* y, int n, int hi, int wi, int ci, int ho,
                         int wo, int co, int kh, int kw, int stride, int pad, int act, float slope, void* ws, size_t ws_bytes,
                         movae_stream_t stream, movae_fuse_t* fuse) {
-    unsigned* const ws_header = ws && ws_bytes > (size_t)MOVAE_WS_HEADER_BYTES ? static_cast<unsigned*>(ws) : nullptr;
-    MOVAE_WS_SCRATCH(ws, ws_bytes);
-    MOVAE_CHECK_ARG(x && w && y, "movae_convT2d_fwd: null pointer");
-    if (int rc = check_conv_shape("movae_convT2d_fwd", n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, true)) return rc;
-    MOVAE_CHECK_FUSE(fuse, ci);
-    FuseScope scope(fuse, 0);
-    g_fuse.fin.counter = ws_header ? ws_header + 64 : nullptr;  // words 64 .. 127 of the header: one arrival counter per column tile
-    Geom g{n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad};
-    return launch_bwd(x, w, y, g, Epilogue{bias, act, slope}, ws, ws_bytes, (hipStream_t)stream);
+    return conv_fwd(true, x, w, bias, y, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, act, slope, ws, ws_bytes, stream, fuse);
 }
 
 int movae_convT2d_fwd(const float* x, const float* w, const float* bias, float* y, int n, int hi, int wi, int ci, int ho,
                       int wo, int co, int kh, int kw, int stride, int pad, int act, float slope, void* ws, size_t ws_bytes,
                       movae_stream_t stream) {
-    return movae_convT2d_fwd_f(x, w, bias, y, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, act, slope, ws, ws_bytes, stream, nullptr);
+    return conv_fwd(true, x, w, bias, y, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, act, slope, ws, ws_bytes, stream, nullptr);
 }
 
 int movae_convT2d_dgrad(const float* dy, const float* w, float* dx, int n, int hi, int wi, int ci, int ho, int wo, int co,
                         int kh, int kw, int stride, int pad, void* ws, size_t ws_bytes, movae_stream_t stream) {
-    MOVAE_WS_SCRATCH(ws, ws_bytes);
-    MOVAE_CHECK_ARG(dy && w && dx, "movae_convT2d_dgrad: null pointer");
-    if (int rc = check_conv_shape("movae_convT2d_dgrad", n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, true)) return rc;
-    // dx[p][ci] = sum dy[p*s - pad + tap][co] * W[ci][tap][co]  : FWD form over dy with W as [Nn=ci][tap][Cr=co]
-    Geom g{n, ho, wo, co, hi, wi, ci, kh, kw, stride, pad};
-    return launch_fwd(dy, w, dx, g, Epilogue{nullptr, MOVAE_ACT_NONE, 0.f}, ws, ws_bytes, (hipStream_t)stream);
+    return conv_dgrad(true, dy, w, dx, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream, nullptr, 1);
 }
 
 int movae_convT2d_dgrad_f(const float* dy, const float* w, float* dx, int n, int hi, int wi, int ci, int ho, int wo, int co,
                           int kh, int kw, int stride, int pad, void* ws, size_t ws_bytes, movae_stream_t stream, movae_fuse_t* fuse,
                           int groups) {
-    g_fuse = FuseCtx();
-    fuse_bn_install(fuse, groups);
-    const int rc = movae_convT2d_dgrad(dy, w, dx, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream);
-    fuse_bn_collect(fuse);
-    return rc;
+    return conv_dgrad(true, dy, w, dx, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream, fuse, groups);
 }
 
 int movae_convT2d_wgrad_grouped_f(int groups, const float* dy, const float* x, float* const* dw, float* const* dbias, int n, int hi,
                                 int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride, int pad, int accumulate,
                                 void* ws, size_t ws_bytes, movae_stream_t stream, const movae_fuse_t* fuse) {
-    DeferArmScope defer_scope;  // (movae_reduce_defer arms ONE weight-gradient call)
-    MOVAE_CHECK_FUSE(fuse, ci);
-    FuseScope scope(const_cast<movae_fuse_t*>(fuse), 1);
-    void* ws_full = ws;
-    const size_t ws_full_bytes = ws_bytes;
-    MOVAE_WS_SCRATCH(ws, ws_bytes);
-    MOVAE_CHECK_ARG(dy && x && dw && groups >= 1 && groups <= 8, "movae_convT2d_wgrad: null pointer / bad group count");
-    for (int i = 0; i < groups; ++i) MOVAE_CHECK_ARG(dw[i], "movae_convT2d_wgrad: null dw");
-    if (int rc = check_conv_shape("movae_convT2d_wgrad", n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, true)) return rc;
-    WGeom g{n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad};
-    const long dy_gs = (long)n * ho * wo * co;  // the small side (x) is shared, the gathered side (dy) is per group
-    if (int rc = launch_wgrad(x, dy, dw, groups, 0, dy_gs, g, accumulate, ws, ws_bytes, (hipStream_t)stream)) return rc;
-    if (dbias && !g_bench_main_only && g_defer.pending && g_defer.serial != defer_scope.serial)
-        if (int rc = defer_flush()) return rc;  // the column sums below use the arena the parked reduce's slabs lie in
-    if (dbias && !g_bench_main_only)
-        for (int i = 0; i < groups; ++i)
-            if (dbias[i])
-                if (int rc = movae_colsum(dy + i * dy_gs, dbias[i], n * ho * wo, co, accumulate, ws_full, ws_full_bytes, stream)) return rc;
-    return MOVAE_OK;
+    return conv_wgrad_grouped(true, groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, fuse);
 }
 
 int movae_convT2d_wgrad_grouped(int groups, const float* dy, const float* x, float* const* dw, float* const* dbias, int n, int hi,
                                 int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride, int pad, int accumulate,
                                 void* ws, size_t ws_bytes, movae_stream_t stream) {
-    return movae_convT2d_wgrad_grouped_f(groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
+    return conv_wgrad_grouped(true, groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
 }
 
 int movae_convT2d_wgrad(const float* dy, const float* x, float* dw, float* dbias, int n, int hi, int wi, int ci, int ho,
@@ -1720,90 +1756,33 @@ int movae_convT2d_wgrad(const float* dy, const float* x, float* dw, float* dbias
                         movae_stream_t stream) {
     float* dws[1] = {dw};
     float* dbs[1] = {dbias};
-    return movae_convT2d_wgrad_grouped(1, dy, x, dws, dbias ? dbs : nullptr, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate,
-                                       ws, ws_bytes, stream);
-}
-
-// dgrad (over groups * n images) and the grouped wgrad of one layer through ONE main launch when both land on the small-tile
-// MFMA kernels (igemm2_pair); otherwise exactly the two calls above, in that order.
-static int pair_calls(bool transposed, int groups, const float* dy, const float* w, const float* x, float* dx, float* const* dw,
-                      float* const* dbias, int n, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride, int pad,
-                      int accumulate, void* ws, size_t ws_bytes, movae_stream_t stream, const movae_fuse_t* fuse) {
-    static const bool enabled = !getenv("MOVAE_NO_PAIR");
-    v2::g_pending.active = false;
-    kg::g_kpend.active = false;
-    lin::g_lin_pend.active = false;
-    v2::g_pair_collect = enabled;
-    g_fuse = FuseCtx();
-    fuse_bn_install(const_cast<movae_fuse_t*>(fuse), groups);  // (the dgrad's plan -- also a stashed one -- keeps what it claimed)
-    int rc = transposed ? movae_convT2d_dgrad(dy, w, dx, groups * n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream)
-                        : movae_conv2d_dgrad(dy, w, dx, groups * n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, ws, ws_bytes, stream);
-    fuse_bn_collect(const_cast<movae_fuse_t*>(fuse));
-    v2::g_pair_collect = false;
-    const char* dgrad_kernel = g_last_kernel;
-    if (rc) {
-        v2::g_pending.active = false;
-        kg::g_kpend.active = false;
-        lin::g_lin_pend.active = false;
-            return rc;
-    }
-    size_t used = v2::g_pending.active ? (v2::g_pending.ws_used + 255) / 256 * 256 : 0;
-    if (v2::g_pending.active && (!ws || used + (32u << 20) > ws_bytes)) {  // no room left for the wgrad's slabs next to the dgrad's
-        if ((rc = v2::flush_pending((hipStream_t)stream))) return rc;
-        used = 0;
-    }
-    void* ws2 = ws ? static_cast<char*>(ws) + used : nullptr;
-    // (`fuse` describes the activation operand x, which only the weight gradient reads)
-    rc = transposed ? movae_convT2d_wgrad_grouped_f(groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws2,
-                                                    ws_bytes - used, stream, fuse)
-                    : movae_conv2d_wgrad_grouped_f(groups, dy, x, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws2,
-                                                   ws_bytes - used, stream, fuse);
-    if (v2::g_pending.active || kg::g_kpend.active) {  // the wgrad took a kernel that does not pair (thin / linear / generic)
-        const int rc2 = v2::flush_pending((hipStream_t)stream);
-        if (!rc) rc = rc2;
-    }
-    if (lin::g_lin_pend.active) {  // a linear input gradient whose weight gradient took another kernel
-        const int rc2 = lin::lin_flush((hipStream_t)stream);
-        if (!rc) rc = rc2;
-    }
-    if (strncmp(g_last_kernel, "igemm2_pair", 11) != 0 && strncmp(g_last_kernel, "kpair_k", 7) != 0 && strncmp(g_last_kernel, "linear_bwd_k", 12) != 0) {  // two main launches: movae_bench_last_kernel() names both
-        static thread_local char both[128];
-        snprintf(both, sizeof(both), "%s + %s", dgrad_kernel, g_last_kernel);
-        g_last_kernel = both;
-    }
-    return rc;
+    return conv_wgrad_grouped(true, 1, dy, x, dws, dbias ? dbs : nullptr, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
 }
 
 int movae_conv2d_dgrad_wgrad_grouped_f(int groups, const float* dy, const float* w, const float* x, float* dx, float* const* dw,
                                        float* const* dbias, int n, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw,
                                        int stride, int pad, int accumulate, void* ws, size_t ws_bytes, movae_stream_t stream,
                                        const movae_fuse_t* fuse) {
-    MOVAE_CHECK_ARG(dx && w, "movae_conv2d_dgrad_wgrad: null pointer");
-    return pair_calls(false, groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes,
-                      stream, fuse);
+    return conv_dgrad_wgrad_grouped(false, groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, fuse);
 }
 
 int movae_conv2d_dgrad_wgrad_grouped(int groups, const float* dy, const float* w, const float* x, float* dx, float* const* dw,
                                      float* const* dbias, int n, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw,
                                      int stride, int pad, int accumulate, void* ws, size_t ws_bytes, movae_stream_t stream) {
-    return movae_conv2d_dgrad_wgrad_grouped_f(groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate,
-                                              ws, ws_bytes, stream, nullptr);
+    return conv_dgrad_wgrad_grouped(false, groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
 }
 
 int movae_convT2d_dgrad_wgrad_grouped_f(int groups, const float* dy, const float* w, const float* x, float* dx, float* const* dw,
                                         float* const* dbias, int n, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw,
                                         int stride, int pad, int accumulate, void* ws, size_t ws_bytes, movae_stream_t stream,
                                         const movae_fuse_t* fuse) {
-    MOVAE_CHECK_ARG(dx && w, "movae_convT2d_dgrad_wgrad: null pointer");
-    return pair_calls(true, groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes,
-                      stream, fuse);
+    return conv_dgrad_wgrad_grouped(true, groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, fuse);
 }
 
 int movae_convT2d_dgrad_wgrad_grouped(int groups, const float* dy, const float* w, const float* x, float* dx, float* const* dw,
                                       float* const* dbias, int n, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw,
                                       int stride, int pad, int accumulate, void* ws, size_t ws_bytes, movae_stream_t stream) {
-    return movae_convT2d_dgrad_wgrad_grouped_f(groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate,
-                                               ws, ws_bytes, stream, nullptr);
+    return conv_dgrad_wgrad_grouped(true, groups, dy, w, x, dx, dw, dbias, n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, accumulate, ws, ws_bytes, stream, nullptr);
 }
 
 // Two fully connected layers on one input (fc_mu || fc_var) -- see lin::LinPair.  MOVAE_EUNSUPPORTED (nothing launched) for shapes

@@ -1189,41 +1189,26 @@ __global__ __launch_bounds__(256) void igemm2_pair(FwdArgs fa, BwdArgs ba, WgArg
 #undef ZERO4
 
 // ---- host side ------------------------------------------------------------------------------------
-// Pairing (movae_conv*_dgrad_wgrad*): while g_pair_collect is set, a dgrad that lands on one of the small-tile kernels is
-// PLANNED but not launched -- its arguments wait in g_pending -- and the wgrad that follows launches both through
-// igemm2_pair when it lands on a small-tile kernel too.  Anything else flushes the pending dgrad as an ordinary launch.
-struct PendingDgrad {
-    bool active = false;
-    int form = 0, bm = 0, bn = 0;  // 0 = FWD gather (transposed-conv dgrad), 1 = BWD gather (conv dgrad)
+// Pairing (movae_conv*_dgrad_wgrad*, pair.h): inside such a call a dgrad that lands on one of the small-tile kernels is PLANNED but
+// not launched -- its plan waits in the stash -- and the wgrad that follows launches both through igemm2_pair when it lands on a
+// small-tile kernel too.  Anything else launches the stashed plan as an ordinary launch (launch_tile_dgrad).
+struct TileDgrad {
+    int form = 0, bm = 0;  // 0 = FWD gather (transposed-conv dgrad), 1 = BWD gather (conv dgrad); tile <64,64> or <128,32>
     FwdArgs fa;
     BwdArgs ba;
     int gx = 0, gy = 0, gz = 0;
-    size_t ws_used = 0;            // bytes of the scratch arena taken by the dgrad's slabs
+    size_t slab_bytes = 0;  // bytes of the scratch arena taken by the dgrad's slabs
     // split-K epilogue of the dgrad, issued after the (paired or plain) main launch
-    bool reduce = false;
     int S = 1;
-    long total = 0;
     BnBwd rbb{};          // rbb.y != null: the reduce also emits the fused BatchNorm's backward sums (rows per block: rbb_rpb)
     int rbb_rpb = 0;
     ActMul ram{nullptr, 0, 0.f, 0, 0, nullptr};  // set: the reduce applies the ActMul (activation derivative / residual) instead of the epilogue
 };
-static thread_local PendingDgrad g_pending;
-static thread_local bool g_pair_collect = false;
 
 template <int BM, int BN>
 constexpr bool pair_dgrad_tile() { return (BM == 64 && BN == 64) || (BM == 128 && BN == 32); }
 template <int BM, int BN>
 constexpr bool pair_wgrad_tile() { return (BM == 64 && BN == 64) || (BM == 32 && BN == 128); }
-
-// The block-internal split-K kernels (kgemm.h, included after this file) stash their input-gradient launch the same way; the
-// weight-gradient launchers below reach it through these hooks: pending? / launch it together with this weight gradient (one
-// kernel: kpair_k) / launch it on its own.
-struct KPairHooks {
-    bool (*pending)();
-    int (*pair)(const WgArgs& wa, int wgx, int wgy, int wgz, bool w64, hipStream_t st);
-    int (*flush)(hipStream_t st);
-};
-static KPairHooks g_kpair{nullptr, nullptr, nullptr};
 
 // The main launch of a split-K plan wrote S > 1 slabs: the ONE reduce that turns them into the result, for both gather forms
 // (BwdArgs: per-class split factors, rows are output pixels).  In order of precedence: with the backward sums of a fused
@@ -1260,33 +1245,72 @@ int finish_splitk(const Args& a, int S, const BnBwd& rbb, int rbb_rpb, const Act
     }
 }
 
-// What the BatchNorm side products of a launch need from the host: are statistics of the result wanted (for the BatchNorm that
-// follows; never on a backward pass: those are the paired / collected ones), do the side products leave through the LDS tile
-// epilogue, where its 16-byte pieces apply, and how many partial slots a block then owns (one; else one per wave row).
-struct SidePlan {
-    bool want_stats;
-    int side_lds, slots;
+// The side products of one tiled FWD- or BWD-form launch, as the calling entry point asked for them (g_fuse): the statistics of the
+// result (for the BatchNorm that follows; a dgrad + wgrad call installs no such request for its input gradient), the backward
+// sums of a fused BatchNorm whose output gradient the result is, and the previous layer's activation derivative / a residual on
+// the result (ActMul).  Unsplit (S == 1) they leave through the main kernel's epilogue -- through its LDS tile where the 16-byte
+// pieces apply (side_lds: one partial slot per block, else one per wave row) -- and under split-K through the reduce
+// (finish_splitk: want_stats, rbb, ram).
+struct SideProducts {
+    int side_lds = 0;
+    bool want_stats = false;
+    float* stats = nullptr;
+    BnBwd bb{}, rbb{};
+    int rbb_rpb = 0;  // rows per block of the reduce that emits rbb
+    ActMul am{nullptr, 0, 0.f, 0, 0, nullptr}, ram{nullptr, 0, 0.f, 0, 0, nullptr};
 };
-template <int BM, int BN>
-SidePlan side_plan(const float* Y, const Epilogue& ep, int Nn) {
-    const int lds = (Nn % 4 == 0 && ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias) |
-                                      reinterpret_cast<uintptr_t>(g_fuse.bn_y)) & 15) == 0) ? 1 : 0;
-    return SidePlan{g_fuse.stats && ep.act == MOVAE_ACT_NONE && !g_pair_collect, lds, lds ? 1 : T2<BM, BN>::WM};
+// rows: result rows over all cotangent groups, in ncls output-parity classes (FWD form: one) of gx row blocks of BM rows each;
+// cls_equal: the classes are equally large (Ho % s == 0 && Wo % s == 0).  Claims, in this order: statistics, backward sums, ActMul.
+inline SideProducts plan_side_products(const float* Y, const Epilogue& ep, int Nn, long rows, int ncls, bool cls_equal, int BM, int wave_rows,
+                                       int gx, int S) {
+    SideProducts p;
+    p.side_lds = (Nn % 4 == 0 && ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias) |
+                                   reinterpret_cast<uintptr_t>(g_fuse.bn_y)) & 15) == 0) ? 1 : 0;
+    const int slots = p.side_lds ? 1 : wave_rows;
+    p.want_stats = g_fuse.stats && ep.act == MOVAE_ACT_NONE;
+    if (p.want_stats && S == 1) p.stats = fuse_stats_claim((long)ncls * gx * slots, Nn);
+    if (g_fuse.bn_y && ep.act == MOVAE_ACT_NONE && !ep.bias) {
+        const int G = g_fuse.bn_groups;
+        if (S == 1) {
+            // from the epilogue: equally large classes and whole row blocks per group and class
+            const long rows_c = rows / ncls / G;
+            if (cls_equal && rows % ((long)ncls * G) == 0 && rows_c % BM == 0) {
+                const long ppg = (long)ncls * (rows_c / BM) * slots;
+                if (float* part = fuse_bn_claim(ppg, Nn))
+                    p.bb = BnBwd{g_fuse.bn_y, g_fuse.bn_scale, g_fuse.bn_shift, g_fuse.bn_slope, part, (int)(rows / G), (int)ppg};
+            }
+        } else {
+            plan_reduce_bnbwd(rows, Nn, &p.rbb, &p.rbb_rpb);
+        }
+    }
+    if ((g_fuse.am.y || g_fuse.am.res) && ep.act == MOVAE_ACT_NONE && (!ep.bias || !g_fuse.am.y) && !p.rbb.y && !p.bb.y && Nn % 4 == 0 &&
+        ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias)) & 15) == 0 && !p.want_stats) {
+        const int G = g_fuse.am_groups;
+        if (rows % G == 0) {
+            ActMul am = g_fuse.am;
+            am.per_group = rows / G * Nn;
+            bool ok = true;
+            if (S == 1 && G > 1 && am.y) {  // epilogue: whole row blocks per group and class (equally large classes)
+                const long rows_c = rows / ncls / G;
+                ok = cls_equal && rows % ((long)ncls * G) == 0 && rows_c % BM == 0;
+                am.gx_per_group = ok ? (int)(rows_c / BM) : 0;
+            }
+            if (ok) {
+                if (S == 1) p.am = am;
+                else p.ram = am;
+                g_fuse.am_done = true;
+            }
+        }
+    }
+    return p;
 }
 
-// the stashed dgrad's reduce: never with statistics -- a dgrad is stashed under g_pair_collect only, where side_plan wants none
-inline int finish_pending(hipStream_t st) {
-    const PendingDgrad& p = g_pending;
-    if (!p.reduce) return MOVAE_OK;
+// the stashed dgrad's reduce (never with statistics: see SideProducts)
+inline int finish_tile_dgrad(const TileDgrad& p, hipStream_t st) {
     return p.form == 0 ? finish_splitk(p.fa, p.S, p.rbb, p.rbb_rpb, p.ram, false, st) : finish_splitk(p.ba, p.S, p.rbb, p.rbb_rpb, p.ram, false, st);
 }
 
-inline int flush_pending(hipStream_t st) {  // launch the stashed dgrad on its own
-    if (g_kpair.flush)
-        if (int rc = g_kpair.flush(st)) return rc;
-    PendingDgrad& p = g_pending;
-    if (!p.active) return MOVAE_OK;
-    p.active = false;
+inline int launch_tile_dgrad(const TileDgrad& p, hipStream_t st) {  // the stashed dgrad on its own
     dim3 grid(p.gx, p.gy, p.gz);
     int gz;
     const RSide sd = defer_take_3d(st, &grid, &gz);
@@ -1298,7 +1322,7 @@ inline int flush_pending(hipStream_t st) {  // launch the stashed dgrad on its o
         else hipLaunchKernelGGL((igemm2_bwd<128, 32>), grid, dim3(256), 0, st, p.ba, sd, gz);
     }
     MOVAE_CHECK_LAUNCH("igemm2 dgrad (unpaired)");
-    return finish_pending(st);
+    return finish_tile_dgrad(p, st);
 }
 
 template <int BM, int BN>
@@ -1313,47 +1337,15 @@ int launch_fwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     FwdArgs a{X, W, Y, g, ep, M, K, per_split, slab};
     a.fd_cr = fastdiv_make(g.Cr), a.fd_kw = fastdiv_make(g.KW), a.fd_wlen = fastdiv_make(g.wlen > 0 ? g.wlen : 1);
     a.nrm = g_fuse.nrm;
-    const SidePlan sp = side_plan<BM, BN>(Y, ep, g.Nn);
-    const bool want_stats = sp.want_stats;
-    const int slots = sp.slots;
-    a.side_lds = sp.side_lds;
-    if (want_stats && S == 1) a.stats = fuse_stats_claim((long)gx * slots, g.Nn);
-    // the result is a fused BatchNorm's output gradient: its backward sums from the epilogue (unsplit) or from the reduce
-    BnBwd rbb{};
-    int rbb_rpb = 0;
-    if (g_fuse.bn_y && ep.act == MOVAE_ACT_NONE && !ep.bias) {
-        const long rpg = M / g_fuse.bn_groups;
-        if (S == 1) {
-            if (M % g_fuse.bn_groups == 0 && rpg % BM == 0) {
-                const long ppg = rpg / BM * slots;
-                if (float* part = fuse_bn_claim(ppg, g.Nn))
-                    a.bb = BnBwd{g_fuse.bn_y, g_fuse.bn_scale, g_fuse.bn_shift, g_fuse.bn_slope, part, (int)rpg, (int)ppg};
-            }
-        } else {
-            plan_reduce_bnbwd(M, g.Nn, &rbb, &rbb_rpb);
-        }
-    }
-    // the previous layer's activation derivative on the result: in the epilogue (unsplit) or in the reduce
-    ActMul ram{nullptr, 0, 0.f, 0, 0, nullptr};
-    if ((g_fuse.am.y || g_fuse.am.res) && ep.act == MOVAE_ACT_NONE && (!ep.bias || !g_fuse.am.y) && !rbb.y && !a.bb.y &&
-        M % g_fuse.am_groups == 0 && g.Nn % 4 == 0 && ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias)) & 15) == 0 &&
-        !want_stats) {
-        const long rpg = M / g_fuse.am_groups;
-        if (g_fuse.am_groups == 1 || rpg % BM == 0 || S > 1 || !g_fuse.am.y) {
-            ActMul am = g_fuse.am;
-            am.per_group = rpg * g.Nn;
-            if (S == 1) a.am = am;
-            else ram = am;
-            g_fuse.am_done = true;
-        }
-    }
-    if (g_pair_collect && pair_dgrad_tile<BM, BN>()) {
-        PendingDgrad& p = g_pending;
-        p.active = true;
-        p.form = 0, p.bm = BM, p.bn = BN, p.fa = a, p.gx = gx, p.gy = gy, p.gz = S;
-        p.rbb = rbb, p.rbb_rpb = rbb_rpb, p.ram = ram;
-        p.reduce = S > 1, p.S = S, p.total = (long)M * g.Nn;
-        p.ws_used = S > 1 ? (size_t)M * g.Nn * sizeof(float) * S : 0;
+    const SideProducts sp = plan_side_products(Y, ep, g.Nn, M, 1, true, BM, T2<BM, BN>::WM, gx, S);
+    a.side_lds = sp.side_lds, a.stats = sp.stats, a.bb = sp.bb, a.am = sp.am;
+    a.am.gx_per_group = 0;  // (only the BWD-form body counts row blocks per group)
+    if (pair_collecting() && pair_dgrad_tile<BM, BN>()) {
+        TileDgrad p{};
+        p.form = 0, p.bm = BM, p.fa = a, p.gx = gx, p.gy = gy, p.gz = S;
+        p.S = S, p.rbb = sp.rbb, p.rbb_rpb = sp.rbb_rpb, p.ram = sp.ram;
+        p.slab_bytes = S > 1 ? (size_t)M * g.Nn * sizeof(float) * S : 0;
+        pair_stash(p);
         return MOVAE_OK;
     }
     dim3 grid(gx, gy, S);
@@ -1362,7 +1354,7 @@ int launch_fwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     if (BM == 128 && BN == 128 && g_movae_compute_bf16) hipLaunchKernelGGL((igemm2_fwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
     else hipLaunchKernelGGL((igemm2_fwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_fwd");
-    return finish_splitk(a, S, rbb, rbb_rpb, ram, want_stats, st);
+    return finish_splitk(a, S, sp.rbb, sp.rbb_rpb, sp.ram, sp.want_stats, st);
 }
 
 template <int BM, int BN>
@@ -1432,55 +1424,15 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     }
     a.nrm = g_fuse.nrm;
     a.stats_gx = gx;
-    const SidePlan sp = side_plan<BM, BN>(Y, ep, g.Nn);
-    const bool want_stats = sp.want_stats;
-    const int slots = sp.slots;
-    a.side_lds = sp.side_lds;
-    if (want_stats && Sreal == 1) a.stats = fuse_stats_claim((long)ncls * gx * slots, g.Nn);
-    BnBwd rbb{};
-    int rbb_rpb = 0;
-    if (g_fuse.bn_y && ep.act == MOVAE_ACT_NONE && !ep.bias) {
-        const long pix = (long)g.Nimg * g.Ho * g.Wo;  // output pixels over all cotangent groups
-        if (Sreal == 1) {
-            // equally large classes (even output grid) and whole row blocks per group and class
-            const long rows_c = pix / ncls / g_fuse.bn_groups;
-            if (g.Ho % s == 0 && g.Wo % s == 0 && pix % ((long)ncls * g_fuse.bn_groups) == 0 && rows_c % BM == 0) {
-                const long ppg = (long)ncls * (rows_c / BM) * slots;
-                if (float* part = fuse_bn_claim(ppg, g.Nn))
-                    a.bb = BnBwd{g_fuse.bn_y, g_fuse.bn_scale, g_fuse.bn_shift, g_fuse.bn_slope, part, (int)(pix / g_fuse.bn_groups), (int)ppg};
-            }
-        } else {
-            plan_reduce_bnbwd(pix, g.Nn, &rbb, &rbb_rpb);
-        }
-    }
-    ActMul ram{nullptr, 0, 0.f, 0, 0, nullptr};  // (see launch_fwd2)
-    if ((g_fuse.am.y || g_fuse.am.res) && ep.act == MOVAE_ACT_NONE && (!ep.bias || !g_fuse.am.y) && !rbb.y && !a.bb.y && g.Nn % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(ep.bias)) & 15) == 0 && !want_stats) {
-        const long pix = (long)g.Nimg * g.Ho * g.Wo;
-        const int G = g_fuse.am_groups;
-        if (pix % G == 0) {
-            ActMul am = g_fuse.am;
-            am.per_group = pix / G * g.Nn;
-            bool ok = true;
-            if (Sreal == 1 && G > 1 && am.y) {  // epilogue: whole row blocks per group and class (equally large classes)
-                const long rows_c = pix / ncls / G;
-                ok = g.Ho % s == 0 && g.Wo % s == 0 && pix % ((long)ncls * G) == 0 && rows_c % BM == 0;
-                am.gx_per_group = ok ? (int)(rows_c / BM) : 0;
-            }
-            if (ok) {
-                if (Sreal == 1) a.am = am;
-                else ram = am;
-                g_fuse.am_done = true;
-            }
-        }
-    }
-    if (g_pair_collect && pair_dgrad_tile<BM, BN>()) {
-        PendingDgrad& p = g_pending;
-        p.active = true;
-        p.form = 1, p.bm = BM, p.bn = BN, p.ba = a, p.gx = gx, p.gy = gy, p.gz = zsum;
-        p.rbb = rbb, p.rbb_rpb = rbb_rpb, p.ram = ram;
-        p.reduce = Sreal > 1, p.S = Sreal, p.total = total;
-        p.ws_used = Sreal > 1 ? (size_t)total * sizeof(float) * Sreal : 0;
+    const SideProducts sp = plan_side_products(Y, ep, g.Nn, (long)g.Nimg * g.Ho * g.Wo, ncls, g.Ho % s == 0 && g.Wo % s == 0, BM,
+                                               T2<BM, BN>::WM, gx, Sreal);
+    a.side_lds = sp.side_lds, a.stats = sp.stats, a.bb = sp.bb, a.am = sp.am;
+    if (pair_collecting() && pair_dgrad_tile<BM, BN>()) {
+        TileDgrad p{};
+        p.form = 1, p.bm = BM, p.ba = a, p.gx = gx, p.gy = gy, p.gz = zsum;
+        p.S = Sreal, p.rbb = sp.rbb, p.rbb_rpb = sp.rbb_rpb, p.ram = sp.ram;
+        p.slab_bytes = Sreal > 1 ? (size_t)total * sizeof(float) * Sreal : 0;
+        pair_stash(p);
         return MOVAE_OK;
     }
     dim3 grid(gx, gy, zsum);
@@ -1489,20 +1441,27 @@ int launch_bwd2(const float* X, const float* W, float* Y, const Geom& g, const E
     if (BM == 128 && BN == 128 && g_movae_compute_bf16) hipLaunchKernelGGL((igemm2_bwd<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
     else hipLaunchKernelGGL((igemm2_bwd<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
     MOVAE_CHECK_LAUNCH("igemm2_bwd");
-    return finish_splitk(a, Sreal, rbb, rbb_rpb, ram, want_stats, st);
+    return finish_splitk(a, Sreal, sp.rbb, sp.rbb_rpb, sp.ram, sp.want_stats, st);
 }
 
 template <int FORM, int ABM, int ABN, int WBM, int WBN>
-inline void launch_pair(const PendingDgrad& p, const WgArgs& wa, int wgx, int wgy, int wgz, hipStream_t st) {
+inline void launch_pair(const TileDgrad& p, const WgArgs& wa, int wgx, int wgy, int wgz, hipStream_t st) {
     const int nd = p.gx * p.gy * p.gz, nw = wgx * wgy * wgz;
     const RSide sd = defer_take(st);  // the previous layer's parked weight-gradient reduce rides behind the two problems
     hipLaunchKernelGGL((igemm2_pair<FORM, ABM, ABN, WBM, WBN>), dim3(nd + nw + sd.nblk), dim3(256), 0, st, p.fa, p.ba, wa, nd, p.gx, p.gy,
                        wgx, wgy, nw, sd);
 }
 
-template <int BM, int BN>
-int launch_wgrad2(const float* Sm, const float* Bg, float* const* dW, int G, long s_gs, long b_gs, const WGeom& g, int K,
-                  int accumulate, void* ws, size_t ws_bytes, hipStream_t st, float* const* colsum = nullptr) {
+// The plan of a tiled weight gradient of G cotangent groups on BM x BN tiles: kernel arguments, grid, and whether the result goes
+// through slabs (split-K or accumulate).  pair.h launches it -- alone or in one kernel with the layer's stashed input gradient --
+// and reduce_wgrad2 then folds the slabs.
+struct WgPlan {
+    WgArgs a;
+    int gx, gy, gz;
+    bool slab;
+};
+inline int plan_wgrad2(int BM, int BN, const float* Sm, const float* Bg, float* const* dW, int G, long s_gs, long b_gs, const WGeom& g, int K,
+                       int accumulate, void* ws, size_t ws_bytes, float* const* colsum, WgPlan* p) {
     const int M = g.Cs, N = g.KH * g.KW * g.Cb;
     const long stride = (long)M * N + (colsum ? M : 0);  // floats per slab
     const int gx = ceil_div(M, BM), gy = ceil_div(N, BN);
@@ -1525,46 +1484,19 @@ int launch_wgrad2(const float* Sm, const float* Bg, float* const* dW, int G, lon
     a.cs_on = colsum ? 1 : 0;
     a.slab_stride = stride;
     for (int i = 0; i < 8; ++i) a.cs.p[i] = (colsum && i < G) ? colsum[i] : nullptr;
-    PendingDgrad& p = g_pending;
-    if (g_kpair.pending && g_kpair.pending() && pair_wgrad_tile<BM, BN>()) {  // a kgemm.h input gradient waits: one launch for both
-        if (int rc = g_kpair.pair(a, gx, gy, Sp * G, BM == 64, st)) return rc;
-    } else if (p.active && pair_wgrad_tile<BM, BN>() && (long)p.gx * p.gy * p.gz + (long)gx * gy * Sp * G < 0x7fffffffL) {
-        p.active = false;
-        constexpr int W64 = BM == 64 ? 1 : 0;  // wgrad tile: <64,64> or <32,128>
-        // names as rocprofv3 prints the instantiations: <form, dgrad tile, wgrad tile>
-        if (p.form == 0 && p.bm == 64) {
-            launch_pair<0, 64, 64, W64 ? 64 : 32, W64 ? 64 : 128>(p, a, gx, gy, Sp * G, st);
-            g_last_kernel = W64 ? "igemm2_pair<0,64,64,64,64>" : "igemm2_pair<0,64,64,32,128>";
-        } else if (p.form == 0) {
-            launch_pair<0, 128, 32, W64 ? 64 : 32, W64 ? 64 : 128>(p, a, gx, gy, Sp * G, st);
-            g_last_kernel = W64 ? "igemm2_pair<0,128,32,64,64>" : "igemm2_pair<0,128,32,32,128>";
-        } else if (p.bm == 64) {
-            launch_pair<1, 64, 64, W64 ? 64 : 32, W64 ? 64 : 128>(p, a, gx, gy, Sp * G, st);
-            g_last_kernel = W64 ? "igemm2_pair<1,64,64,64,64>" : "igemm2_pair<1,64,64,32,128>";
-        } else {
-            launch_pair<1, 128, 32, W64 ? 64 : 32, W64 ? 64 : 128>(p, a, gx, gy, Sp * G, st);
-            g_last_kernel = W64 ? "igemm2_pair<1,128,32,64,64>" : "igemm2_pair<1,128,32,32,128>";
-        }
-        MOVAE_CHECK_LAUNCH("igemm2_pair");
-        if (int rc = finish_pending(st)) return rc;
-    } else {
-        if (int rc = flush_pending(st)) return rc;
-        dim3 grid(gx, gy, Sp * G);
-        int gz;
-        const RSide sd = defer_take_3d(st, &grid, &gz);
-        if (BM == 128 && BN == 128 && g_movae_compute_bf16) hipLaunchKernelGGL((igemm2_wgrad<BM, BN, BM == 128 && BN == 128>), grid, dim3(256), 0, st, a, sd, gz);
-        else hipLaunchKernelGGL((igemm2_wgrad<BM, BN>), grid, dim3(256), 0, st, a, sd, gz);
-        MOVAE_CHECK_LAUNCH("igemm2_wgrad");
-    }
-    if (slab) {  // ONE reduce launch for all groups (blockIdx.y = group)
-        RGroups rg{};
-        for (int i = 0; i < G; ++i) rg.out[i] = dW[i], rg.out2[i] = colsum ? colsum[i] : nullptr;
-        rg.slab_gs = (long)Sp * stride;
-        // (deferrable: movae_reduce_defer armed this call -- the reduce waits for the next launch that can carry it)
-        return launch_reduce_groups(out, rg, G, (long)M * N, colsum ? M : 0, Sp, N, nullptr, 0, 0.f, accumulate, st,
-                                    ActMul{nullptr, 0, 0.f, 0, 0, nullptr}, true);
-    }
+    *p = WgPlan{a, gx, gy, Sp * G, slab};
     return MOVAE_OK;
+}
+
+inline int reduce_wgrad2(const WgPlan& p, float* const* dW, int G, int accumulate, hipStream_t st, float* const* colsum) {
+    if (!p.slab) return MOVAE_OK;
+    const int M = p.a.g.Cs, N = p.a.g.KH * p.a.g.KW * p.a.g.Cb;
+    RGroups rg{};  // ONE reduce launch for all groups (blockIdx.y = group)
+    for (int i = 0; i < G; ++i) rg.out[i] = dW[i], rg.out2[i] = colsum ? colsum[i] : nullptr;
+    rg.slab_gs = (long)p.a.Sp * p.a.slab_stride;
+    // (deferrable: movae_reduce_defer armed this call -- the reduce waits for the next launch that can carry it)
+    return launch_reduce_groups(p.a.out, rg, G, (long)M * N, colsum ? M : 0, p.a.Sp, N, nullptr, 0, 0.f, accumulate, st,
+                                ActMul{nullptr, 0, 0.f, 0, 0, nullptr}, true);
 }
 
 }  // namespace v2

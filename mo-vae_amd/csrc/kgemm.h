@@ -659,29 +659,20 @@ __global__ __launch_bounds__(256) void kpair_k(KArgs ka, v2::WgArgs wa, int nd, 
     }
 }
 
-struct KPending {
-    bool active = false;
-    int form = 0;
+// a planned input gradient (four waves, KS = 4) that waits in the stash of a dgrad + wgrad call (pair.h) for its weight gradient
+struct KDgrad {
+    int form = 0;  // 0 = FWD gather, 1 = BWD gather
     KArgs a;
     dim3 tiles;
 };
-static thread_local KPending g_kpend;
-
-template <int FORM>
-inline void launch_k(const KArgs& a, KSplit k, dim3 tiles, hipStream_t st);
-
-inline bool kpend_active() { return g_kpend.active; }
-inline int kpend_flush(hipStream_t st) {
-    if (!g_kpend.active) return MOVAE_OK;
-    g_kpend.active = false;
-    if (g_kpend.form == 0) launch_k<0>(g_kpend.a, KSplit{4, 4}, g_kpend.tiles, st);
-    else launch_k<1>(g_kpend.a, KSplit{4, 4}, g_kpend.tiles, st);
+inline int launch_kdgrad(const KDgrad& p, hipStream_t st) {  // on its own
+    if (p.form == 0) launch_k<0>(p.a, KSplit{4, 4}, p.tiles, st);
+    else launch_k<1>(p.a, KSplit{4, 4}, p.tiles, st);
     MOVAE_CHECK_LAUNCH("kgemm_k (unpaired input gradient)");
     return MOVAE_OK;
 }
-inline int kpend_pair(const v2::WgArgs& wa, int wgx, int wgy, int wgz, bool w64, hipStream_t st) {
-    KPending& p = g_kpend;
-    p.active = false;
+// ... and in one launch with the layer's tiled weight gradient (tile <64,64>: w64, else <32,128>)
+inline int launch_kpair(const KDgrad& p, const v2::WgArgs& wa, int wgx, int wgy, int wgz, bool w64, hipStream_t st) {
     const int nd = p.tiles.x * p.tiles.y * p.tiles.z, nw = wgx * wgy * wgz;
     const RSide sd = defer_take(st);  // the previous layer's parked weight-gradient reduce rides behind the two problems
     const dim3 grid(nd + nw + sd.nblk);
@@ -703,10 +694,6 @@ inline int kpend_pair(const v2::WgArgs& wa, int wgx, int wgy, int wgz, bool w64,
     MOVAE_CHECK_LAUNCH("kpair_k");
     return MOVAE_OK;
 }
-struct KPairInstall {
-    KPairInstall() { v2::g_kpair = v2::KPairHooks{kpend_active, kpend_pair, kpend_flush}; }
-};
-static KPairInstall g_kpair_install;
 
 // MOVAE_KGEMM_BN_FIN=1 (or movae_bench_kgemm_bn_fin(1)): a kgemm forward finishes the BatchNorm that follows inside its own launch
 // (the tail of kgemm_body).  OFF by default: measured at C2 the six layers it applies to cost 7-9 us more per kernel under the
@@ -725,7 +712,7 @@ inline bool plan_side(KArgs& a, const Epilogue& ep, long rows_all, int ncls, int
     const long rows_c = rows_all / ncls;
     a.tiles_c = (int)((rows_c + 31) / 32);
     a.tpg = a.tiles_c;
-    const bool want_stats = g_fuse.stats && ep.act == MOVAE_ACT_NONE && !v2::g_pair_collect;
+    const bool want_stats = g_fuse.stats && ep.act == MOVAE_ACT_NONE;
     if (g_fuse.bn_y && ep.act == MOVAE_ACT_NONE && !ep.bias) {
         const int G = g_fuse.bn_groups;
         if (rows_all % ((long)ncls * G) != 0 || (rows_c / G) % 32 != 0 || !al16(g_fuse.bn_y) || !al16(g_fuse.bn_scale) || !al16(g_fuse.bn_shift))
@@ -781,8 +768,8 @@ inline int launch_kfwd(const float* X, const float* W, float* Y, const Geom& g, 
     static const char* const names[4] = {"kgemm_k<0,8,8,false>", "kgemm_k<0,4,4,false>", "kgemm_k<0,4,2,false>", "kgemm_k<0,4,1,false>"};
     static const char* const names_n[4] = {"kgemm_k<0,8,8,true>", "kgemm_k<0,4,4,true>", "kgemm_k<0,4,2,true>", "kgemm_k<0,4,1,true>"};
     g_last_kernel = a.nrm.scale ? ks_name(names_n, ks) : ks_name(names, ks);  // (as rocprofv3 prints the instantiation)
-    if (v2::g_pair_collect && ks.ks == 4 && !a.nrm.scale) {  // an input gradient with its layer's weight gradient to follow: stash it
-        g_kpend.active = true, g_kpend.form = 0, g_kpend.a = a, g_kpend.tiles = dim3(tx, ty, 1);
+    if (pair_collecting() && ks.ks == 4 && !a.nrm.scale) {  // an input gradient with its layer's weight gradient to follow: stash it
+        pair_stash(KDgrad{0, a, dim3(tx, ty, 1)});
         *handled = true;
         return MOVAE_OK;
     }
@@ -832,8 +819,8 @@ inline int launch_kbwd(const float* X, const float* W, float* Y, const Geom& g, 
     static const char* const names[4] = {"kgemm_k<1,8,8,false>", "kgemm_k<1,4,4,false>", "kgemm_k<1,4,2,false>", "kgemm_k<1,4,1,false>"};
     static const char* const names_n[4] = {"kgemm_k<1,8,8,true>", "kgemm_k<1,4,4,true>", "kgemm_k<1,4,2,true>", "kgemm_k<1,4,1,true>"};
     g_last_kernel = a.nrm.scale ? ks_name(names_n, ks) : ks_name(names, ks);
-    if (v2::g_pair_collect && ks.ks == 4 && !a.nrm.scale) {
-        g_kpend.active = true, g_kpend.form = 1, g_kpend.a = a, g_kpend.tiles = dim3(tx, ty, ncls);
+    if (pair_collecting() && ks.ks == 4 && !a.nrm.scale) {
+        pair_stash(KDgrad{1, a, dim3(tx, ty, ncls)});
         *handled = true;
         return MOVAE_OK;
     }
@@ -875,7 +862,7 @@ inline int launch_kwgrad(const float* Sm, const float* Bg, float* const* dW, int
     a.accumulate = accumulate, a.s_gs = s_gs, a.b_gs = b_gs, a.slab_stride = stride;
     for (int i = 0; i < 8; ++i) a.tab.p[i] = i < G ? dW[i] : nullptr;
     a.nrm = g_fuse.nrm, a.nrm_side = g_fuse.nrm_side;
-    if (int rc = v2::flush_pending(st)) return rc;  // (a stashed dgrad of the paired path goes first, on its own)
+    if (int rc = pair_flush(st)) return rc;  // (a stashed dgrad of the paired path goes first, on its own)
     const dim3 grid(ceil_div(ceil_div(M, 32), wt), N / 32, G * Sp);
     const int nside = a.nrm.scale ? a.nrm_side : 0;
 #define MOVAE_KW(NW_, KS_)                                                                               \

@@ -232,16 +232,9 @@ inline int launch_linear_bwd(const LinProb& d, const LinProb& w, hipStream_t st)
     return MOVAE_OK;
 }
 
-// a linear layer's input gradient planned inside a dgrad + wgrad call (v2::g_pair_collect), waiting for its weight gradient
-struct LinPending {
-    bool active = false;
-    LinProb d;
-};
-static thread_local LinPending g_lin_pend;
-inline int lin_flush(hipStream_t st) {  // the weight gradient took another kernel: the input gradient goes alone
-    if (!g_lin_pend.active) return MOVAE_OK;
-    g_lin_pend.active = false;
-    const LinProb& d = g_lin_pend.d;
+// a linear layer's input gradient that was planned inside a dgrad + wgrad call (pair.h) and whose weight gradient took another
+// kernel: it goes alone
+inline int launch_linear_dgrad(const LinProb& d, hipStream_t st) {
     hipLaunchKernelGGL((linear_small_k<1>), dim3(d.gx, d.gy, d.gz), dim3(256), 0, st, d.A, d.B, d.out, d.bias, d.M, d.N, d.K, d.act, d.slope,
                        d.a_gs, d.accumulate, d.pr);
     MOVAE_CHECK_LAUNCH("linear_small (unpaired input gradient)");
