@@ -673,6 +673,22 @@ int movae_vgg_prep_bwd(int g, const float* const* dy, const float* const* x, con
 int movae_maxpool2x2_fwd(const float* x, float* y, int n, int h, int w, int c, movae_stream_t stream);
 int movae_maxpool2x2_bwd(const float* dy, const float* x, const float* y, float* dx, int n, int h, int w, int c, movae_stream_t stream);
 
+/* ---- the feature distance of LPIPS (csrc/lpips.hip; utils/metrics.py:290-357 lpips) -------------------------------------------------
+ * movae_lpips_layer: f1, f2 contiguous fp32 NHWC [n][h][w][c], c % 4 == 0 (at most 1024), 16-byte aligned.  Per pixel
+ * sum_c (f1 / max(||f1||_2, 1e-12) - f2 / max(||f2||_2, 1e-12))^2 (F.normalize's rule: an all-zero pixel normalises to zeros), formed
+ * directly from the two normalised values -- identical operands give exactly 0.  Every element is read once; the arithmetic is fp64.
+ * partials (device, movae_lpips_ws_bytes(n, h, w, c) bytes, 8-byte aligned, plain scratch: carve it from a workspace BEHIND its
+ * 4096-byte header) receives, per image, the blocks' sums over their pixels times `scale` (a weight on the layer; 1 for the
+ * reference's plain mean).  A block never straddles two images.  One launch, no atomics, no memset.
+ * movae_lpips_finalize: one launch over the partials of `layers` (1..8) such calls with the same n (h, w, c: HOST arrays of the layers'
+ * geometry; partials: HOST array of the device pointers): per image the mean over the layers of (sum of the layer's partials) / (h w),
+ * out (device float[1 + n]) = [mean over the images, image 0, ..., image n - 1].  Fixed summation order: bit-identical between runs. */
+size_t movae_lpips_ws_bytes(int n, int h, int w, int c);
+int movae_lpips_layer(const float* f1, const float* f2, int n, int h, int w, int c, float scale, double* partials,
+                      size_t partials_bytes, movae_stream_t stream);
+int movae_lpips_finalize(int layers, const double* const* partials, const int* h, const int* w, const int* c, int n, float* out,
+                         movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,9 @@ SIGNATURES = {
     "movae_recon_metrics_ws_bytes": ([_i, _i, _i, _i], _z),
     "movae_recon_metrics": ([_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, C.c_longlong, C.c_longlong,
                              C.c_longlong, _i, _i, _i, _i, _i, _f, _p, _p, _z, _p], _i),
+    "movae_lpips_ws_bytes": ([_i, _i, _i, _i], _z),
+    "movae_lpips_layer": ([_p, _p, _i, _i, _i, _i, _f, _p, _z, _p], _i),
+    "movae_lpips_finalize": ([_i, _p, _p, _p, _p, _i, _p, _p], _i),
     "movae_bench_main_kernel_only": ([_i], _i),
     "movae_bench_last_kernel": ([], C.c_char_p),
     "movae_reduce_defer": ([_i], _i),
@@ -307,6 +310,7 @@ def stream_ptr(device=None):
 
 _workspaces = {}
 WS_BYTES = 96 << 20
+WS_HEADER_BYTES = 4096  # include/movae.h: the reserved, zero head of every workspace; plain scratch lies behind it
 
 
 def workspace(device, slot=0):

@@ -6,12 +6,17 @@
 C-ABI call (include/movae.h: movae_recon_metrics, three launches, no host read): the min-reduction that decides the
 normalisation, the fused SSIM / MSE / signal-variance pass, and a fixed-order finalize.
 
+`lpips` is the reference's utils/metrics.py:290-357 on VGG16 weights the caller registered (perceptual.use_vgg16_weights): the
+input normalisation and the feature stack of the perceptual loss, extended to relu4_3 (perceptual.LpipsFeatures), then one
+movae_lpips_layer per tapped layer and one movae_lpips_finalize (csrc/lpips.hip); `lpips_into` is the form without a host read.
+
 `ReconMetricAccumulator` is the collection of main.py:376-463 without the host copies: (real, recon) pairs are taken batch by
 batch up to `max_samples`, cut into the reference's 128-sample chunks (the chunks of the concatenated collection, so they
 straddle loader batches), and each chunk is scored on the device as soon as it is complete.  `result()` is the one host read.
 
 `build_hv_indicator` gives pymoo's HV for the single point the reference passes it, in closed form (pymoo is not needed).
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -98,6 +103,121 @@ def ssnr(img1, img2):
     return float(_run(img1, img2)[2].item())
 
 
+# ---- LPIPS ----------------------------------------------------------------------------------------------------------------
+LPIPS_MIN_SIDE = 8    # three 2x2 pools in front of conv4: the third needs a 2x2 input
+LPIPS_MIN_WIDTH = 32  # main.py:335 min_size_for_lpips, the final evaluation's gate on size(-1)
+_lpips_features = {}  # device -> (the registered 20-entry dict, the LpipsFeatures built from it)
+
+
+def _lpips_weights():
+    from . import perceptual
+
+    return perceptual.registered_vgg16_lpips_weights()
+
+
+def _features_on(device, weights):
+    """The feature extractor of this device, built once per registration (a new registration is a new dict object)."""
+    from . import perceptual
+
+    key = (device.type, device.index)
+    hit = _lpips_features.get(key)
+    if hit is None or hit[0] is not weights:
+        hit = (weights, perceptual.LpipsFeatures(weights, device=device))
+        _lpips_features[key] = hit
+    return hit[1]
+
+
+def _lpips_operand(t):
+    from . import ops
+
+    t = _operand(t)
+    if t.size(1) == 1:
+        t = t.expand(-1, 3, -1, -1)  # utils/metrics.py:271-272
+    if t.size(1) != 3:
+        raise ValueError(f"lpips takes images of 1 or 3 channels, got shape {tuple(t.shape)}")
+    return ops.to_nhwc(t).contiguous()
+
+
+def feature_distance_into(out, pairs):
+    """The distance part alone: `pairs` is a list (one entry per layer, at most 8) of two contiguous fp32 NHWC feature tensors
+    [n, h, w, c] with c % 4 == 0.  out (device float32[1 + n]) receives the mean over the layers of the pixel-averaged squared
+    distance between the channel-normalised features, as [mean over the images, per-image values]: one movae_lpips_layer per
+    pair and one movae_lpips_finalize, no host read."""
+    first = pairs[0][0]
+    L.require_gpu(first)
+    n, dev = first.size(0), first.device
+    for f1, f2 in pairs:
+        if not (f1.dim() == 4 and f1.shape == f2.shape and f1.size(0) == n and f1.dtype == f2.dtype == torch.float32
+                and f1.is_contiguous() and f2.is_contiguous() and f1.device == f2.device == dev):
+            raise ValueError(f"feature pairs must be contiguous float32 NHWC tensors of one shape and batch, got {tuple(f1.shape)} / "
+                             f"{tuple(f2.shape)}")
+    if out.numel() < 1 + n or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous float32 tensor of 1 + n elements on the features' device")
+    lib = L.load()
+    st = L.stream_ptr(dev)
+    # the partials of all layers, one region each, behind the workspace's header
+    sizes = [lib.movae_lpips_ws_bytes(*f.shape) for f, _ in pairs]
+    ws = _workspace(dev, L.WS_HEADER_BYTES + sum(sizes))
+    parts, at = [], ws.data_ptr() + L.WS_HEADER_BYTES
+    for (f1, f2), nbytes in zip(pairs, sizes):
+        L.call("movae_lpips_layer", f1.data_ptr(), f2.data_ptr(), *f1.shape, 1.0, at, nbytes, st)
+        parts.append(at)
+        at += nbytes
+    k = len(pairs)
+    ints = C.c_int * k
+    L.call("movae_lpips_finalize", k, (C.c_void_p * k)(*parts), *[ints(*[f.shape[d] for f, _ in pairs]) for d in (1, 2, 3)], n,
+           out.data_ptr(), st)
+    return out
+
+
+@torch.no_grad()
+def lpips_into(out, real, recon):
+    """One chunk of the reference's lpips (utils/metrics.py:290-357) on the device, without a host read: out (device
+    float32[1 + n]) receives [mean over the images, per-image values].  Both operands are normalised by vgg_prep's two launches
+    (each one's [-1, 1] decision over the whole operand) straight into the two halves of one [2 n, H, W, 3] buffer, the feature
+    stack runs once on the 2 n images, then one movae_lpips_layer per tap on the two halves of its features and one
+    movae_lpips_finalize."""
+    weights = _lpips_weights()
+    if weights is None:
+        raise RuntimeError("lpips needs VGG16 weights with the conv4 block (features.17 / 19 / 21): register them with "
+                           "perceptual.use_vgg16_weights(path or state_dict); nothing is downloaded")
+    if real.shape != recon.shape:
+        raise ValueError(f"image shapes differ: {tuple(real.shape)} vs {tuple(recon.shape)}")
+    if real.device != recon.device:
+        raise ValueError("real and recon must be on the same device")
+    if real.dim() == 4 and min(real.shape[2:]) < LPIPS_MIN_SIDE:
+        raise ValueError(f"lpips needs images of at least {LPIPS_MIN_SIDE} x {LPIPS_MIN_SIDE} (three 2x2 pools in front of conv4), "
+                         f"got {tuple(real.shape)}")
+    a, b = _lpips_operand(real), _lpips_operand(recon)
+    n, h, w, _ = a.shape
+    dev = a.device
+    lib = L.load()
+    st = L.stream_ptr(dev)
+    both = torch.empty((2 * n, h, w, 3), dtype=torch.float32, device=dev)
+    flags = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = _workspace(dev, lib.movae_vgg_prep_ws_bytes(2))
+    ptrs = C.c_void_p * 2
+    L.call("movae_vgg_prep_fwd", 2, ptrs(a.data_ptr(), b.data_ptr()), ptrs(both[:n].data_ptr(), both[n:].data_ptr()), flags.data_ptr(),
+           a.numel(), ws.data_ptr(), ws.numel(), st)
+    taps = _features_on(dev, weights)(both)
+    return feature_distance_into(out, [(f[:n], f[n:]) for f in taps])
+
+
+def lpips(img1, img2, device=None, net='vgg'):
+    """utils/metrics.py:290-357: the mean over the images of the mean over relu1_2, relu2_2, relu3_3, relu4_3 of the squared distance
+    between the channel-normalised VGG16 features, averaged over the pixels (Python float; NaN for an empty operand).  The weights
+    are the ones registered with perceptual.use_vgg16_weights (a torchvision vgg16 state_dict serves both the loss and this metric);
+    `device` moves the operands there first."""
+    if net != 'vgg':
+        raise ValueError(f"Network {net} not supported. Currently only 'vgg' is supported.")
+    if img1.numel() == 0 or img2.numel() == 0:
+        return float("nan")
+    if device is not None:
+        img1, img2 = img1.to(device), img2.to(device)
+    out = torch.empty(1 + img1.size(0), dtype=torch.float32, device=img1.device)
+    return float(lpips_into(out, img1, img2)[0].item())
+
+
 # ---- collection in the reference's chunks ------------------------------------------------------------------------------
 class ChunkPlanner:
     """Host-side bookkeeping of main.py:376-463 + :335-373: which samples of each loader batch are taken (the `take` cut at
@@ -133,10 +253,11 @@ def plan_chunks(batch_sizes, max_samples, chunk=CHUNK):
 
 
 class ReconMetricAccumulator:
-    """(real, recon) batches -> the reference's rFID / PSNR / SSIM / LPIPS dict (rFID and LPIPS need pretrained networks: NaN,
-    as the reference gives when it cannot load them).  At most one chunk is staged on the device (a chunk that lies inside
-    one batch is scored straight from the batch's tensors); every chunk is scored when it completes and its ssim / psnr stay
-    on the device until result()."""
+    """(real, recon) batches -> the reference's rFID / PSNR / SSIM / LPIPS dict.  rFID needs a pretrained Inception: NaN, as the
+    reference gives when it cannot load it.  LPIPS is scored per chunk (lpips_into) when VGG16 weights with the conv4 block are
+    registered (perceptual.use_vgg16_weights) and the images are at least 32 wide, the reference's min_size_for_lpips; else NaN.
+    At most one chunk is staged on the device (a chunk that lies inside one batch is scored straight from the batch's
+    tensors); every chunk is scored when it completes and its ssim / psnr / lpips stay on the device until result()."""
 
     def __init__(self, device, max_samples, chunk=CHUNK, window_size=11):
         _check_window(window_size)
@@ -146,6 +267,7 @@ class ReconMetricAccumulator:
         self._stage = None  # (real, recon) NCHW float32 [chunk, C, H, W]
         self._fill = 0
         self._outs = []
+        self._lpips = None
 
     @property
     def full(self):
@@ -156,7 +278,14 @@ class ReconMetricAccumulator:
         return self.planner.seen
 
     def _score(self, real, recon):
-        self._outs.append(_run(real, recon, self.window_size)[:2])
+        vals = _run(real, recon, self.window_size)[:2]
+        if self._lpips is None:  # decided once, at the first chunk: main.py:344, :357 gate on the width alone
+            self._lpips = (_lpips_weights() is not None and real.size(-1) >= LPIPS_MIN_WIDTH and real.size(-2) >= LPIPS_MIN_SIDE
+                           and real.size(1) in (1, 3))
+        if self._lpips:
+            lp = lpips_into(torch.empty(1 + real.size(0), dtype=torch.float32, device=real.device), real, recon)
+            vals = torch.cat([vals, lp[:1]])
+        self._outs.append(vals)
 
     @torch.no_grad()
     def add(self, real, recon):
@@ -180,8 +309,8 @@ class ReconMetricAccumulator:
         return take
 
     def result(self):
-        """Scores a partial last chunk, then reads every chunk's (ssim, psnr) with one host copy: the unweighted means over
-        chunks of main.py:367-370."""
+        """Scores a partial last chunk, then reads every chunk's (ssim, psnr[, lpips]) with one host copy: the unweighted means
+        over chunks of main.py:362-367."""
         if self._fill > 0:
             self._score(self._stage[0][: self._fill], self._stage[1][: self._fill])
             self._fill = 0
@@ -190,6 +319,8 @@ class ReconMetricAccumulator:
             vals = torch.stack(self._outs).cpu().double().numpy()
             out["ssim"] = float(np.mean(vals[:, 0]))
             out["psnr"] = float(np.mean(vals[:, 1]))
+            if vals.shape[1] > 2:
+                out["lpips"] = float(np.mean(vals[:, 2]))
         return out
 
 

@@ -2,8 +2,8 @@
 :1088-1497 (main) and :1500-1670 (argparse), restricted to what the per-step path needs.
 
 Differences that are by design: the step's device->host reads (losses, hook values) are
-batched into ONE copy per step instead of ~K+5 `.item()` syncs; evaluation metrics that need
-pretrained networks (FID/IS/LPIPS) and dataset downloads are out of scope -- `--dataset synthetic_*`
+batched into ONE copy per step instead of ~K+5 `.item()` syncs; evaluation metrics that need a
+pretrained Inception (FID/IS) and dataset downloads are out of scope -- `--dataset synthetic_*`
 provides seeded in-memory data of the right shape; with torchrun (WORLD_SIZE>1) the batch is sharded
 and the aggregated gradient is all-reduced once per step over RCCL.
 """
@@ -491,8 +491,8 @@ def evaluate(net, loader, device, args):
 def evaluate_with_recon_metrics(net, loader, device, args):
     """main.py:376-463: `evaluate`'s meters and the reconstruction metrics from ONE pass over the loader -> (meters,
     {'rfid', 'psnr', 'ssim', 'lpips'}).  The first `--max_fid_samples` (real, recon) pairs are scored in the reference's
-    128-sample chunks on the device (metrics.ReconMetricAccumulator) instead of being copied to the host; rFID and LPIPS
-    need pretrained networks and are NaN."""
+    128-sample chunks on the device (metrics.ReconMetricAccumulator) instead of being copied to the host; LPIPS is scored
+    there too when VGG16 weights with the conv4 block are registered (perceptual.use_vgg16_weights), else NaN; rFID is NaN."""
     acc = ReconMetricAccumulator(device, getattr(args, "max_fid_samples", 5000))
     meters = _eval_loop(net, loader, device, on_batch=lambda images, out: acc.add(images, out.get("recons")))
     return meters, acc.result()
