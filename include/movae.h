@@ -689,6 +689,17 @@ int movae_lpips_layer(const float* f1, const float* f2, int n, int h, int w, int
 int movae_lpips_finalize(int layers, const double* const* partials, const int* h, const int* w, const int* c, int n, float* out,
                          movae_stream_t stream);
 
+/* ---- batches from a device-resident uint8 image set (csrc/data.hip; the reference's RandomHorizontalFlip -> ToTensor -> Normalize) ----
+ * store: device uint8 [n][h][w][c], c in {1, 3}.  idx: device int[b], row numbers into store (the caller has range-checked them).
+ * lut: device float[c][256], the per-channel value of every byte.  out: device fp32 NHWC [b][h][w][c], 16-byte aligned.
+ * out[j][y][x][ch] = lut[ch][store[idx[j]][y][x'][ch]] with x' = x, or w - 1 - x where row idx[j] is flipped (channel order unchanged).
+ * With flip != 0, row i = idx[j] is flipped iff bit 31 of word 0 of Philox4x32-10 with counter (i low word, i high word, epoch low word,
+ * epoch high word) and key (seed low word, seed high word) is set: a function of (seed, epoch, i) alone.  Offsets into store are 64-bit.
+ * One launch, no atomics, no workspace; capturable.  Refused (MOVAE_EINVAL, nothing launched): a null pointer, b, h or w <= 0, c not in
+ * {1, 3}, a misaligned out. */
+int movae_batch_u8(const uint8_t* store, const int* idx, int b, int h, int w, int c, const float* lut, int flip,
+                   unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

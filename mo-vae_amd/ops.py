@@ -2450,6 +2450,23 @@ def vgg_prep(*xs):
     return out[0] if len(xs) == 1 else out
 
 
+def batch_u8(store, idx, lut, flip, seed, epoch):
+    """One batch from a device-resident uint8 image set (csrc/data.hip; data.DeviceBatchLoader): store uint8 [N][H][W][C], idx int32 [B]
+    row numbers into it (range-checked by the caller), lut float32 [C][256] -> a fresh fp32 NHWC [B][H][W][C] with
+    out[j] = lut[ch][store[idx[j]]], row idx[j] mirrored along W where the Philox bit of (seed, epoch, idx[j]) says so and `flip` is set.
+    One launch; not differentiable (a data source)."""
+    L.require_gpu(store)
+    assert store.dtype == torch.uint8 and store.dim() == 4 and store.is_contiguous(), "batch_u8: store is contiguous uint8 [N][H][W][C]"
+    _, h, w, c = store.shape
+    assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous() and idx.device == store.device, "batch_u8: idx is int32 [B]"
+    assert lut.dtype == torch.float32 and tuple(lut.shape) == (c, 256) and lut.is_contiguous() and lut.device == store.device, \
+        f"batch_u8: lut is float32 [{c}][256]"
+    out = torch.empty((idx.numel(), h, w, c), dtype=torch.float32, device=store.device)
+    _call("movae_batch_u8", store.data_ptr(), idx.data_ptr(), idx.numel(), h, w, c, lut.data_ptr(), int(bool(flip)), int(seed), int(epoch),
+          out.data_ptr(), _st(store))
+    return out
+
+
 class MaxPool2x2(Function):
     """nn.MaxPool2d(kernel_size=2, stride=2) (floor mode) on NHWC [N, H, W, C], C % 4 == 0.  The backward writes every element of dx
     in one launch: dy to the first maximum of each window in scan order (torch's tie rule), zeros elsewhere and in the row / column

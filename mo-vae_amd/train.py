@@ -3,7 +3,8 @@
 
 Differences that are by design: the step's device->host reads (losses, hook values) are
 batched into ONE copy per step instead of ~K+5 `.item()` syncs; evaluation metrics that need a
-pretrained Inception (FID/IS) and dataset downloads are out of scope -- `--dataset synthetic_*`
+pretrained Inception (FID/IS) and dataset downloads are out of scope -- the reference's datasets are
+read from files already on disk and held on the device as uint8 (data.py), `--dataset synthetic_*`
 provides seeded in-memory data of the right shape; with torchrun (WORLD_SIZE>1) the batch is sharded
 and the aggregated gradient is all-reduced once per step over RCCL.
 """
@@ -21,6 +22,7 @@ from . import aggregation
 from . import autojac
 from . import ops
 from .aggregation import COMFORT, MGDA
+from .data import ALIASES, NPY_SETS, DeviceBatchLoader, ResidentImages, get_real_dataset
 from .metrics import ReconMetricAccumulator, build_hv_indicator
 from .models import get_network
 from .optim import FusedAdam, FusedAdamW, clip_grad_norm_
@@ -542,16 +544,44 @@ class SyntheticImages(torch.utils.data.Dataset):
 
 
 def get_dataset(name, data_dir="./data", normalize=False, max_items=None):
-    """utils/utils.py:144-426 for real datasets needs torchvision / HF `datasets` downloads, which are
-    unavailable offline; synthetic_* names give shape-compatible data."""
+    """utils/utils.py:144-426 -> (train set, test set, image side).  The reference's names (case-insensitive) are read from files
+    already under `data_dir` as uint8 sets (data.get_real_dataset: nothing is downloaded; imagenet and oxford-flower-102 are refused,
+    with the reason); synthetic_* names give seeded shape-compatible data."""
     key = name.lower()
     if key in SYNTHETIC:
         size, n = SYNTHETIC[key]
         n = min(n, max_items) if max_items else n
         return SyntheticImages(n, size, 0, normalize), SyntheticImages(max(1, n // 10), size, 1, normalize), size
+    real = get_real_dataset(name, data_dir=data_dir, normalize=normalize, max_items=max_items)
+    if real is not None:
+        return real
     raise NotImplementedError(
-        f"dataset {name!r}: real datasets are fetched over the network by the reference (torchvision / HF hub) and are "
-        f"outside the hot path; use one of {sorted(SYNTHETIC)}")
+        f"dataset {name!r} is not known; use one of {sorted(['cifar10', 'cifar100', *NPY_SETS, *ALIASES])} (read from --data_dir) or "
+        f"{sorted(SYNTHETIC)}")
+
+
+def make_loader(ds, batch_size, device, args, shuffle, sampler=None, dp=None):
+    """The loader of one stage.  `--data_loader auto` (default): a ResidentImages set gets the device loader (data.DeviceBatchLoader:
+    the set in HBM, one launch per batch), anything else the DataLoader this build always used; `host` forces the DataLoader, `device`
+    insists on the device loader.  `dp` (with the device loader) / `sampler` (with the DataLoader) shard a training set over the ranks."""
+    if uses_device_loader(ds, args):
+        rank, world = (dp.rank, dp.world_size) if dp is not None else (0, 1)
+        return DeviceBatchLoader(ds, batch_size, device, shuffle, rank=rank, world_size=world, seed=args.seed or 0)
+    # pinning in the main thread (num_workers == 0) allocates and frees page-locked memory per batch: ~20 ms per batch on ROCm.
+    # A ResidentImages set gets fresh workers per epoch: a worker holds a COPY of the set, taken when it starts, and persistent
+    # workers would keep the epoch of that moment -- every later epoch would repeat its flips
+    persistent = args.num_workers > 0 and not isinstance(ds, ResidentImages)
+    kw = dict(num_workers=args.num_workers, pin_memory=args.num_workers > 0, drop_last=False, persistent_workers=persistent)
+    return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=shuffle and sampler is None, sampler=sampler, **kw)
+
+
+def uses_device_loader(ds, args):
+    """Whether make_loader gives `ds` the device loader under `--data_loader` (ValueError: `device` asked for a set with no uint8 form)."""
+    mode = getattr(args, "data_loader", "auto")
+    resident = isinstance(ds, ResidentImages)
+    if mode == "device" and not resident:
+        raise ValueError(f"--data_loader device needs a dataset held as uint8 images; {type(ds).__name__} is generated on the host")
+    return resident and mode in ("auto", "device")
 
 
 # ---- CLI -----------------------------------------------------------------------------------------
@@ -660,7 +690,11 @@ def build_parser():
                    help="fp32 (default): the reference's arithmetic, the parity path.  bf16 (opt-in): bf16 operands / fp32 "
                         "accumulation in the 128x128 implicit-GEMM convolution kernels (the MFMA-bound layers of the 64x64+ "
                         "configurations); master weights, BatchNorm, losses, aggregation and optimizer stay fp32")
-    p.add_argument("--max_items", type=int, default=None, help="cap the synthetic dataset length")
+    p.add_argument("--data_loader", choices=["auto", "device", "host"], default="auto",
+                   help="auto (default): a real image set is kept on the device as uint8 and each batch is assembled there by one "
+                        "kernel (gather, flip, ToTensor / Normalize); synthetic sets keep the host DataLoader.  host: the DataLoader "
+                        "for every set (a set too large for the device).  device: refuse a set that has no uint8 form")
+    p.add_argument("--max_items", type=int, default=None, help="cap the dataset length (test set: a tenth of it)")
     p.add_argument("--max_steps", type=int, default=None, help="stop after this many optimisation steps")
     return p
 
@@ -726,14 +760,14 @@ def main(args):
                                                 max_items=args.max_items)
     per_rank_bs = args.batch_size if dp is None else max(1, args.batch_size // dp.world_size)
     sampler = None
-    if dp is not None:
+    if dp is not None and not uses_device_loader(train_ds, args):  # (the device loader shards by the same rule itself)
         sampler = torch.utils.data.distributed.DistributedSampler(train_ds, num_replicas=dp.world_size, rank=dp.rank,
                                                                   shuffle=True, seed=args.seed or 0)
-    # pinning in the main thread (num_workers == 0) allocates and frees page-locked memory per batch: ~20 ms per batch on ROCm
-    loader_kw = dict(num_workers=args.num_workers, pin_memory=args.num_workers > 0, drop_last=False,
-                     persistent_workers=args.num_workers > 0)
-    train_loader = torch.utils.data.DataLoader(train_ds, batch_size=per_rank_bs, shuffle=sampler is None, sampler=sampler, **loader_kw)
-    test_loader = torch.utils.data.DataLoader(test_ds, batch_size=per_rank_bs, shuffle=False, **loader_kw)
+    for ds in (train_ds, test_ds):
+        if isinstance(ds, ResidentImages):
+            ds.seed = args.seed or 0  # the flips follow --seed, on the device and on the host alike
+    train_loader = make_loader(train_ds, per_rank_bs, device, args, shuffle=True, sampler=sampler, dp=dp)
+    test_loader = make_loader(test_ds, per_rank_bs, device, args, shuffle=False)
     args.dataset_size = len(train_ds)
     net = get_network(input_size, num_channels=3, args=args, device=device).to(device)
     args.total_params = net.total_trainable_params()
@@ -782,6 +816,10 @@ def main(args):
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
+        if isinstance(train_loader, DeviceBatchLoader):
+            train_loader.set_epoch(epoch)  # the epoch's shuffle and flips
+        elif isinstance(train_ds, ResidentImages):
+            train_ds.set_epoch(epoch)  # the host path's flips (its order is the DataLoader's / the sampler's)
         if isinstance(aggregator, COMFORT):  # main.py:1290-1291
             aggregator.set_epoch(epoch, args.epochs)
         t0 = time.time()
@@ -829,7 +867,7 @@ def main(args):
         # the training loader is a DistributedSampler shard at the per-rank batch size, so rank 0 builds a plain loader of its own.
         prior_loader = train_loader
         if dp is not None:
-            prior_loader = torch.utils.data.DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, **loader_kw)
+            prior_loader = make_loader(train_ds, args.batch_size, device, args, shuffle=True)
         _prior.train_pixelcnn_prior(net, prior_loader, device, args, save_root)
     if rank0 and getattr(args, "max_fid_samples", 0) > 0:  # main.py:1457-1470, after the prior stage like the reference
         final_meters, recon = evaluate_with_recon_metrics(net, test_loader, device, args)

@@ -1,0 +1,88 @@
+"""Image folder -> the uint8 .npy sets that train.get_dataset reads (<name>_train_u8.npy / <name>_test_u8.npy, [N][S][S][3]).
+
+    python tools/prepare_images.py --src img_align_celeba --out data --name celeba --size 64 --center_crop 148 --split 0.9
+
+Per image: RGB, an optional centre crop, then Image.resize((S, S), Image.BICUBIC) -- what the reference's CenterCrop + Resize(BICUBIC,
+antialias=True) do to a PIL image (utils/utils.py:262-274).  Files are taken in sorted order.  --split F sends the first F of them to
+the train file and the rest to the test file; --split_list FILE names the TRAIN files, one per line (the others are the test set).
+Pure host code; nothing is downloaded."""
+import argparse
+import os
+
+import numpy as np
+from PIL import Image
+
+EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".webp")
+
+
+def load_image(path, size, center_crop=None):
+    """-> uint8 [size][size][3]."""
+    img = Image.open(path).convert("RGB")
+    if center_crop:
+        w, h = img.size
+        # torchvision's CenterCrop: the window's corner is round((side - crop) / 2) (transforms/functional.py: center_crop)
+        left, top = int(round((w - center_crop) / 2.0)), int(round((h - center_crop) / 2.0))
+        img = img.crop((left, top, left + center_crop, top + center_crop))
+    return np.asarray(img.resize((size, size), Image.BICUBIC), dtype=np.uint8)
+
+
+def list_images(src):
+    return sorted(f for f in os.listdir(src) if f.lower().endswith(EXTENSIONS))
+
+
+def split_names(names, split=None, split_list=None):
+    """-> (train names, test names), each in sorted order."""
+    if split_list is not None:
+        chosen = set(split_list)
+        missing = sorted(chosen - set(names))
+        if missing:
+            raise ValueError(f"{len(missing)} names of the split list are not in the folder, e.g. {missing[:3]}")
+        return [n for n in names if n in chosen], [n for n in names if n not in chosen]
+    if split is None:
+        return list(names), []
+    if not 0.0 < split <= 1.0:
+        raise ValueError(f"--split is the train fraction in (0, 1], got {split}")
+    k = int(len(names) * split)
+    return names[:k], names[k:]
+
+
+def convert(src, out, name, size, center_crop=None, split=None, split_list=None):
+    """Writes <out>/<name>_train_u8.npy and, when the split leaves any, <out>/<name>_test_u8.npy.  -> the paths written."""
+    names = list_images(src)
+    if not names:
+        raise FileNotFoundError(f"no images ({', '.join(EXTENSIONS)}) in {src}")
+    os.makedirs(out, exist_ok=True)
+    written = []
+    for part, chosen in zip(("train", "test"), split_names(names, split, split_list)):
+        if not chosen:
+            continue
+        path = os.path.join(out, f"{name}_{part}_u8.npy")
+        arr = np.lib.format.open_memmap(path, mode="w+", dtype=np.uint8, shape=(len(chosen), size, size, 3))
+        for i, n in enumerate(chosen):
+            arr[i] = load_image(os.path.join(src, n), size, center_crop)
+        arr.flush()
+        del arr
+        written.append(path)
+    return written
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--src", required=True, help="folder of images")
+    p.add_argument("--out", required=True, help="the --data_dir of training")
+    p.add_argument("--name", required=True, help="celeba | celeba-128 | celeba-hq | afhq")
+    p.add_argument("--size", type=int, required=True, help="S: 64 / 128 / 256")
+    p.add_argument("--center_crop", type=int, default=None, help="148 (celeba), 178 (celeba-128)")
+    p.add_argument("--split", type=float, default=None, help="fraction of the sorted files that goes to the train file")
+    p.add_argument("--split_list", type=str, default=None, help="text file naming the train files, one per line")
+    a = p.parse_args(argv)
+    listed = None
+    if a.split_list:
+        with open(a.split_list) as f:
+            listed = [line.strip() for line in f if line.strip()]
+    for path in convert(a.src, a.out, a.name, a.size, a.center_crop, a.split, listed):
+        print(path)
+
+
+if __name__ == "__main__":
+    main()
