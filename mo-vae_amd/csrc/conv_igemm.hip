@@ -1210,16 +1210,16 @@ int launch_fwd(const float* X, const float* W, float* Y, const Geom& g_in, const
     }
     if (thin::thin_in_ok(g)) {
         MOVAE_NO_NORM("thin-channel input conv");
-        return (g_last_kernel = "thin_in_k<fwd>", thin::launch_thin_in<false>(X, W, Y, g, ep, st));
+        return thin::launch_thin_in<false>(X, W, Y, g, ep, st);
     }
     if (g.Nn <= 4) {  // 3-channel output: LDS-tiled direct kernel (applies the fused input transform while staging)
         bool handled = false;
         if (int rc = thin::launch_thin_out_tile<false>(X, W, Y, g, ep, st, &handled)) return rc;
-        if (handled) return (g_last_kernel = "thin_out_tile_k<fwd>", MOVAE_OK);
+        if (handled) return MOVAE_OK;
     }
     if (thin::thin_out_ok(g, X)) {
         MOVAE_NO_NORM("thin-channel output conv");
-        return (g_last_kernel = "thin_out_fwd_k", thin::launch_thin_out_fwd(X, W, Y, g, ep, st));
+        return thin::launch_thin_out_fwd(X, W, Y, g, ep, st);
     }
     // fast path (igemm_v2.h); its 32-bit buffer offsets need every row block's images and the weights within 2 GiB of their bases
     const bool span_ok = v2::buf_span_ok((128L / ((long)g.Ho * g.Wo) + 2) * g.Hi * g.Wi * g.Cr) &&
@@ -1288,12 +1288,12 @@ int launch_bwd(const float* X, const float* W, float* Y, const Geom& g, const Ep
     }
     if (thin::thin_in_ok(g)) {
         MOVAE_NO_NORM("thin-channel input (bwd form)");
-        return (g_last_kernel = "thin_in_k<bwd>", thin::launch_thin_in<true>(X, W, Y, g, ep, st));
+        return thin::launch_thin_in<true>(X, W, Y, g, ep, st);
     }
     if (g.Nn <= 4) {  // 3-channel output of a transposed conv: LDS-tiled direct kernel
         bool handled = false;
         if (int rc = thin::launch_thin_out_tile<true>(X, W, Y, g, ep, st, &handled)) return rc;
-        if (handled) return (g_last_kernel = "thin_out_tile_k<bwd>", MOVAE_OK);
+        if (handled) return MOVAE_OK;
     }
     // fast path (igemm_v2.h); 32-bit buffer offsets: a row block's images (smallest output-parity class) and the weights within 2 GiB
     const long hwc_min = (long)(g.Ho / g.stride > 0 ? g.Ho / g.stride : 1) * (g.Wo / g.stride > 0 ? g.Wo / g.stride : 1);
@@ -1355,7 +1355,7 @@ int launch_wgrad1(const float* S, const float* Bg, float* dW, const WGeom& g, in
     const long Kl = (long)g.Nimg * g.Hs * g.Ws;
     const int vec = ((g.Cs % 4 == 0 && aligned16(S)) ? 1 : 0) | ((g.Cb % 4 == 0 && aligned16(Bg)) ? 2 : 0);
     const int N = g.KH * g.KW * g.Cb;
-    if (thin::thin_wgrad_ok(g) && ws) return (g_last_kernel = "thin_wgrad", thin::launch_thin_wgrad(S, Bg, dW, g, (int)Kl, accumulate, ws, ws_bytes, st));
+    if (thin::thin_wgrad_ok(g) && ws) return thin::launch_thin_wgrad(S, Bg, dW, g, (int)Kl, accumulate, ws, ws_bytes, st);
     if (N <= 32) return (g_last_kernel = "igemm_wgrad<128,32>", launch_wgrad_t<128, 32>(S, Bg, dW, g, (int)Kl, vec, accumulate, ws, ws_bytes, st));
     return (g_last_kernel = "igemm_wgrad<64,64>", launch_wgrad_t<64, 64>(S, Bg, dW, g, (int)Kl, vec, accumulate, ws, ws_bytes, st));
 }
@@ -1417,8 +1417,7 @@ int launch_wgrad(const float* S, const float* Bg, float* const* dW, int G, long 
         return (g_last_kernel = "igemm2_wgrad<64,64>", launch_wgrad2<64, 64>(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, cs));
     }
     if (thin::thin_wgrad_ok(g) && ws)
-        return (g_last_kernel = "thin_wgrad",
-                thin::launch_thin_wgrad_grouped(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, colsum_S, colsum_done));
+        return thin::launch_thin_wgrad_grouped(S, Bg, dW, G, s_gs, b_gs, g, (int)Kl, accumulate, ws, ws_bytes, st, colsum_S, colsum_done);
     MOVAE_NO_NORM("generic wgrad");
     for (int i = 0; i < G; ++i)
         if (int rc = launch_wgrad1(S + i * s_gs, Bg + i * b_gs, dW[i], g, accumulate, ws, ws_bytes, st)) return rc;

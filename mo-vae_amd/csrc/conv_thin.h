@@ -1238,6 +1238,8 @@ int launch_thin_in(const float* X, const float* W, float* Y, const Geom& g, cons
                        fastdiv_make(g.Wo))
         if (k33) MOVAE_TI(3); else MOVAE_TI(4);
 #undef MOVAE_TI
+        g_last_kernel = k33 ? (BWD ? "thin_in_mfma_k<3,3,true>" : "thin_in_mfma_k<3,3,false>")
+                            : (BWD ? "thin_in_mfma_k<4,4,true>" : "thin_in_mfma_k<4,4,false>");
         MOVAE_CHECK_LAUNCH("thin_in_mfma");
         return MOVAE_OK;
     }
@@ -1245,11 +1247,13 @@ int launch_thin_in(const float* X, const float* W, float* Y, const Geom& g, cons
         grid.y = ceil_div(g.Nn, 64);
         hipLaunchKernelGGL((thin_in_k<64, BWD>), grid, dim3(256), (size_t)K * 64 * sizeof(float), st, X, W, ep.bias, Y, g, M,
                            ep.act, ep.slope, (float*)nullptr, BnBwd{}, ActMul{nullptr, 0, 0.f, 0, 0, nullptr});
+        g_last_kernel = BWD ? "thin_in_k<64,true>" : "thin_in_k<64,false>";
     } else {
         size_t lds_floats = (size_t)K * 32;
         if (n32 && lds_floats < 256 * 33) lds_floats = 256 * 33;  // room for the coalescing transpose of the outputs
         hipLaunchKernelGGL((thin_in_k<32, BWD>), grid, dim3(256), lds_floats * sizeof(float), st, X, W, ep.bias, Y, g, M,
                            ep.act, ep.slope, stats, bb, am);
+        g_last_kernel = BWD ? "thin_in_k<32,true>" : "thin_in_k<32,false>";
     }
     MOVAE_CHECK_LAUNCH("thin_in");
     return MOVAE_OK;
@@ -1264,6 +1268,7 @@ int launch_thin_out_fwd(const float* X, const float* W, float* Y, const Geom& g,
     const int M = g.Nimg * g.Ho * g.Wo, K = g.KH * g.KW * g.Cr;
     hipLaunchKernelGGL((thin_out_fwd_k<4>), dim3(ceil_div(M, 256)), dim3(256), (size_t)4 * K * sizeof(float), st, X, W, ep.bias,
                        Y, g, M, ep.act, ep.slope);
+    g_last_kernel = "thin_out_fwd_k<4>";
     MOVAE_CHECK_LAUNCH("thin_out_fwd");
     return MOVAE_OK;
 }
@@ -1315,6 +1320,7 @@ int launch_thin_out_tile(const float* X, const float* W, float* Y, const Geom& g
             else
                 hipLaunchKernelGGL((thin_out_mfma_k<3, 3, false>), dim3((unsigned)nblk), dim3(256), (size_t)NG * 32 * 27 * sizeof(float), st,
                                    X, W, ep.bias, Y, g, tiles_h, tiles_w, ep.act, ep.slope, g_fuse.nrm);
+            g_last_kernel = g.Cr == 32 ? "thin_out_mfma_k<3,3,true>" : "thin_out_mfma_k<3,3,false>";
             MOVAE_CHECK_LAUNCH("thin_out_mfma");
             *handled = true;
             return MOVAE_OK;
@@ -1330,6 +1336,7 @@ int launch_thin_out_tile(const float* X, const float* W, float* Y, const Geom& g
         if (nblk <= 0x7fffffffL && shb <= 80 * 1024) {
             hipLaunchKernelGGL(thin_outT_mfma_k, dim3((unsigned)nblk), dim3(256), shb, st, X, W, ep.bias, Y, g, tiles_h, tiles_w, ep.act,
                                ep.slope, g_fuse.nrm);
+            g_last_kernel = "thin_outT_mfma_k";
             MOVAE_CHECK_LAUNCH("thin_outT_mfma");
             *handled = true;
             return MOVAE_OK;
@@ -1345,9 +1352,13 @@ int launch_thin_out_tile(const float* X, const float* W, float* Y, const Geom& g
         return MOVAE_OK;
     }
     const size_t shb = ((size_t)IH * IW * (CC + 4) + (size_t)g.KH * g.KW * 4 * CC) * sizeof(float);
-#define MOVAE_TO(CCV, PPTV)                                                                                                      \
-    hipLaunchKernelGGL((thin_out_tile_k<BWD, CCV, PPTV>), dim3((unsigned)nblk), dim3(256), shb, st, X, W, ep.bias, Y, g, TH, TW, tiles_h, \
-                       tiles_w, IH, IW, ep.act, ep.slope, g_fuse.nrm)
+    // (the names as rocprofv3 prints the instantiations: <BWD,CC,PPT>)
+#define MOVAE_TO(CCV, PPTV)                                                                                                                            \
+    do {                                                                                                                                               \
+        hipLaunchKernelGGL((thin_out_tile_k<BWD, CCV, PPTV>), dim3((unsigned)nblk), dim3(256), shb, st, X, W, ep.bias, Y, g, TH, TW, tiles_h,          \
+                           tiles_w, IH, IW, ep.act, ep.slope, g_fuse.nrm);                                                                             \
+        g_last_kernel = BWD ? "thin_out_tile_k<true," #CCV "," #PPTV ">" : "thin_out_tile_k<false," #CCV "," #PPTV ">";                                \
+    } while (0)
     if (CC == 32) {
         if (PPT == 2) MOVAE_TO(32, 2); else MOVAE_TO(32, 1);
     } else {
@@ -1447,13 +1458,19 @@ int launch_thin_wgrad_impl(const float* S, const float* Bg, float* const* dW, in
                     }
                     wide_nrm = g_fuse.nrm;
                 }
-#define MOVAE_SW(K, REVV)                                                                                                      \
-    hipLaunchKernelGGL((thin_wgrad_sweep_k<3, K, K, REVV>), grid, dim3(256), shb, st, Wd, Tn, slab, Hw, Ww, wide, Ht, Wt, g.stride, \
-                       g.pad, TH, TW, tiles_h, tiles_w, g.Cs, g.Cb, wide_gs, thin_gs, slab_gs, wide_nrm)
-#define MOVAE_MF(K, REVV)                                                                                                      \
-    hipLaunchKernelGGL((thin_wgrad_mfma_k<3, K, K, REVV>), grid, dim3(256), shb, st, Wd, Tn, slab, Hw, Ww, wide, Ht, Wt, g.stride, \
-                       g.pad, TH, TW, tiles_h, tiles_w, g.Cs, g.Cb, wide_gs, thin_gs, slab_gs, wide_nrm, (int)ntiles, fastdiv_make(TW),    \
-                       fastdiv_make(thin_small ? TW + g.KW - 1 : (TW - 1) * g.stride + g.KW), cs_on ? 1 : 0, row)
+#define MOVAE_SW(K, REVV)                                                                                                                              \
+    do {                                                                                                                                               \
+        hipLaunchKernelGGL((thin_wgrad_sweep_k<3, K, K, REVV>), grid, dim3(256), shb, st, Wd, Tn, slab, Hw, Ww, wide, Ht, Wt, g.stride,                \
+                           g.pad, TH, TW, tiles_h, tiles_w, g.Cs, g.Cb, wide_gs, thin_gs, slab_gs, wide_nrm);                                          \
+        g_last_kernel = "thin_wgrad_sweep_k<3," #K "," #K "," #REVV ">";                                                                               \
+    } while (0)
+#define MOVAE_MF(K, REVV)                                                                                                                              \
+    do {                                                                                                                                               \
+        hipLaunchKernelGGL((thin_wgrad_mfma_k<3, K, K, REVV>), grid, dim3(256), shb, st, Wd, Tn, slab, Hw, Ww, wide, Ht, Wt, g.stride,                 \
+                           g.pad, TH, TW, tiles_h, tiles_w, g.Cs, g.Cb, wide_gs, thin_gs, slab_gs, wide_nrm, (int)ntiles, fastdiv_make(TW),            \
+                           fastdiv_make(thin_small ? TW + g.KW - 1 : (TW - 1) * g.stride + g.KW), cs_on ? 1 : 0, row);                                 \
+        g_last_kernel = "thin_wgrad_mfma_k<3," #K "," #K "," #REVV ">";                                                                                \
+    } while (0)
                 if (use_mfma) {
                     if (thin_small) {
                         if (k33) MOVAE_MF(3, true); else MOVAE_MF(4, true);
@@ -1527,9 +1544,12 @@ int launch_thin_wgrad(const float* S, const float* Bg, float* dW, const WGeom& g
             float* slab = static_cast<float*>(ws);
             const size_t shb = (size_t)lds_floats(TH, TW) * sizeof(float);
             const int tc = thin_small ? g.Cs : g.Cb;
-#define MOVAE_TW(SM, TCV)                                                                                               \
-    hipLaunchKernelGGL((thin_wgrad_tiled_k<SM, TCV>), dim3((unsigned)nblk), dim3(nth), shb, st, S, Bg, slab, g, TH, TW, \
-                       tiles_h, tiles_w)
+#define MOVAE_TW(SM, TCV)                                                                                                                              \
+    do {                                                                                                                                               \
+        hipLaunchKernelGGL((thin_wgrad_tiled_k<SM, TCV>), dim3((unsigned)nblk), dim3(nth), shb, st, S, Bg, slab, g, TH, TW,                            \
+                           tiles_h, tiles_w);                                                                                                          \
+        g_last_kernel = "thin_wgrad_tiled_k<" #SM "," #TCV ">";                                                                                        \
+    } while (0)
             if (thin_small) {
                 if (tc == 1) MOVAE_TW(true, 1); else if (tc == 2) MOVAE_TW(true, 2); else if (tc == 3) MOVAE_TW(true, 3); else MOVAE_TW(true, 4);
             } else {
@@ -1559,7 +1579,8 @@ int launch_thin_wgrad(const float* S, const float* Bg, float* dW, const WGeom& g
         hipLaunchKernelGGL((thin_wgrad_k<true>), grid, dim3(256), 0, st, S, Bg, slab, g, K, chunk, WL);
     else
         hipLaunchKernelGGL((thin_wgrad_k<false>), grid, dim3(256), 0, st, S, Bg, slab, g, K, chunk, WL);
-    MOVAE_CHECK_LAUNCH("thin_wgrad");
+    g_last_kernel = thin_small ? "thin_wgrad_k<true>" : "thin_wgrad_k<false>";
+    MOVAE_CHECK_LAUNCH("thin_wgrad_k");
     return launch_reduce(slab, dW, (long)M * N, nch, N, nullptr, 0, 0.f, accumulate, st);
 }
 

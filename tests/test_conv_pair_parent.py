@@ -2,7 +2,10 @@
 the side-product plan, the entry-point bodies) was consolidated: tests/golden/conv_pair_parent.json, written by
 tests/golden/record_conv_pair.py from that build on an MI355X.  Only host code changed, the kernels fold in a fixed order and use no
 float atomics, so every recorded field -- the kernel the call dispatched to, what the fuse struct reports back, the deferred-reduce
-counters and the SHA-256 of every result -- must come out the same.  GPU only."""
+counters and the SHA-256 of every result -- must come out the same.  The twelve records of the first conv (3 -> 32, 3x3, stride 2)
+had their kernel field respelled from the two per-dispatch-site labels of the thin-channel family to the launched instantiations,
+"thin_out_tile_k<true,32,1> + thin_wgrad_mfma_k<3,3,3,false>", when movae_bench_last_kernel() began to name those (one label used
+to cover several kernels there); nothing else in the recording changed.  GPU only."""
 import importlib.util
 import json
 import os

@@ -45,8 +45,8 @@ CASES = {
 
 
 class Geo:
-    def __init__(self, name):
-        c = CASES[name]
+    def __init__(self, name, case=None):
+        c = CASES[name] if case is None else case  # (case: a geometry of another file's, under that file's name for it)
         self.name, self.tr = name, len(c) == 9
         self.n, self.hi, self.wi, self.ci, self.co, self.k, self.s, self.p = c[:8]
         if self.tr:
@@ -310,11 +310,12 @@ class Scratch:
         return 0 if written.numel() == 0 else -(-(int(written[-1]) + 1) // per_slab)
 
 
-def fuse_of(L, nrm, dev):
+def fuse_of(L, nrm, dev, f=None):
+    """f: a movae_fuse_t of the caller's with further requests, which gets the transform added."""
     if nrm is None:
-        return None, ()
+        return f, ()
     sc, sh = nrm[0].to(dev), nrm[1].to(dev)
-    f = L.MovaeFuse()
+    f = f or L.MovaeFuse()
     f.in_scale, f.in_shift, f.in_slope = sc.data_ptr(), sh.data_ptr(), nrm[2]
     return f, (sc, sh)
 
@@ -323,13 +324,14 @@ def last(lib):
     return lib.movae_bench_last_kernel().decode()
 
 
-def run_fwd(L, lib, dev, g, x, w, b, expect, nrm=None, act=True, ws=None):
-    xd, wd, bd = x.to(dev), w.to(dev), b.to(dev)
+def run_fwd(L, lib, dev, g, x, w, b, expect, nrm=None, act=True, ws=None, fuse=None):
+    """b None: no bias.  fuse: a movae_fuse_t with side-product requests (the caller reads its out fields afterwards)."""
+    xd, wd, bd = x.to(dev), w.to(dev), None if b is None else b.to(dev)
     y = Out((g.n, g.ho, g.wo, g.co), dev)
     ws, st = ws or L.workspace(dev), torch.cuda.current_stream().cuda_stream
-    f, keep = fuse_of(L, nrm, dev)
+    f, keep = fuse_of(L, nrm, dev, fuse)
     pre = "movae_convT2d_fwd" if g.tr else "movae_conv2d_fwd"
-    head = (xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.ptr(), *g.args(), LRELU if act else 0, SLOPE, ws.data_ptr(), ws.numel(), st)
+    head = (xd.data_ptr(), wd.data_ptr(), None if bd is None else bd.data_ptr(), y.ptr(), *g.args(), LRELU if act else 0, SLOPE, ws.data_ptr(), ws.numel(), st)
     if f is None:
         L.call(pre, *head)
     else:
@@ -338,16 +340,16 @@ def run_fwd(L, lib, dev, g, x, w, b, expect, nrm=None, act=True, ws=None):
     return y.get(f"{g.name} forward")
 
 
-def run_dgrad(L, lib, dev, g, dy, w, expect, groups=1, ws=None):
+def run_dgrad(L, lib, dev, g, dy, w, expect, groups=1, ws=None, fuse=None):
     dyd, wd = dy.to(dev), w.to(dev)
     dx = Out((groups * g.n, g.hi, g.wi, g.ci), dev)
     ws, st = ws or L.workspace(dev), torch.cuda.current_stream().cuda_stream
     pre = "movae_convT2d_dgrad" if g.tr else "movae_conv2d_dgrad"
     head = (dyd.data_ptr(), wd.data_ptr(), dx.ptr(), *g.args(groups), ws.data_ptr(), ws.numel(), st)
-    if groups == 1:
+    if groups == 1 and fuse is None:
         L.call(pre, *head)
     else:
-        L.call(pre + "_f", *head, None, groups)
+        L.call(pre + "_f", *head, None if fuse is None else C.byref(fuse), groups)
     assert last(lib) == expect
     return dx.get(f"{g.name} input gradient")
 
