@@ -416,6 +416,11 @@ int movae_bench_main_kernel_only(int on);
 /* name (as rocprofv3 prints it, without the argument list) of the main kernel the most recent conv-family call
  * on this process dispatched to, e.g. "igemm2_bwd<64,64>" -- lets bench.py group its HIP-event timings per kernel */
 const char* movae_bench_last_kernel(void);
+/* names of the split-K reduce kernels the conv family chose since the previous read (a parked reduce is named when it is
+ * parked), joined with " + " in launch order, e.g. "splitk_reduce_cls + splitk_reduce_flat"; "" if there was none.  Reading
+ * clears the list.  The main kernel's name does not change with the split factor: this is what tells a test which of
+ * splitk_reduce / _wide / _vec / _flat / _cls / _stats a call went through. */
+const char* movae_bench_last_reduce(void);
 /* s > 0 pins the conv family's split-K factor (tools/conv_microbench.py tuning sweeps); 0 restores the heuristic.
  * Returns the previous value. */
 int movae_bench_force_split(int s);

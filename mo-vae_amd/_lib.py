@@ -168,6 +168,7 @@ SIGNATURES = {
     "movae_batch_u8": ([_p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_bench_main_kernel_only": ([_i], _i),
     "movae_bench_last_kernel": ([], C.c_char_p),
+    "movae_bench_last_reduce": ([], C.c_char_p),
     "movae_reduce_defer": ([_i], _i),
     "movae_reduce_flush": ([], _i),
     "movae_reduce_defer_stats": ([_p, _i], _i),

@@ -898,6 +898,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats(const float* __restri
 }
 
 const char* g_last_kernel = "";  // movae_bench_last_kernel(): main kernel chosen by the most recent conv-family dispatch
+// movae_bench_last_reduce(): the split-K reduce kernels chosen since the previous read, " + "-joined in launch order.  A name is
+// noted where the kernel is CHOSEN (a parked reduce counts once, when it is parked).  Bounded: what does not fit is dropped, so a
+// run that never reads the list pays one length check per reduce.
+char g_last_reduce[256] = "";
+size_t g_last_reduce_len = 0;
+inline void note_reduce(const char* name) {
+    const size_t n = strlen(name), sep = g_last_reduce_len ? 3 : 0;
+    if (g_last_reduce_len + sep + n + 1 > sizeof(g_last_reduce)) return;
+    if (sep) memcpy(g_last_reduce + g_last_reduce_len, " + ", 3);
+    memcpy(g_last_reduce + g_last_reduce_len + sep, name, n + 1);
+    g_last_reduce_len += sep + n;
+}
 int g_force_split = 0;           // movae_bench_force_split(): > 0 pins the split-K factor (tuning sweeps)
 bool g_bench_main_only = false;  // movae_bench_main_kernel_only(): time the MFMA kernel without its epilogue launches
 int g_force_kgemm = 0;           // movae_bench_force_kgemm(): 1 = every shape kgemm.h can serve takes it, -1 = none does (tests, A/B)
@@ -1011,6 +1023,8 @@ inline int launch_reduce_groups(const float* slab, const RGroups& rg, int G, lon
         r.kind = 3, r.nbx = (int)gq;
     }
     r.nblk = r.nbx * G;
+    static const char* const kind_name[4] = {"splitk_reduce_wide", "splitk_reduce_vec", "splitk_reduce", "splitk_reduce_flat"};
+    note_reduce(kind_name[r.kind]);
     if (deferrable && g_defer.armed && !bias && act == MOVAE_ACT_NONE && !am.y && !am.res &&
         (size_t)total * S * G * sizeof(float) <= (defer_max_bytes() > defer_max_bytes_pair() ? defer_max_bytes() : defer_max_bytes_pair())) {
         if (int rc = defer_flush()) return rc;  // (one slot)
@@ -1048,6 +1062,7 @@ inline bool launch_reduce_stats(const float* slab, float* out, long M, int N, in
     float* part = fuse_stats_claim(nblk, N);
     if (!part) return false;
     ClsSplit one{{S, S, S, S}};
+    note_reduce("splitk_reduce_stats");
     hipLaunchKernelGGL(splitk_reduce_stats, dim3((unsigned)nblk), dim3(256), 0, st, slab, out, (int)M, N, S, scls ? *scls : one, Ho, Wo,
                        scls ? stride : 0, bias, part, (int)rpb, BnBwd{});
     return true;
@@ -1078,6 +1093,7 @@ inline bool plan_reduce_bnbwd(long M, int N, BnBwd* bb, int* rows_per_block) {
 inline void launch_reduce_bnbwd(const float* slab, float* out, long M, int N, int S, const ClsSplit* scls, int Ho, int Wo, int stride,
                                 const BnBwd& bb, int rows_per_block, hipStream_t st) {
     ClsSplit one{{S, S, S, S}};
+    note_reduce("splitk_reduce_stats");
     hipLaunchKernelGGL(splitk_reduce_stats, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0, st, slab, out, (int)M,
                        N, S, scls ? *scls : one, Ho, Wo, scls ? stride : 0, (const float*)nullptr, (float*)nullptr, rows_per_block, bb);
 }
@@ -1238,9 +1254,9 @@ int launch_fwd(const float* X, const float* W, float* Y, const Geom& g_in, const
     }
     MOVAE_NO_NORM("generic conv (fwd form)");
     const bool vec = (g.Cr % BK == 0) && aligned16(X) && aligned16(W);
-    if (g.Nn <= 32) return (g_last_kernel = "igemm_fwd<128,32>", launch_fwd_t<128, 32>(X, W, Y, g, ep, M, K, vec, ws, ws_bytes, st));
-    if (Ml >= 128 * 512) return (g_last_kernel = "igemm_fwd<128,64>", launch_fwd_t<128, 64>(X, W, Y, g, ep, M, K, vec, ws, ws_bytes, st));
-    return (g_last_kernel = "igemm_fwd<64,64>", launch_fwd_t<64, 64>(X, W, Y, g, ep, M, K, vec, ws, ws_bytes, st));
+    if (g.Nn <= 32) return (g_last_kernel = vec ? "igemm_fwd<128,32,true>" : "igemm_fwd<128,32,false>", launch_fwd_t<128, 32>(X, W, Y, g, ep, M, K, vec, ws, ws_bytes, st));
+    if (Ml >= 128 * 512) return (g_last_kernel = vec ? "igemm_fwd<128,64,true>" : "igemm_fwd<128,64,false>", launch_fwd_t<128, 64>(X, W, Y, g, ep, M, K, vec, ws, ws_bytes, st));
+    return (g_last_kernel = vec ? "igemm_fwd<64,64,true>" : "igemm_fwd<64,64,false>", launch_fwd_t<64, 64>(X, W, Y, g, ep, M, K, vec, ws, ws_bytes, st));
 }
 
 template <int BM, int BN>
@@ -1312,9 +1328,9 @@ int launch_bwd(const float* X, const float* W, float* Y, const Geom& g, const Ep
     }
     MOVAE_NO_NORM("generic conv (bwd form)");
     const bool vec = (g.Cr % BK == 0) && (g.Nn % 4 == 0) && aligned16(X) && aligned16(W);
-    if (g.Nn <= 32) return (g_last_kernel = "igemm_bwd<128,32>", launch_bwd_t<128, 32>(X, W, Y, g, ep, vec, ws, ws_bytes, st));
-    if (Mc >= 128 * 512) return (g_last_kernel = "igemm_bwd<128,64>", launch_bwd_t<128, 64>(X, W, Y, g, ep, vec, ws, ws_bytes, st));
-    return (g_last_kernel = "igemm_bwd<64,64>", launch_bwd_t<64, 64>(X, W, Y, g, ep, vec, ws, ws_bytes, st));
+    if (g.Nn <= 32) return (g_last_kernel = vec ? "igemm_bwd<128,32,true>" : "igemm_bwd<128,32,false>", launch_bwd_t<128, 32>(X, W, Y, g, ep, vec, ws, ws_bytes, st));
+    if (Mc >= 128 * 512) return (g_last_kernel = vec ? "igemm_bwd<128,64,true>" : "igemm_bwd<128,64,false>", launch_bwd_t<128, 64>(X, W, Y, g, ep, vec, ws, ws_bytes, st));
+    return (g_last_kernel = vec ? "igemm_bwd<64,64,true>" : "igemm_bwd<64,64,false>", launch_bwd_t<64, 64>(X, W, Y, g, ep, vec, ws, ws_bytes, st));
 }
 
 template <int BM, int BN>
@@ -1356,8 +1372,11 @@ int launch_wgrad1(const float* S, const float* Bg, float* dW, const WGeom& g, in
     const int vec = ((g.Cs % 4 == 0 && aligned16(S)) ? 1 : 0) | ((g.Cb % 4 == 0 && aligned16(Bg)) ? 2 : 0);
     const int N = g.KH * g.KW * g.Cb;
     if (thin::thin_wgrad_ok(g) && ws) return thin::launch_thin_wgrad(S, Bg, dW, g, (int)Kl, accumulate, ws, ws_bytes, st);
-    if (N <= 32) return (g_last_kernel = "igemm_wgrad<128,32>", launch_wgrad_t<128, 32>(S, Bg, dW, g, (int)Kl, vec, accumulate, ws, ws_bytes, st));
-    return (g_last_kernel = "igemm_wgrad<64,64>", launch_wgrad_t<64, 64>(S, Bg, dW, g, (int)Kl, vec, accumulate, ws, ws_bytes, st));
+    static const char* const wgrad_name[2][4] = {  // [tile][vec]: bit 0 of vec is VECA, bit 1 VECB
+        {"igemm_wgrad<128,32,false,false>", "igemm_wgrad<128,32,true,false>", "igemm_wgrad<128,32,false,true>", "igemm_wgrad<128,32,true,true>"},
+        {"igemm_wgrad<64,64,false,false>", "igemm_wgrad<64,64,true,false>", "igemm_wgrad<64,64,false,true>", "igemm_wgrad<64,64,true,true>"}};
+    if (N <= 32) return (g_last_kernel = wgrad_name[0][vec], launch_wgrad_t<128, 32>(S, Bg, dW, g, (int)Kl, vec, accumulate, ws, ws_bytes, st));
+    return (g_last_kernel = wgrad_name[1][vec], launch_wgrad_t<64, 64>(S, Bg, dW, g, (int)Kl, vec, accumulate, ws, ws_bytes, st));
 }
 
 // G cotangent groups of one layer: group i reads S + i * s_gs and Bg + i * b_gs (0 = shared operand), writes dW[i]
@@ -1614,6 +1633,13 @@ static int conv_dgrad_wgrad_grouped(bool transposed, int groups, const float* dy
 extern "C" {
 
 const char* movae_bench_last_kernel(void) { return g_last_kernel; }
+
+const char* movae_bench_last_reduce(void) {
+    static char out[sizeof(g_last_reduce)];
+    memcpy(out, g_last_reduce, g_last_reduce_len + 1);
+    g_last_reduce[0] = 0, g_last_reduce_len = 0;
+    return out;
+}
 
 int movae_reduce_defer(int on) {
     const int prev = g_defer.armed ? 1 : 0;

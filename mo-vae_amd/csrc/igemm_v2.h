@@ -1236,6 +1236,7 @@ int finish_splitk(const Args& a, int S, const BnBwd& rbb, int rbb_rpb, const Act
     if constexpr (CLS) {
         long gq = (a.total / 4 + 255) / 256;
         if (gq > 4096) gq = 4096;
+        note_reduce("splitk_reduce_cls");
         hipLaunchKernelGGL(splitk_reduce_cls, dim3((unsigned)gq), dim3(256), 0, st, a.slab, a.Y, a.total, g.Nn, g.Ho, g.Wo, g.stride, a.scls,
                            a.ep.bias, a.ep.act, a.ep.slope, ram);
         MOVAE_CHECK_LAUNCH("splitk_reduce_cls");

@@ -258,15 +258,16 @@ def kern(form, dtype, tile="128,128"):
 
 
 class Out:
-    """An output between two guard zones: NaN (or `init`) inside, the sentinel around it."""
+    """An output between two guard zones: NaN (or `init`) inside, the sentinel around it.  off: floats past a 16-byte boundary."""
 
-    def __init__(self, shape, dev, init=None):
+    def __init__(self, shape, dev, init=None, off=0):
         n = 1
         for d in shape:
             n *= d
-        self.buf = torch.full((n + 2 * GUARD,), SENTINEL, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
-        assert self.t.data_ptr() % 16 == 0
+        self.lo = GUARD + off
+        self.buf = torch.full((n + 2 * GUARD + off,), SENTINEL, device=dev)
+        self.t = self.buf[self.lo:self.lo + n].view(shape)
+        assert self.t.data_ptr() % 16 == 4 * off
         if init is None:
             self.t.fill_(float("nan"))
         else:
@@ -278,7 +279,7 @@ class Out:
     def get(self, what):
         torch.cuda.synchronize()
         n = self.t.numel()
-        lo, hi = self.buf[:GUARD], self.buf[GUARD + n:]
+        lo, hi = self.buf[:self.lo], self.buf[self.lo + n:]
         assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), f"{what}: a store outside the output"
         bad = ~torch.isfinite(self.t)
         assert not bool(bad.any()), f"{what}: {int(bad.sum())} elements unwritten or not finite, first at flat index {int(bad.flatten().nonzero()[0])}"
@@ -302,11 +303,12 @@ class Scratch:
     def numel(self):
         return self.buf.numel() * 4  # bytes, as L.workspace()
 
-    def slabs(self, per_slab):
+    def slabs(self, per_slab, start=0, stop=None):
         """Slabs of `per_slab` floats that were written to: the last one may be ragged (rows past M are not stored), so the
-        count is taken from the last float written."""
+        count is taken from the last float written.  start, stop: the region of the scratch to look at, in floats (a paired
+        call keeps its input gradient's slabs in front of its weight gradient's)."""
         torch.cuda.synchronize()
-        written = (~torch.isnan(self.buf[WS_HEADER:])).nonzero()
+        written = (~torch.isnan(self.buf[WS_HEADER:][start:stop])).nonzero()
         return 0 if written.numel() == 0 else -(-(int(written[-1]) + 1) // per_slab)
 
 
@@ -324,10 +326,27 @@ def last(lib):
     return lib.movae_bench_last_kernel().decode()
 
 
-def run_fwd(L, lib, dev, g, x, w, b, expect, nrm=None, act=True, ws=None, fuse=None):
-    """b None: no bias.  fuse: a movae_fuse_t with side-product requests (the caller reads its out fields afterwards)."""
-    xd, wd, bd = x.to(dev), w.to(dev), None if b is None else b.to(dev)
-    y = Out((g.n, g.ho, g.wo, g.co), dev)
+def last_reduce(lib):
+    """The split-K reduce kernels chosen since the previous read, " + "-joined ("": none); reading clears the list."""
+    return lib.movae_bench_last_reduce().decode()
+
+
+def put(t, dev, off=False):
+    """t on the device; off: the same values one float past a 16-byte boundary, a view into a larger buffer."""
+    if not off:
+        return t.to(dev)
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=dev)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
+def run_fwd(L, lib, dev, g, x, w, b, expect, nrm=None, act=True, ws=None, fuse=None, off=""):
+    """b None: no bias.  fuse: a movae_fuse_t with side-product requests (the caller reads its out fields afterwards).
+    off: which of "x", "w", "y" lie one float past a 16-byte boundary, e.g. "xw"."""
+    xd, wd, bd = put(x, dev, "x" in off), put(w, dev, "w" in off), None if b is None else b.to(dev)
+    y = Out((g.n, g.ho, g.wo, g.co), dev, off="y" in off)
     ws, st = ws or L.workspace(dev), torch.cuda.current_stream().cuda_stream
     f, keep = fuse_of(L, nrm, dev, fuse)
     pre = "movae_convT2d_fwd" if g.tr else "movae_conv2d_fwd"
@@ -340,9 +359,10 @@ def run_fwd(L, lib, dev, g, x, w, b, expect, nrm=None, act=True, ws=None, fuse=N
     return y.get(f"{g.name} forward")
 
 
-def run_dgrad(L, lib, dev, g, dy, w, expect, groups=1, ws=None, fuse=None):
-    dyd, wd = dy.to(dev), w.to(dev)
-    dx = Out((groups * g.n, g.hi, g.wi, g.ci), dev)
+def run_dgrad(L, lib, dev, g, dy, w, expect, groups=1, ws=None, fuse=None, off=""):
+    """off: which of "w" and "y" (the result, dx) lie one float past a 16-byte boundary."""
+    dyd, wd = dy.to(dev), put(w, dev, "w" in off)
+    dx = Out((groups * g.n, g.hi, g.wi, g.ci), dev, off="y" in off)
     ws, st = ws or L.workspace(dev), torch.cuda.current_stream().cuda_stream
     pre = "movae_convT2d_dgrad" if g.tr else "movae_conv2d_dgrad"
     head = (dyd.data_ptr(), wd.data_ptr(), dx.ptr(), *g.args(groups), ws.data_ptr(), ws.numel(), st)
@@ -354,9 +374,10 @@ def run_dgrad(L, lib, dev, g, dy, w, expect, groups=1, ws=None, fuse=None):
     return dx.get(f"{g.name} input gradient")
 
 
-def run_wgrad(L, lib, dev, g, dy, x, expect, groups=1, nrm=None, init=None, bias=True, ws=None):
-    """-> ([dW per group], [dbias per group] or None); init = ([dW0 per group], [db0 per group]): accumulate into them."""
-    dyd, xd = dy.to(dev), x.to(dev)
+def run_wgrad(L, lib, dev, g, dy, x, expect, groups=1, nrm=None, init=None, bias=True, ws=None, off=""):
+    """-> ([dW per group], [dbias per group] or None); init = ([dW0 per group], [db0 per group]): accumulate into them.
+    off: "x" puts x one float past a 16-byte boundary."""
+    dyd, xd = dy.to(dev), put(x, dev, "x" in off)
     dws = [Out(g.wshape, dev, None if init is None else init[0][i]) for i in range(groups)]
     dbs = [Out((g.co,), dev, None if init is None else init[1][i]) for i in range(groups)] if bias else None
     arr = C.c_void_p * groups
@@ -373,6 +394,24 @@ def run_wgrad(L, lib, dev, g, dy, x, expect, groups=1, nrm=None, init=None, bias
     assert last(lib) == expect
     return ([o.get(f"{g.name} weight gradient {i}") for i, o in enumerate(dws)],
             [o.get(f"{g.name} bias gradient {i}") for i, o in enumerate(dbs)] if bias else None)
+
+
+def run_pair(L, lib, dev, g, dy, w, x, expect, groups=1, init=None, ws=None):
+    """The paired entry point (input gradient over all groups + grouped weight gradient with bias gradient of one layer):
+    -> (dx, [dW per group], [dbias per group])."""
+    dyd, wd, xd = dy.to(dev), w.to(dev), x.to(dev)
+    dx = Out((groups * g.n, g.hi, g.wi, g.ci), dev)
+    dws = [Out(g.wshape, dev, None if init is None else init[0][i]) for i in range(groups)]
+    dbs = [Out((g.co,), dev, None if init is None else init[1][i]) for i in range(groups)]
+    arr = C.c_void_p * groups
+    dwp, dbp = arr(*[o.ptr() for o in dws]), arr(*[o.ptr() for o in dbs])
+    ws, st = ws or L.workspace(dev), torch.cuda.current_stream().cuda_stream
+    pre = "movae_convT2d_dgrad_wgrad_grouped" if g.tr else "movae_conv2d_dgrad_wgrad_grouped"
+    L.call(pre, groups, dyd.data_ptr(), wd.data_ptr(), xd.data_ptr(), dx.ptr(), dwp, dbp, *g.args(), 0 if init is None else 1,
+           ws.data_ptr(), ws.numel(), st)
+    assert last(lib) == expect
+    return (dx.get(f"{g.name} input gradient (paired)"), [o.get(f"{g.name} weight gradient {i} (paired)") for i, o in enumerate(dws)],
+            [o.get(f"{g.name} bias gradient {i} (paired)") for i, o in enumerate(dbs)])
 
 
 def judge(what, got, ref, ops, dtype, kind, refkey=None):

@@ -49,7 +49,7 @@ def close(a, b, what="", rtol=None, atol=None):
 
 CONV_CASES = [
     # n, ci, h, w, co, k, s, p
-    (2, 3, 16, 16, 8, 3, 2, 1),      # generic gather path (ci = 3)
+    (2, 3, 16, 16, 8, 3, 2, 1),      # 3-channel input, 8 outputs: thin_in_k (the generic gather path is the (2, 6, ...) case below)
     (3, 16, 9, 7, 24, 3, 2, 1),      # vector path, odd sizes, N not multiple of tile
     (2, 32, 8, 8, 64, 3, 1, 1),      # stride 1
     (2, 3, 16, 16, 16, 4, 2, 1),     # k4 s2 (VQ / BetaTC encoders)
@@ -70,6 +70,7 @@ CONV_CASES = [
     (1, 3, 4, 512, 32, 3, 1, 1),     # ... blocks are row SEGMENTS (Wo a multiple of 256), stride 1
     (2, 32, 16, 16, 3, 3, 1, 1),     # thin_out_mfma_k fwd; its input gradient is thin_in_mfma_k BWD (32 outputs)
     (1, 64, 8, 32, 3, 3, 1, 1),      # ... two channel chunks fwd, two column tiles in the input gradient
+    (2, 6, 9, 7, 10, 3, 2, 1),       # no channel count a multiple of 4: the generic igemm_fwd / igemm_bwd / igemm_wgrad (test_hip_mid_tile.py's G1)
 ]
 
 
@@ -107,6 +108,7 @@ CONVT_CASES = [
     (3, 32, 8, 8, 3, 3, 2, 1, 1),     # thin-output kernel, 3x3 taps with output padding
     (2, 24, 16, 16, 2, 4, 2, 1, 0),   # thin-output kernel, 2 outputs, channels not a multiple of the chunk
     (2, 128, 16, 16, 3, 4, 2, 1, 0),  # VQ last layer: the input gradient is thin_in_mfma_k in FWD form with 128 outputs (four column tiles)
+    (2, 10, 5, 4, 6, 3, 2, 1, 1),     # the generic kernels through the transposed mapping (test_hip_mid_tile.py's GT1)
 ]
 
 
