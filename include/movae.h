@@ -578,6 +578,30 @@ int movae_cross_entropy_fwd(const float* logits, const int64_t* target, float* l
 int movae_cross_entropy_bwd(const float* logits, const int64_t* target, const float* lse, const float* gscale_dev, float* dlogits,
                             size_t rows, int k, movae_stream_t stream);
 
+/* ---- Cached ancestral sampling for the PixelCNN prior (pixelcnn_prior.py:323-349 PixelCNN.sample) ---------------------------
+ * The reference runs a full-grid forward for each of the H*W positions and keeps one pixel's logits.  The network is causal,
+ * so movae_prior_sample_step computes raster position (i, j) alone, for every sample of the batch, in one launch:
+ *   conv_in (mask A) over the causal taps of h0 [B,H,W,D0] = embedding(code) ++ condition (zero outside the grid)  -> x [C]
+ *   per GatedResBlock l: a = relu(conv1 x + b), stored to acache[l][B,H,W,C/2] at (i, j); m = relu(masked-B 3x3 over acache[l],
+ *     the centre tap being that a); x += sigmoid(conv_gate m) * tanh(conv_feature m)
+ *   logits = conv(relu(conv(relu(x))))  [K], stored raw to logits_out [B,H,W,K] where that is not NULL
+ *   code = forced[b,i,j] where forced is not NULL, else the smallest k with u < cdf_k of softmax(logits * inv_temperature),
+ *     clamped to K - 1; u = uniforms[b,i,j] where uniforms is not NULL, else 24 bits of Philox4x32-10 under key `seed` at
+ *     counter (sample_base + b, i*W + j, draw) -- a sample's draws do not depend on the batch it sits in
+ *   codes[b,i,j] = code (int64);  h0[b,i,j,0..E-1] = embedding row `code`
+ * Call it for (i, j) in raster order on one stream; h0's channels E..D0-1 hold the condition beforehand.  No workgroup talks to
+ * another and nothing is atomic: results are bit-identical from run to run and independent of B.
+ *   wpack: one 16-byte-aligned fp32 buffer of movae_prior_sample_pack_floats(...) floats (0 for an unsupported shape), every
+ *     matrix stored [row][cout padded to a multiple of 4, zero filled] with row = tap * cin + ci over the CAUSAL taps in raster
+ *     order, followed by its bias [cout padded]:  conv_in | per block: conv1, conv2 (taps (-1,-1) (-1,0) (-1,1) (0,-1) (0,0)),
+ *     gate ++ feature side by side ([C/2][2 * pad4(C)], bias alike) | head conv 1 | head conv 2 | embedding [K][E].
+ *   Supported: C even <= 256, 1 <= E <= D0 <= 256, K <= 2048, ks odd <= 7, any B, H, W >= 1, L >= 0 (3x3 block convs). */
+size_t movae_prior_sample_pack_floats(int D0, int E, int C, int L, int K, int ks);
+int movae_prior_sample_step(const float* wpack, size_t wpack_floats, float* h0, float* acache, int64_t* codes, const int64_t* forced,
+                            const float* uniforms, float* logits_out, int B, int H, int W, int D0, int E, int C, int L, int K, int ks, int i,
+                            int j, float inv_temperature, unsigned long long seed, unsigned long long draw, unsigned long long sample_base,
+                            movae_stream_t stream);
+
 /* ---- PixelSNAIL's causal self-attention (models/pixelcnn_prior.py:95-135 CausalAttention2d.forward; :16-22 the mask) ------
  * Replaces  attn = matmul(q, k^T) / sqrt(hd); masked_fill(tril == 0, -inf); softmax(-1); dropout; out = matmul(attn, v) and the
  * permute(0, 2, 3, 1).reshape of `out` (:118-131) -- fused, FlashAttention-2 style: no [L, L] matrix is ever stored.

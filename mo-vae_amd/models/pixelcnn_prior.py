@@ -103,9 +103,13 @@ class PixelCNN(tnn.Module):
         return ops.cross_entropy(logits.reshape(-1, self.num_embeddings), x.reshape(-1))
 
     @torch.no_grad()
-    def sample(self, batch_size, height, width, device, condition=None, temperature=1.0):
-        """Raster-scan ancestral sampling (pixelcnn_prior.py:323-349); the categorical draw uses torch's device generator."""
+    def sample(self, batch_size, height, width, device, condition=None, temperature=1.0, cached=False):
+        """Raster-scan ancestral sampling (pixelcnn_prior.py:323-349); the categorical draw uses torch's device generator.
+        cached=True: one launch per code on the cached activations (sampling.CachedPixelCNNSampler) instead of one full forward per
+        code; its draws come from Philox under torch.cuda.initial_seed(), so they differ from the full path's for the same seed."""
         self.eval()
+        if cached:
+            return self.cached_sampler().run(batch_size, height, width, condition=condition, temperature=temperature)
         samples = torch.zeros(batch_size, height, width, dtype=torch.long, device=device)
         cond = ops.to_nhwc(condition) if condition is not None else None
         for i in range(height):
@@ -114,6 +118,15 @@ class PixelCNN(tnn.Module):
                 probs = torch.softmax(logits, dim=1)
                 samples[:, i, j] = torch.multinomial(probs, 1).squeeze(-1)
         return samples
+
+    def cached_sampler(self):
+        """This model's CachedPixelCNNSampler, kept so that its draw counter advances from one sample() call to the next."""
+        from ..sampling import CachedPixelCNNSampler
+
+        s = self.__dict__.get("_cached_sampler")
+        if s is None:
+            s = self.__dict__["_cached_sampler"] = CachedPixelCNNSampler(self)
+        return s
 
     def total_trainable_params(self):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
@@ -148,17 +161,22 @@ class HierarchicalPixelCNN(tnn.Module):
         return {"loss_top": loss_top, "loss_bottom": loss_bottom, "total_loss": loss_top + loss_bottom}
 
     @torch.no_grad()
-    def sample(self, batch_size, top_shape, bottom_shape, device, temperature=1.0):
+    def sample(self, batch_size, top_shape, bottom_shape, device, temperature=1.0, cached=False):
+        """cached: both levels through PixelCNN.sample(cached=True); the upsampled top embedding is the bottom level's condition."""
         self.eval()
-        z_top = self.prior_top.sample(batch_size, top_shape[0], top_shape[1], device, temperature=temperature)
+        z_top = self._sample_top(batch_size, top_shape, device, temperature, cached)
         cond = nchw_view(self._condition(z_top))
-        z_bottom = self.prior_bottom.sample(batch_size, bottom_shape[0], bottom_shape[1], device, condition=cond, temperature=temperature)
+        z_bottom = self.prior_bottom.sample(batch_size, bottom_shape[0], bottom_shape[1], device, condition=cond, temperature=temperature,
+                                            cached=cached)
         return z_top, z_bottom
 
+    def _sample_top(self, batch_size, top_shape, device, temperature, cached):
+        return self.prior_top.sample(batch_size, top_shape[0], top_shape[1], device, temperature=temperature, cached=cached)
+
     @torch.no_grad()
-    def sample_with_vqvae2(self, vqvae2_model, batch_size, device, temperature=1.0):
+    def sample_with_vqvae2(self, vqvae2_model, batch_size, device, temperature=1.0, cached=False):
         t, b = vqvae2_model.latent_spatial_dim_top, vqvae2_model.latent_spatial_dim_bottom
-        z_top, z_bottom = self.sample(batch_size, (t, t), (b, b), device, temperature)
+        z_top, z_bottom = self.sample(batch_size, (t, t), (b, b), device, temperature, cached=cached)
         return vqvae2_model.decode_code(z_top, z_bottom)
 
     def total_trainable_params(self):
@@ -252,7 +270,13 @@ class PixelSNAIL(tnn.Module):
 
     forward = PixelCNN.forward
     loss = PixelCNN.loss
-    sample = PixelCNN.sample
+
+    def sample(self, batch_size, height, width, device, condition=None, temperature=1.0, cached=False):
+        if cached:
+            raise NotImplementedError("PixelSNAIL.sample(cached=True): the attention K/V cache is not built; cached sampling covers "
+                                      "PixelCNN and HierarchicalPixelCNN (sampling.CachedPixelCNNSampler)")
+        return PixelCNN.sample(self, batch_size, height, width, device, condition=condition, temperature=temperature)
+
     total_trainable_params = PixelCNN.total_trainable_params
 
 
@@ -269,3 +293,8 @@ class HierarchicalPixelSNAIL(HierarchicalPixelCNN):
         self.embedding_top = Embedding(num_embeddings, embedding_dim)
         self.upsample_top = mnn.ConvTranspose2d(embedding_dim, embedding_dim, 4, stride=2, padding=1)
         self.prior_bottom = PixelCNN(num_embeddings, embedding_dim, hidden_channels, num_layers_bottom, conditional_channels=embedding_dim)
+
+    def _sample_top(self, batch_size, top_shape, device, temperature, cached):
+        """The PixelSNAIL top is sampled by full recompute whatever `cached` says (no attention K/V cache); the PixelCNN bottom,
+        the expensive level, takes the cached path."""
+        return self.prior_top.sample(batch_size, top_shape[0], top_shape[1], device, temperature=temperature)

@@ -167,7 +167,8 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None)
     print(f"{name} prior training complete. Best loss: {best:.4f}. Saved to {prior_dir}")
     prior.eval()
     samples = generate_samples_vq_with_prior(net, prior, getattr(args, "num_vis_samples", 4), device,
-                                             getattr(args, "pixelcnn_temperature", 1.0))
+                                             getattr(args, "pixelcnn_temperature", 1.0),
+                                             cached=getattr(args, "prior_sampler", "full") == "cached")
     LAST_RUN.clear()
     LAST_RUN.update(net=net, prior=prior, epoch_losses=epoch_losses, use_cache=use_cache, n_codes=n_codes, samples=samples.detach().cpu(),
                     num_embeddings=K)
@@ -175,13 +176,13 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None)
 
 
 @torch.no_grad()
-def generate_samples_vq_with_prior(net, prior, num_samples, device, temperature=1.0):
-    """main.py:1046-1085."""
+def generate_samples_vq_with_prior(net, prior, num_samples, device, temperature=1.0, cached=False):
+    """main.py:1046-1085.  cached: sample the PixelCNN levels with one launch per code (sampling.py) instead of a forward per code."""
     net.eval()
     prior.eval()
     if hasattr(prior, "sample_with_vqvae2"):
-        return prior.sample_with_vqvae2(vqvae2_model=net, batch_size=num_samples, device=device, temperature=temperature)
+        return prior.sample_with_vqvae2(vqvae2_model=net, batch_size=num_samples, device=device, temperature=temperature, cached=cached)
     s = net.latent_spatial_dim
-    z = prior.sample(batch_size=num_samples, height=s, width=s, device=device, temperature=temperature)
+    z = prior.sample(batch_size=num_samples, height=s, width=s, device=device, temperature=temperature, cached=cached)
     q = net.vq_layer.embed_code(z).permute(0, 3, 1, 2)
     return net.decode(q)
