@@ -602,6 +602,29 @@ int movae_prior_sample_step(const float* wpack, size_t wpack_floats, float* h0, 
                             int j, float inv_temperature, unsigned long long seed, unsigned long long draw, unsigned long long sample_base,
                             movae_stream_t stream);
 
+/* ---- Cached ancestral sampling for the PixelSNAIL prior (pixelcnn_prior.py:159-259 PixelSNAIL; :95-156 its blocks) -------------
+ * The same step as movae_prior_sample_step, with NB PixelSNAILBlocks of NR GatedResBlocks each between conv_in and the head, and
+ * the attention's K and V rows of every earlier position kept in a cache.  Raster position (i, j) of every sample, one launch:
+ *   x = conv_in (mask A) over the causal taps of h0 [B,H,W,D0] = embedding(code) ++ the 2 position channels ++ condition
+ *   per PixelSNAILBlock nb:  r = its NR gated blocks applied to x, over acache[nb * NR + g][B,H,W,C/2] as above
+ *     q ++ k ++ v = r [Wq ++ Wk ++ Wv] + b (one product);  k, v stored to kvcache[nb][B][H*W][2P] at raster index i*W + j
+ *       (k in columns 0 .. P-1, v in P .. 2P-1, P = heads * hd; head h = channels h*hd .. h*hd+hd-1)
+ *     per head: o = softmax(q . k_t / sqrt(hd), t = 0 .. i*W + j, the position itself included) V, written in the reference's
+ *       channel order d * heads + h;  a = out_proj(o);  x = x + (out_conv([r ++ a]) + r)
+ *   head, draw, codes and h0's embedding channels exactly as movae_prior_sample_step (same Philox keying); no dropout.
+ * The keys of a (sample, head) are split over the lanes of one wave in a fixed pattern and the online-softmax partials merged in a
+ * fixed butterfly order; no atomics: results are bit-identical from run to run and independent of B and of the sample's slot.
+ *   wpack: as above, of movae_prior_snail_sample_pack_floats(...) floats:  conv_in | per PixelSNAILBlock: its NR gated blocks (conv1,
+ *     conv2, gate ++ feature), q ++ k ++ v side by side ([C][3 * pad4(P)], bias alike), out_proj [P][pad4(C)] (rows in the order
+ *     d * heads + h), out_conv [2C][pad4(C)] (rows r, then attention) | head conv 1 | head conv 2 | embedding [K][E].
+ *   Supported: what movae_prior_sample_step supports with E + 2 <= D0 <= 256, 1 <= hd <= 64, P <= 256, NB >= 0, NR >= 0; the LDS
+ *     need (at most 140 KiB at these limits) is checked against the 160 KiB of a workgroup.  kvcache 16-byte aligned. */
+size_t movae_prior_snail_sample_pack_floats(int D0, int E, int C, int NB, int NR, int heads, int hd, int K, int ks);
+int movae_prior_snail_sample_step(const float* wpack, size_t wpack_floats, float* h0, float* acache, float* kvcache, int64_t* codes,
+                                  const int64_t* forced, const float* uniforms, float* logits_out, int B, int H, int W, int D0, int E, int C,
+                                  int NB, int NR, int heads, int hd, int K, int ks, int i, int j, float inv_temperature,
+                                  unsigned long long seed, unsigned long long draw, unsigned long long sample_base, movae_stream_t stream);
+
 /* ---- PixelSNAIL's causal self-attention (models/pixelcnn_prior.py:95-135 CausalAttention2d.forward; :16-22 the mask) ------
  * Replaces  attn = matmul(q, k^T) / sqrt(hd); masked_fill(tril == 0, -inf); softmax(-1); dropout; out = matmul(attn, v) and the
  * permute(0, 2, 3, 1).reshape of `out` (:118-131) -- fused, FlashAttention-2 style: no [L, L] matrix is ever stored.

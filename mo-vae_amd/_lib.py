@@ -141,6 +141,8 @@ SIGNATURES = {
     "movae_cross_entropy_bwd": ([_p, _p, _p, _p, _p, _z, _i, _p], _i),
     "movae_prior_sample_pack_floats": ([_i] * 6, _z),
     "movae_prior_sample_step": ([_p, _z] + [_p] * 6 + [_i] * 11 + [_f, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, _p], _i),
+    "movae_prior_snail_sample_pack_floats": ([_i] * 9, _z),
+    "movae_prior_snail_sample_step": ([_p, _z] + [_p] * 7 + [_i] * 14 + [_f, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, _p], _i),
     "movae_causal_attn_fwd": ([_p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _f, C.c_ulonglong, C.c_ulonglong, _p], _i),
     "movae_causal_attn_ws_bytes": ([_i, _i, _i], _z),
     "movae_causal_attn_bwd": ([_p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, C.c_ulonglong, C.c_ulonglong, _p, _z, _p], _i),

@@ -272,10 +272,26 @@ class PixelSNAIL(tnn.Module):
     loss = PixelCNN.loss
 
     def sample(self, batch_size, height, width, device, condition=None, temperature=1.0, cached=False):
+        """cached="kv": one launch per code on the cached activations and the attention layers' K/V cache
+        (sampling.CachedPixelSNAILSampler), with Philox inverse-CDF draws like PixelCNN's cached path.  Any other truthy value still
+        raises: cached=True means the PixelCNN levels' sampler, which this model does not have."""
+        if cached == "kv":
+            self.eval()
+            return self.cached_sampler().run(batch_size, height, width, condition=condition, temperature=temperature)
         if cached:
-            raise NotImplementedError("PixelSNAIL.sample(cached=True): the attention K/V cache is not built; cached sampling covers "
-                                      "PixelCNN and HierarchicalPixelCNN (sampling.CachedPixelCNNSampler)")
+            raise NotImplementedError("PixelSNAIL.sample(cached=True): the attention K/V cache is not built on this path; cached=True "
+                                      "covers PixelCNN and HierarchicalPixelCNN (sampling.CachedPixelCNNSampler).  Pass cached=\"kv\" "
+                                      "for the K/V-cached sampler (sampling.CachedPixelSNAILSampler)")
         return PixelCNN.sample(self, batch_size, height, width, device, condition=condition, temperature=temperature)
+
+    def cached_sampler(self):
+        """This model's CachedPixelSNAILSampler, kept so that its draw counter advances from one sample() call to the next."""
+        from ..sampling import CachedPixelSNAILSampler
+
+        s = self.__dict__.get("_cached_sampler")
+        if s is None:
+            s = self.__dict__["_cached_sampler"] = CachedPixelSNAILSampler(self)
+        return s
 
     total_trainable_params = PixelCNN.total_trainable_params
 
@@ -295,6 +311,7 @@ class HierarchicalPixelSNAIL(HierarchicalPixelCNN):
         self.prior_bottom = PixelCNN(num_embeddings, embedding_dim, hidden_channels, num_layers_bottom, conditional_channels=embedding_dim)
 
     def _sample_top(self, batch_size, top_shape, device, temperature, cached):
-        """The PixelSNAIL top is sampled by full recompute whatever `cached` says (no attention K/V cache); the PixelCNN bottom,
-        the expensive level, takes the cached path."""
-        return self.prior_top.sample(batch_size, top_shape[0], top_shape[1], device, temperature=temperature)
+        """cached="kv": the PixelSNAIL top through its K/V-cached sampler.  Any other value: by full recompute, as before that sampler
+        existed; the PixelCNN bottom, the expensive level, takes the cached path for every truthy `cached`."""
+        return self.prior_top.sample(batch_size, top_shape[0], top_shape[1], device, temperature=temperature,
+                                     cached="kv" if cached == "kv" else False)

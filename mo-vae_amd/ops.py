@@ -2078,6 +2078,31 @@ def prior_sample_step(wpack, h0, acache, codes, dims, i, j, inv_temperature, see
           int(sample_base), _st(h0))
 
 
+def prior_snail_sample_pack_floats(d0, e, c, blocks, res_blocks, heads, head_dim, k, ks):
+    """Length of the packed weight buffer prior_snail_sample_step reads (include/movae.h); 0 for a shape it does not support."""
+    return int(L.load().movae_prior_snail_sample_pack_floats(d0, e, c, blocks, res_blocks, heads, head_dim, k, ks))
+
+
+@torch.no_grad()
+def prior_snail_sample_step(wpack, h0, acache, kvcache, codes, dims, i, j, inv_temperature, seed, draw, sample_base=0, forced=None,
+                            uniforms=None, logits_out=None):
+    """Raster position (i, j) of cached PixelSNAIL sampling for every sample of the batch, in one launch and in place: as
+    prior_sample_step, and the attention layers' k / v rows of (i, j) go to kvcache [blocks,B,H*W,2*heads*head_dim], whose earlier rows
+    they attend over (include/movae.h: movae_prior_snail_sample_step).
+    dims = (embedding_dim, hidden, blocks, res_blocks, heads, head_dim, K, kernel)."""
+    L.require_gpu(h0)
+    B, H, W, d0 = h0.shape
+    e, c, nb, nr, heads, hd, k, ks = dims
+    for t, shape, dt in ((wpack, (wpack.numel(),), torch.float32), (acache, (nb * nr, B, H, W, c // 2), torch.float32),
+                         (kvcache, (nb, B, H * W, 2 * heads * hd), torch.float32), (codes, (B, H, W), torch.int64),
+                         (forced, (B, H, W), torch.int64), (uniforms, (B, H, W), torch.float32), (logits_out, (B, H, W, k), torch.float32)):
+        assert t is None or (tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()), (tuple(t.shape), shape, t.dtype)
+    assert h0.dtype == torch.float32 and h0.is_contiguous() and (acache is not None or nb * nr == 0) and (kvcache is not None or nb == 0)
+    _call("movae_prior_snail_sample_step", wpack.data_ptr(), wpack.numel(), h0.data_ptr(), L.ptr(acache), L.ptr(kvcache), codes.data_ptr(),
+          L.ptr(forced), L.ptr(uniforms), L.ptr(logits_out), B, H, W, d0, e, c, nb, nr, heads, hd, k, ks, i, j, float(inv_temperature),
+          int(seed), int(draw), int(sample_base), _st(h0))
+
+
 class CrossEntropy(Function):
     """F.cross_entropy(logits[rows, K], target[rows]) with mean reduction (main.py:1003-1006; pixelcnn_prior.py:392-395)."""
 

@@ -168,16 +168,21 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None)
     prior.eval()
     samples = generate_samples_vq_with_prior(net, prior, getattr(args, "num_vis_samples", 4), device,
                                              getattr(args, "pixelcnn_temperature", 1.0),
-                                             cached=getattr(args, "prior_sampler", "full") == "cached")
+                                             cached=PRIOR_SAMPLERS[getattr(args, "prior_sampler", "full")])
     LAST_RUN.clear()
     LAST_RUN.update(net=net, prior=prior, epoch_losses=epoch_losses, use_cache=use_cache, n_codes=n_codes, samples=samples.detach().cpu(),
                     num_embeddings=K)
     return prior
 
 
+#: --prior_sampler -> the `cached` argument of the priors' sample()
+PRIOR_SAMPLERS = {"full": False, "cached": True, "cached_kv": "kv"}
+
+
 @torch.no_grad()
 def generate_samples_vq_with_prior(net, prior, num_samples, device, temperature=1.0, cached=False):
-    """main.py:1046-1085.  cached: sample the PixelCNN levels with one launch per code (sampling.py) instead of a forward per code."""
+    """main.py:1046-1085.  cached: sample the PixelCNN levels with one launch per code (sampling.py) instead of a forward per code;
+    cached="kv": every level that can be cached, the PixelSNAIL levels through their K/V cache included."""
     net.eval()
     prior.eval()
     if hasattr(prior, "sample_with_vqvae2"):

@@ -673,8 +673,9 @@ def build_parser():
     p.add_argument("--pixelcnn_num_layers", type=int, default=15)
     p.add_argument("--pixelcnn_lr", type=float, default=3e-4)
     p.add_argument("--pixelcnn_temperature", type=float, default=1.0)
-    # how the prior's samples are drawn: "full" = the reference's forward per code, "cached" = one launch per code (sampling.py)
-    p.add_argument("--prior_sampler", type=str, default="full", choices=["full", "cached"])
+    # how the prior's samples are drawn: "full" = the reference's forward per code, "cached" = one launch per code for the PixelCNN
+    # levels, "cached_kv" = that and the PixelSNAIL levels through their attention K/V cache (sampling.py)
+    p.add_argument("--prior_sampler", type=str, default="full", choices=["full", "cached", "cached_kv"])
     p.add_argument("--prior_use_lmdb_codes", action="store_true", default=True)
     p.add_argument("--no_prior_lmdb_codes", action="store_false", dest="prior_use_lmdb_codes")
     p.add_argument("--prior_force_extract_codes", action="store_true")
