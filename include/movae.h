@@ -752,6 +752,18 @@ int movae_lpips_finalize(int layers, const double* const* partials, const int* h
 int movae_batch_u8(const uint8_t* store, const int* idx, int b, int h, int w, int c, const float* lut, int flip,
                    unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream);
 
+/* ---- batches of VQ code grids from device-resident stores (csrc/prior.hip; prior.DeviceCodeLoader) -----------------------------------
+ * store_top: device [n][len_top], store_bottom: device [n][len_bottom] or NULL (one level only); both int16 (wide == 0) or both int32
+ * (wide == 1).  idx: device int[b], row numbers into the stores.  out_top: device int64 [b][len_top]; out_bottom: int64 [b][len_bottom],
+ * NULL exactly when store_bottom is.  out_x[j][:] = (int64) store_x[idx[j]][:], both levels in ONE launch.  A level whose row length
+ * is a multiple of 4 and whose bases are aligned (store: 4 elements, out: 16 bytes) moves 4 codes per load and two 16-byte stores; any
+ * other length goes code by code (lengths such as 15 work).  The caller range-checks idx; the kernel clamps a row number into
+ * [0, n - 1] all the same, so it never reads outside a store.  Offsets are 64-bit.  No atomics, no workspace; capturable.  Refused
+ * (MOVAE_EINVAL, nothing launched): a null store_top / idx / out_top, a second store without its output or the reverse, wide not in
+ * {0, 1}, n, b or a row length <= 0, a pointer not aligned to its element. */
+int movae_codes_batch(const void* store_top, const void* store_bottom, int wide, int n, int len_top, int len_bottom, const int* idx, int b,
+                      int64_t* out_top, int64_t* out_bottom, movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

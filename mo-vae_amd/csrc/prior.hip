@@ -114,9 +114,84 @@ __global__ void xent_bwd_k(const float* __restrict__ logits, const int64_t* __re
     }
 }
 
+// One level of a code batch: out[j][:] = (int64) store[idx[j]][:], rows of `len` codes.  A work item is 4 consecutive codes of one row
+// (one 8- or 16-byte load, two 16-byte stores) when every row starts on a vector boundary (len % 4 == 0, aligned bases: `vec`), the
+// same 4 codes one by one otherwise; the last item of a row whose length is no multiple of 4 is the scalar tail of len % 4 codes.
+struct CodesLevel {
+    const void* store;
+    int64_t* out;
+    int len;     // codes per row
+    int groups;  // work items per row: ceil(len / 4)
+    int vec;
+};
+
+struct CodesBatchArgs {
+    CodesLevel lv[2];  // lv[1].groups == 0: one level only
+    const int* idx;
+    long long items0;  // b * lv[0].groups: items below this belong to level 0
+    long long items;   // b * (lv[0].groups + lv[1].groups)
+    int n;             // rows of every store
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void codes_batch_k(CodesBatchArgs a) {
+    typedef T tx4 __attribute__((ext_vector_type(4)));
+    typedef long long i64x2 __attribute__((ext_vector_type(2)));
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < a.items; it += stride) {
+        const bool second = it >= a.items0;
+        const CodesLevel& l = a.lv[second ? 1 : 0];
+        const long long r = second ? it - a.items0 : it;
+        const long long j = r / l.groups;
+        const int g = (int)(r - j * l.groups), c0 = 4 * g;
+        int i = a.idx[j];
+        i = i < 0 ? 0 : (i >= a.n ? a.n - 1 : i);  // (the host checks the range before the launch; never read outside a store)
+        const T* src = static_cast<const T*>(l.store) + (size_t)i * l.len + c0;
+        int64_t* dst = l.out + (size_t)j * l.len + c0;
+        if (l.vec) {
+            const tx4 v = *reinterpret_cast<const tx4*>(src);
+            reinterpret_cast<i64x2*>(dst)[0] = i64x2{(long long)v.x, (long long)v.y};
+            reinterpret_cast<i64x2*>(dst)[1] = i64x2{(long long)v.z, (long long)v.w};
+        } else {
+            const int m = l.len - c0 < 4 ? l.len - c0 : 4;
+            for (int q = 0; q < m; ++q) dst[q] = (int64_t)src[q];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int movae_codes_batch(const void* store_top, const void* store_bottom, int wide, int n, int len_top, int len_bottom, const int* idx, int b,
+                      int64_t* out_top, int64_t* out_bottom, movae_stream_t stream) {
+    MOVAE_CHECK_ARG(store_top && idx && out_top, "movae_codes_batch: null pointer");
+    MOVAE_CHECK_ARG((store_bottom != nullptr) == (out_bottom != nullptr), "movae_codes_batch: the second store and its output go together");
+    MOVAE_CHECK_ARG(wide == 0 || wide == 1, "movae_codes_batch: wide is 0 (int16 stores) or 1 (int32 stores), got %d", wide);
+    MOVAE_CHECK_ARG(n > 0 && b > 0 && len_top > 0, "movae_codes_batch: n, b, len_top must be positive (got %d, %d, %d)", n, b, len_top);
+    MOVAE_CHECK_ARG(!store_bottom || len_bottom > 0, "movae_codes_batch: len_bottom must be positive (got %d)", len_bottom);
+    const size_t esz = wide ? 4 : 2;
+    MOVAE_CHECK_ARG(((uintptr_t)store_top & (esz - 1)) == 0 && ((uintptr_t)store_bottom & (esz - 1)) == 0 && ((uintptr_t)idx & 3) == 0 &&
+                        ((uintptr_t)out_top & 7) == 0 && ((uintptr_t)out_bottom & 7) == 0,
+                    "movae_codes_batch: a pointer is not aligned to its element");
+    CodesBatchArgs a;
+    const void* st[2] = {store_top, store_bottom};
+    int64_t* out[2] = {out_top, out_bottom};
+    const int len[2] = {len_top, store_bottom ? len_bottom : 0};
+    for (int q = 0; q < 2; ++q) {
+        a.lv[q].store = st[q], a.lv[q].out = out[q], a.lv[q].len = len[q], a.lv[q].groups = (len[q] + 3) / 4;
+        a.lv[q].vec = len[q] > 0 && len[q] % 4 == 0 && ((uintptr_t)st[q] & (4 * esz - 1)) == 0 && ((uintptr_t)out[q] & 15) == 0;
+    }
+    a.idx = idx, a.n = n;
+    a.items0 = (long long)b * a.lv[0].groups;
+    a.items = a.items0 + (long long)b * a.lv[1].groups;
+    const long long want = (a.items + 255) / 256;
+    const dim3 grid((unsigned)(want < 2048 ? want : 2048));  // grid-stride past 2048 blocks
+    if (wide) hipLaunchKernelGGL(codes_batch_k<int>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(codes_batch_k<short>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    MOVAE_CHECK_LAUNCH("codes_batch");
+    return MOVAE_OK;
+}
 
 int movae_embedding_fwd(const float* weight, const int64_t* idx, float* y, size_t rows, int k, int d, movae_stream_t stream) {
     MOVAE_CHECK_ARG(weight && idx && y && rows > 0 && k > 0 && d > 0, "movae_embedding_fwd: bad argument");

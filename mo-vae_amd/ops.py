@@ -2516,6 +2516,57 @@ def batch_u8(store, idx, lut, flip, seed, epoch):
     return out
 
 
+def check_rows(idx, n):
+    """Host-side range check of a row list (a sequence or a CPU tensor) against a store of n rows: ValueError before anything is
+    launched.  -> the list as a CPU int32 tensor."""
+    t = torch.as_tensor(idx).reshape(-1)
+    if t.is_cuda:
+        raise TypeError("check_rows: a host row list (a device list was range-checked where it was built)")
+    if t.numel() == 0:
+        raise ValueError("an empty row list")
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"row numbers are integers, got {t.dtype}")
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0 or hi >= n:
+        raise ValueError(f"row numbers {lo} .. {hi} outside the store's 0 .. {n - 1}")
+    return t.to(torch.int32)
+
+
+def codes_batch(store_top, idx, store_bottom=None, out_top=None, out_bottom=None):
+    """One batch of VQ code grids from device-resident stores (csrc/prior.hip: movae_codes_batch; prior.DeviceCodeLoader):
+    store_top [N][H][W] and, for the two-level models, store_bottom [N][H2][W2], both int16 or both int32; idx the b row numbers --
+    a host sequence / CPU tensor (range-checked here: ValueError, then uploaded) or a device int32 [b] its builder has range-checked.
+    -> int64 [b][H][W], or the pair (top, bottom): out[j] = store[idx[j]] widened, both levels in ONE launch.  out_top / out_bottom:
+    caller-supplied int64 buffers written in place and returned (a captured step's static inputs); fresh ones otherwise.
+    Not differentiable (a data source)."""
+    n = store_top.size(0)
+    if not (torch.is_tensor(idx) and idx.is_cuda):
+        idx = check_rows(idx, n).to(store_top.device)
+    L.require_gpu(store_top)
+    assert store_top.dtype in (torch.int16, torch.int32) and store_top.dim() == 3 and store_top.is_contiguous(), \
+        "codes_batch: store is contiguous int16 / int32 [N][H][W]"
+    assert idx.dtype == torch.int32 and idx.dim() == 1 and idx.numel() > 0 and idx.is_contiguous() and idx.device == store_top.device, \
+        "codes_batch: idx is int32 [b]"
+    b, outs = idx.numel(), []
+    for store, out in ((store_top, out_top), (store_bottom, out_bottom)):
+        if store is None:
+            assert out is None, "codes_batch: an output buffer without its store"
+            outs.append(None)
+            continue
+        assert store.dtype == store_top.dtype and store.dim() == 3 and store.size(0) == n and store.is_contiguous() and \
+            store.device == store_top.device, "codes_batch: both stores share dtype, device and row count"
+        shape = (b,) + tuple(store.shape[1:])
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=store.device)
+        assert out.dtype == torch.int64 and tuple(out.shape) == shape and out.is_contiguous() and out.device == store.device, \
+            f"codes_batch: an output buffer is contiguous int64 {shape}"
+        outs.append(out)
+    lens = [s[0].numel() if s is not None else 0 for s in (store_top, store_bottom)]
+    _call("movae_codes_batch", store_top.data_ptr(), L.ptr(store_bottom), 1 if store_top.dtype == torch.int32 else 0, n, lens[0], lens[1],
+          idx.data_ptr(), b, outs[0].data_ptr(), L.ptr(outs[1]), _st(store_top))
+    return outs[0] if store_bottom is None else (outs[0], outs[1])
+
+
 class MaxPool2x2(Function):
     """nn.MaxPool2d(kernel_size=2, stride=2) (floor mode) on NHWC [N, H, W, C], C % 4 == 0.  The backward writes every element of dx
     in one launch: dy to the first maximum of each window in scan order (torch's tie rule), zeros elsewhere and in the row / column

@@ -6,7 +6,11 @@ prior from a Dataset over it (:106-172).  `lmdb` is not importable here (and its
 cache is kept IN MEMORY: `VQCodeDataset` has the reference Dataset's `__len__` / `__getitem__` contract (a long tensor `z`, or a
 pair `(z_top, z_bottom)` for the hierarchical models) -- parity unpinned as a storage format, the tensors it yields are the
 golden-pinned models' own outputs.  `--no_prior_lmdb_codes` re-extracts the codes on the fly each batch, like the reference.
+
+Opt-in: `--prior_loader device` keeps the cache on the device and assembles each batch in one launch
+(DeviceCodeLoader), `--prior_step graph` replays the optimisation step as one hipGraph (GraphedPriorStep; PixelCNN priors only).
 """
+import math
 import os
 
 import torch
@@ -46,25 +50,201 @@ class VQCodeDataset(torch.utils.data.Dataset):
         return t(z) if t is not None else z
 
 
+def _refuse_if_too_big(need, device):
+    """The rule of data.DeviceBatchLoader._upload: a resident store may take at most half of the memory free on the device."""
+    free, _ = torch.cuda.mem_get_info(device)
+    if need > free // 2:
+        raise RuntimeError(f"the code grids need {need} bytes on {device}, more than half of the {free} bytes free there; "
+                           "keep them on the host with --prior_loader host")
+
+
 @torch.no_grad()
-def extract_codes(net, train_loader, device, is_hierarchical):
-    """One pass of the frozen VQ model over the training set (utils/vq_codes_lmdb.py:47-93): code grids on the host."""
+def extract_codes(net, train_loader, device, is_hierarchical, on_device=False):
+    """One pass of the frozen VQ model over the training set (utils/vq_codes_lmdb.py:47-93): code grids on the host, or with
+    `on_device` left where the model wrote them (no .cpu() round trip; what DeviceCodeLoader gathers its batches from)."""
     net.eval()
     tops, bots = [], []
-    # held as int16 / int32 on the host (a code is < num_embeddings): an int64 grid per ImageNet-scale VQ-VAE-2 sample would be
+    # held as int16 / int32 (a code is < num_embeddings): an int64 grid per ImageNet-scale VQ-VAE-2 sample would be
     # ~50 GB where the reference spills to LMDB; VQCodeDataset.__getitem__ hands out .long() like the reference's Dataset
     store = torch.int16 if int(getattr(net, "num_embeddings", 1 << 20)) <= (1 << 15) else torch.int32
+    keep = (lambda t: t.to(store)) if on_device else (lambda t: t.to(store).cpu())
+    sized = False
     for images, _ in train_loader:
         images = images.to(device)
         if is_hierarchical:
             cd = net.get_code_indices(images)
-            tops.append(cd["indices_top"].to(store).cpu())
-            bots.append(cd["indices_bottom"].to(store).cpu())
+            tops.append(keep(cd["indices_top"]))
+            bots.append(keep(cd["indices_bottom"]))
         else:
-            tops.append(net.get_code_indices(images).to(store).cpu())
+            tops.append(keep(net.get_code_indices(images)))
+        if on_device and not sized:  # refuse before the set is resident, not after: the first batch gives the bytes per sample
+            sized = True
+            per = sum(t[-1][0].numel() * t[-1].element_size() for t in (tops, bots) if t)
+            try:
+                total = len(train_loader.dataset)
+            except (AttributeError, TypeError):
+                total = tops[0].size(0)
+            _refuse_if_too_big(2 * per * total, tops[0].device)  # twice: the pieces and, for a moment, their concatenation
     if is_hierarchical:
         return VQCodeDataset((torch.cat(tops), torch.cat(bots)), True)
     return VQCodeDataset((torch.cat(tops),), False)
+
+
+class DeviceCodeLoader:
+    """data.DeviceBatchLoader for code grids: an iterable over the batches of a VQCodeDataset whose int16 / int32 grids are resident
+    on the device (uploaded on first use when the dataset holds them on the host).  Each epoch's index list is uploaded once as int32
+    and every batch is ONE movae_codes_batch launch that gathers the rows of both levels and widens them to int64.  drop_last=False:
+    the last batch may be ragged.  Yields z for a flat dataset, (z_top, z_bottom) for a hierarchical one.
+
+    bind(out_top, out_bottom): full batches are written into these buffers (a captured step's static inputs) and the buffers
+    themselves are yielded -- valid until the next batch; without it every batch is a fresh tensor."""
+
+    def __init__(self, ds, batch_size, device, shuffle=True, seed=0):
+        if not isinstance(ds, VQCodeDataset):
+            raise TypeError(f"DeviceCodeLoader needs a VQCodeDataset, got {type(ds).__name__}")
+        if ds.transform_index is not None:
+            raise TypeError("DeviceCodeLoader: a dataset with a per-item transform_index needs the host loader")
+        if batch_size <= 0:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if len(ds) >= 2 ** 31:
+            raise ValueError(f"{len(ds)} code grids: row numbers are int32")
+        self.dataset, self.batch_size, self.device = ds, int(batch_size), torch.device(device)
+        self.shuffle, self.seed, self.epoch = bool(shuffle), int(seed), 0
+        self._stores = None
+        self._out = (None, None)
+        self._idx = (None, None)  # (epoch, device int32 list)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def indices(self, epoch=None):
+        """The index list of `epoch` (default: the current one), on the host; no device is touched."""
+        from .data import shard_indices
+
+        return shard_indices(len(self.dataset), self.shuffle, self.seed, self.epoch if epoch is None else int(epoch))
+
+    def __len__(self):
+        return math.ceil(len(self.dataset) / self.batch_size)
+
+    def bind(self, out_top, out_bottom=None):
+        self._out = (out_top, out_bottom)
+
+    def _upload(self):
+        ds = self.dataset
+        grids = [ds.z_top, ds.z_bottom] if ds.is_hierarchical else [ds.z]
+        for g in grids:
+            if g.dim() != 3 or g.dtype not in (torch.int16, torch.int32, torch.int64):
+                raise ValueError(f"DeviceCodeLoader: code grids are integer [N][H][W], got {g.dtype} {tuple(g.shape)}")
+        dt = torch.int16 if all(g.dtype == torch.int16 for g in grids) else torch.int32
+        need = sum(g.numel() * (2 if dt == torch.int16 else 4) for g in grids if not g.is_cuda or g.dtype != dt)
+        if need:
+            _refuse_if_too_big(need, self.device)
+        self._stores = [g.to(device=self.device, dtype=dt).contiguous() for g in grids]
+
+    def _device_indices(self):
+        if self._idx[0] != self.epoch:
+            from . import ops
+
+            rows = ops.check_rows(self.indices(), len(self.dataset))  # ValueError before anything reaches the device
+            self._idx = (self.epoch, rows.to(self.device))
+        return self._idx[1]
+
+    def __iter__(self):
+        from . import ops
+
+        idx = self._device_indices()
+        if self._stores is None:
+            self._upload()
+        top, bottom = self._stores[0], (self._stores[1] if len(self._stores) == 2 else None)
+        for s in range(0, idx.numel(), self.batch_size):
+            rows = idx[s:s + self.batch_size]
+            out_top, out_bottom = self._out if rows.numel() == self.batch_size else (None, None)
+            yield ops.codes_batch(top, rows, bottom, out_top=out_top, out_bottom=out_bottom)
+
+
+def _one_step(prior, opt, z_top, z_bottom=None):
+    """One optimisation step of the prior (main.py:996-1016) -> the step's loss, a device scalar."""
+    opt.zero_grad()
+    if z_bottom is not None:
+        loss = prior.loss_function(z_top, z_bottom)["total_loss"]
+    else:
+        loss = prior.loss(z_top)  # == F.cross_entropy(logits.permute(0,2,3,1).reshape(-1,K), z.reshape(-1)), main.py:1003
+    loss.backward()
+    clip_grad_norm_(prior.parameters(), max_norm=1.0)
+    opt.step()
+    return loss.detach()
+
+
+class GraphedPriorStep:
+    """_one_step captured ONCE into a hipGraph and replayed per full batch (train.GraphedTrainStep for the prior stage): zero_grad,
+    the loss, its backward, clip_grad_norm_(max_norm=1.0) and the FusedAdam(device_step=True) step are a few hundred short launches
+    and a replay is one submission.  PixelCNN and HierarchicalPixelCNN only: they draw nothing in training, so the graph holds exactly
+    the launches the eager step makes.  The warm-up steps a capture needs are rewound (train._snapshot_state / _restore_state): the
+    first replay is step 1 of the stage, as the eager loop makes it.
+
+    step(z_top, z_bottom=None) -> the step's loss (a fresh device scalar).  A batch of the captured shape replays -- with one copy_
+    per level, or none when the batch IS the static input (DeviceCodeLoader.bind(step.static_top, step.static_bottom)); a batch of
+    any other shape (the ragged last one) takes the eager step on the same optimizer state."""
+
+    def __init__(self, prior, opt, example_top, example_bottom=None, warmup=3, record_calls=False):
+        from . import _lib as L
+        from . import ops
+        from .train import _restore_state, _snapshot_state
+
+        if isinstance(prior, (PixelSNAIL, HierarchicalPixelSNAIL)) or not isinstance(prior, (PixelCNN, HierarchicalPixelCNN)):
+            raise NotImplementedError(f"{type(prior).__name__}: only PixelCNN / HierarchicalPixelCNN replay (PixelSNAIL counts its dropout "
+                                      "draws in a host integer, which a capture would freeze); use the eager step")
+        if not isinstance(opt, FusedAdam) or not opt._device_step:
+            raise ValueError("GraphedPriorStep needs FusedAdam(device_step=True): the step counter must live on the device")
+        if isinstance(prior, HierarchicalPixelCNN) != (example_bottom is not None):
+            raise ValueError("GraphedPriorStep: a hierarchical prior takes (z_top, z_bottom), a flat one z alone")
+        if warmup < 1:
+            raise ValueError("GraphedPriorStep: at least one warm-up step (it creates the optimizer state the graph points at)")
+        self.prior, self.opt = prior, opt
+        self.replayed_steps = self.eager_steps = 0
+        dev = example_top.device
+        prior.train()
+        self.static_top = example_top.clone()
+        self.static_bottom = example_bottom.clone() if example_bottom is not None else None
+        snap = _snapshot_state(prior, opt, dev)
+        try:
+            L.workspace(dev)  # allocate the scratch arena outside the capture
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(warmup):
+                    _one_step(prior, opt, self.static_top, self.static_bottom)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            opt.zero_grad(set_to_none=True)
+            #: (name, args) of every C-ABI launch in the captured step (tools/prior_train_bench.py counts them)
+            self.calls = []
+            if record_calls:
+                L.TRACE = lambda name, cargs: self.calls.append((name, cargs))
+            try:
+                ops.forget_nhwc()
+                with torch.cuda.graph(self.graph):
+                    self.loss = _one_step(prior, opt, self.static_top, self.static_bottom)
+                ops.forget_nhwc()
+            finally:
+                L.TRACE = None
+        finally:
+            _restore_state(snap, prior, opt, dev)
+
+    def step(self, z_top, z_bottom=None):
+        if z_top.shape != self.static_top.shape or (z_bottom is None) != (self.static_bottom is None) or \
+                (z_bottom is not None and z_bottom.shape != self.static_bottom.shape):
+            self.eager_steps += 1
+            return _one_step(self.prior, self.opt, z_top, z_bottom)
+        if z_top.data_ptr() != self.static_top.data_ptr():
+            self.static_top.copy_(z_top, non_blocking=True)
+        if z_bottom is not None and z_bottom.data_ptr() != self.static_bottom.data_ptr():
+            self.static_bottom.copy_(z_bottom, non_blocking=True)
+        self.opt.sync_hyper()  # lr schedulers change the host value between replays
+        self.graph.replay()
+        self.replayed_steps += 1
+        return self.loss.clone()  # the graph's own scalar is overwritten by the next replay
 
 
 def is_hierarchical_arch(arch):
@@ -94,6 +274,17 @@ def build_pixelsnail_prior(net, args, device):
     return PixelSNAIL(num_blocks=getattr(args, "pixelsnail_num_blocks", 8), **common).to(device)
 
 
+PRIOR_LOADERS, PRIOR_STEPS = ("host", "device"), ("eager", "graph")
+
+
+def prior_modes(args):
+    """(--prior_loader, --prior_step) of a namespace; one that has neither attribute selects today's path, ("host", "eager")."""
+    loader_mode, step_mode = getattr(args, "prior_loader", "host"), getattr(args, "prior_step", "eager")
+    if loader_mode not in PRIOR_LOADERS or step_mode not in PRIOR_STEPS:
+        raise ValueError(f"prior_loader is one of {PRIOR_LOADERS} and prior_step one of {PRIOR_STEPS}, got {loader_mode!r}, {step_mode!r}")
+    return loader_mode, step_mode
+
+
 def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None):
     """main.py:890-1043.  Returns the trained prior (eval mode).  `prior`: an already built prior to train instead of the one
     build_prior makes (e.g. build_pixelsnail_prior's; a PixelSNAIL prior writes under pixelsnail_prior/, main.py:913)."""
@@ -109,34 +300,54 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None)
     os.makedirs(os.path.join(prior_dir, "checkpoints"), exist_ok=True)
     if prior is None:
         prior = build_prior(net, args, device)
-    opt = FusedAdam(prior.parameters(), lr=lr, weight_decay=0.0)
-    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=epochs, eta_min=1e-6)
     use_cache = getattr(args, "prior_use_lmdb_codes", True)
+    loader_mode, step_mode = prior_modes(args)
+    if loader_mode == "device" and not use_cache:
+        print("--prior_loader device needs the cached codes; with --no_prior_lmdb_codes the codes are extracted on the fly")
+        loader_mode = "host"
+    if step_mode == "graph" and snail:
+        print(f"--prior_step graph: {name} counts its dropout draws in a host integer, which a capture would freeze; "
+              "taking the eager step")
+        step_mode = "eager"
+    # (a captured step needs its step counter and learning rate on the device; the eager default keeps the host counter)
+    opt = FusedAdam(prior.parameters(), lr=lr, weight_decay=0.0, device_step=step_mode == "graph")
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=epochs, eta_min=1e-6)
     codes_loader, n_codes = None, 0
     if use_cache:
-        ds = extract_codes(net, train_loader, device, hier)
+        ds = extract_codes(net, train_loader, device, hier, on_device=loader_mode == "device")
         n_codes = len(ds)
-        codes_loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True, num_workers=0, drop_last=False)
+        if loader_mode == "device":
+            codes_loader = DeviceCodeLoader(ds, args.batch_size, device, shuffle=True, seed=getattr(args, "seed", None) or 0)
+        else:
+            codes_loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True, num_workers=0, drop_last=False)
     print(f"Training {name} prior for {epochs} epochs..." + (" (codes extracted once, held in memory)" if use_cache
                                                              else " (extracting codes on-the-fly)"))
     K = net.num_embeddings
     best, epoch_losses = float("inf"), []
+    graphed, eager_steps = None, 0
 
     def one_step(z_top, z_bottom=None):
-        opt.zero_grad()
-        if hier:
-            loss = prior.loss_function(z_top, z_bottom)["total_loss"]
-        else:
-            loss = prior.loss(z_top)  # == F.cross_entropy(logits.permute(0,2,3,1).reshape(-1,K), z.reshape(-1)), main.py:1003
-        loss.backward()
-        clip_grad_norm_(prior.parameters(), max_norm=1.0)
-        opt.step()
-        return loss.detach()
+        nonlocal graphed, eager_steps
+        if not hier:
+            z_bottom = None
+        if step_mode == "graph":
+            if graphed is None and z_top.size(0) == args.batch_size:  # captured on the first full batch, at its shape
+                graphed = GraphedPriorStep(prior, opt, z_top, z_bottom)
+                if isinstance(codes_loader, DeviceCodeLoader):  # later full batches are gathered straight into the static inputs
+                    codes_loader.bind(graphed.static_top, graphed.static_bottom)
+            if graphed is not None:
+                return graphed.step(z_top, z_bottom)
+        eager_steps += 1
+        return _one_step(prior, opt, z_top, z_bottom)
 
     for epoch in range(1, epochs + 1):
         prior.train()
         losses = []  # device scalars: read once per epoch, not once per step (the reference calls .item() every step)
-        if codes_loader is not None:
+        if isinstance(codes_loader, DeviceCodeLoader):
+            codes_loader.set_epoch(epoch)
+            for batch in codes_loader:
+                losses.append(one_step(*batch) if hier else one_step(batch))
+        elif codes_loader is not None:
             for batch in codes_loader:
                 if hier:
                     losses.append(one_step(batch[0].to(device), batch[1].to(device)))
@@ -171,7 +382,9 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None)
                                              cached=PRIOR_SAMPLERS[getattr(args, "prior_sampler", "full")])
     LAST_RUN.clear()
     LAST_RUN.update(net=net, prior=prior, epoch_losses=epoch_losses, use_cache=use_cache, n_codes=n_codes, samples=samples.detach().cpu(),
-                    num_embeddings=K)
+                    num_embeddings=K, loader=loader_mode, step_mode=step_mode,
+                    replayed_steps=graphed.replayed_steps if graphed is not None else 0,
+                    eager_steps=eager_steps + (graphed.eager_steps if graphed is not None else 0))
     return prior
 
 

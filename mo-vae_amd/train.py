@@ -676,6 +676,10 @@ def build_parser():
     # how the prior's samples are drawn: "full" = the reference's forward per code, "cached" = one launch per code for the PixelCNN
     # levels, "cached_kv" = that and the PixelSNAIL levels through their attention K/V cache (sampling.py)
     p.add_argument("--prior_sampler", type=str, default="full", choices=["full", "cached", "cached_kv"])
+    # where the prior stage's batches are assembled ("device": the cached code grids stay resident, one launch per batch) and how its
+    # step is issued ("graph": one hipGraph replay per full batch; PixelCNN priors only) -- prior.DeviceCodeLoader / GraphedPriorStep
+    p.add_argument("--prior_loader", type=str, default="host", choices=["host", "device"])
+    p.add_argument("--prior_step", type=str, default="eager", choices=["eager", "graph"])
     p.add_argument("--prior_use_lmdb_codes", action="store_true", default=True)
     p.add_argument("--no_prior_lmdb_codes", action="store_false", dest="prior_use_lmdb_codes")
     p.add_argument("--prior_force_extract_codes", action="store_true")
