@@ -14,6 +14,8 @@ import weakref
 import numpy as np
 import torch
 
+from . import ops
+
 _M32 = np.uint64(0xFFFFFFFF)
 
 
@@ -106,25 +108,33 @@ def shard_indices(n, shuffle, seed, epoch, rank=0, world_size=1):
     return idx[rank:total:world_size]
 
 
-#: (address, shape, strides of the host array, device) -> its uint8 copy on the device, while any loader holds it
-_STORES = weakref.WeakValueDictionary()
+def refuse_if_too_big(need, device, what, advice):
+    """The residency rule of every store kept on the device, checked before its upload: at most half of the memory free there."""
+    free, _ = torch.cuda.mem_get_info(device)
+    if need > free // 2:
+        raise RuntimeError(f"{what} {need} bytes on {device}, more than half of the {free} bytes free there; {advice}")
 
 
-class DeviceBatchLoader:
-    """Iterable over (images, labels) batches of a ResidentImages, assembled on the device: the uint8 set and its table are uploaded on
-    first use, each epoch's index list once, and every batch is ONE movae_batch_u8 launch into a fresh NHWC buffer, handed out as its
-    logical-NCHW view (ops.to_nhwc of it is zero-copy).  drop_last=False: the last batch is ragged.  Labels are zeros, like item[1]."""
+class ResidentLoader:
+    """Iterable over the batches of a set whose rows are resident on the device: the epoch's index list of this rank (shard_indices)
+    is range-checked on the host and uploaded once per epoch as int32, the set itself on first use, and every batch is one
+    self._batch(rows) over a slice of `batch_size` row numbers.  drop_last=False: the last batch is ragged."""
 
-    def __init__(self, ds, batch_size, device, shuffle, rank=0, world_size=1, seed=0):
-        if not isinstance(ds, ResidentImages):
-            raise TypeError(f"DeviceBatchLoader needs a ResidentImages, got {type(ds).__name__}")
+    # what a subclass gives --
+    # noun: what a row is, for the messages
+    # _upload(): make the set resident (called once, on first use); refuses a set that does not fit (refuse_if_too_big)
+    # _batch(rows): the batch of the device int32 row numbers `rows` -- what the iteration yields
+    # _checked(idx): the host index list as a CPU int32 tensor, refused unless every entry is a row of the set
+    noun = "rows"
+
+    def __init__(self, ds, batch_size, device, shuffle=True, rank=0, world_size=1, seed=0):
         if batch_size <= 0:
             raise ValueError(f"batch_size must be positive, got {batch_size}")
         if len(ds) >= 2 ** 31:
-            raise ValueError(f"{len(ds)} images: row numbers are int32")
+            raise ValueError(f"{len(ds)} {self.noun}: row numbers are int32")
         self.dataset, self.batch_size, self.device = ds, int(batch_size), torch.device(device)
         self.shuffle, self.rank, self.world_size, self.seed, self.epoch = bool(shuffle), int(rank), int(world_size), int(seed), 0
-        self._store = self._lut = self._zeros = None
+        self._uploaded = False
         self._idx = (None, None)  # (epoch, device int32 list)
 
     def set_epoch(self, epoch):
@@ -139,6 +149,38 @@ class DeviceBatchLoader:
         per_rank = math.ceil(len(self.dataset) / self.world_size)
         return math.ceil(per_rank / self.batch_size)
 
+    def _device_indices(self):
+        if self._idx[0] != self.epoch:
+            rows = self._checked(self.indices())  # on the host: a bad list is refused before anything reaches the device
+            if not self._uploaded:  # (and a set that does not fit before the list's upload)
+                self._upload()
+                self._uploaded = True
+            self._idx = (self.epoch, rows.to(self.device))
+        return self._idx[1]
+
+    def __iter__(self):
+        idx = self._device_indices()
+        for s in range(0, idx.numel(), self.batch_size):
+            yield self._batch(idx[s:s + self.batch_size])
+
+
+#: (address, shape, strides of the host array, device) -> its uint8 copy on the device, while any loader holds it
+_STORES = weakref.WeakValueDictionary()
+
+
+class DeviceBatchLoader(ResidentLoader):
+    """ResidentLoader over the (images, labels) batches of a ResidentImages: the uint8 set and its table are uploaded on first use,
+    and every batch is ONE movae_batch_u8 launch into a fresh NHWC buffer, handed out as its logical-NCHW view (ops.to_nhwc of it is
+    zero-copy).  Labels are zeros, like item[1]."""
+
+    noun = "images"
+
+    def __init__(self, ds, batch_size, device, shuffle, rank=0, world_size=1, seed=0):
+        if not isinstance(ds, ResidentImages):
+            raise TypeError(f"DeviceBatchLoader needs a ResidentImages, got {type(ds).__name__}")
+        super().__init__(ds, batch_size, device, shuffle, rank, world_size, seed)
+        self._store = self._lut = self._zeros = None
+
     def _upload(self):
         u8 = self.dataset.u8
         # loaders over the same host array on the same device share ONE store (the train and the prior loader of a run; AFHQ's train
@@ -146,11 +188,8 @@ class DeviceBatchLoader:
         key = (u8.__array_interface__["data"][0], u8.shape, u8.strides, str(self.device))
         store = _STORES.get(key)
         if store is None:
-            need = int(u8.nbytes) + self.dataset.table.numel() * 4
-            free, _ = torch.cuda.mem_get_info(self.device)
-            if need > free // 2:
-                raise RuntimeError(f"the image set needs {need} bytes on {self.device}, more than half of the {free} bytes free there; "
-                                   "keep it on the host with --data_loader host")
+            refuse_if_too_big(int(u8.nbytes) + self.dataset.table.numel() * 4, self.device, "the image set needs",
+                              "keep it on the host with --data_loader host")
             store = torch.empty(u8.shape, dtype=torch.uint8, device=self.device)
             rows = max(1, (256 << 20) // max(1, int(u8[0].nbytes)))  # staged through <= 256 MB of host memory (the array may be a map)
             for s in range(0, u8.shape[0], rows):
@@ -160,25 +199,15 @@ class DeviceBatchLoader:
         self._lut = self.dataset.table.to(self.device)
         self._zeros = torch.zeros(self.batch_size, dtype=torch.long, device=self.device)
 
-    def _device_indices(self):
-        if self._idx[0] != self.epoch:
-            idx = self.indices()
-            if idx and not 0 <= min(idx) <= max(idx) < len(self.dataset):
-                raise RuntimeError("DeviceBatchLoader: index list outside the store")
-            self._idx = (self.epoch, torch.tensor(idx, dtype=torch.int32).to(self.device))
-        return self._idx[1]
+    def _checked(self, idx):
+        if idx and not 0 <= min(idx) <= max(idx) < len(self.dataset):
+            raise RuntimeError("DeviceBatchLoader: index list outside the store")
+        return torch.tensor(idx, dtype=torch.int32)  # (an empty list gives an empty iteration)
 
-    def __iter__(self):
-        from . import ops
-
-        if self._store is None:
-            self._upload()
-        ds, epoch = self.dataset, self.epoch
-        idx = self._device_indices()
-        for s in range(0, idx.numel(), self.batch_size):
-            rows = idx[s:s + self.batch_size]
-            out = ops.batch_u8(self._store, rows, self._lut, flip=ds.train, seed=ds.seed, epoch=epoch)
-            yield out.permute(0, 3, 1, 2), self._zeros[:rows.numel()]
+    def _batch(self, rows):
+        ds = self.dataset
+        out = ops.batch_u8(self._store, rows, self._lut, flip=ds.train, seed=ds.seed, epoch=self.epoch)
+        return out.permute(0, 3, 1, 2), self._zeros[:rows.numel()]
 
 
 # ---- readers -----------------------------------------------------------------------------------------------------------------------

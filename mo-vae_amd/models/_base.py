@@ -146,7 +146,7 @@ class HotPathModel(tnn.Module):
             self.noise_on_device = True
             params = list(self.parameters())
             if params and params[0].is_cuda:
-                self._noise_state(params[0].device)  # (exists before the capture's state snapshot: train._state_tensors)
+                self._noise_state(params[0].device)  # (exists before the capture's state snapshot: capture.snapshot)
 
     #: draw the reparameterisation noise in the kernel (set by prepare_for_graph); `_noise_state_t`: device int64 {seed, draws}
     noise_on_device = False

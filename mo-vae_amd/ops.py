@@ -257,7 +257,7 @@ _LAST_NHWC = [None]  # (weakref to the NCHW source, its version counter, data_pt
 
 
 def forget_nhwc():
-    """Drop the remembered conversion (train.GraphedTrainStep calls this around every capture: a result produced eagerly
+    """Drop the remembered conversion (capture.capturing calls this around every capture: a result produced eagerly
     must not stand in for a launch the graph has to contain, and graph-pool memory must not leak into eager code)."""
     _LAST_NHWC[0] = None
 

@@ -10,16 +10,20 @@ golden-pinned models' own outputs.  `--no_prior_lmdb_codes` re-extracts the code
 Opt-in: `--prior_loader device` keeps the cache on the device and assembles each batch in one launch
 (DeviceCodeLoader), `--prior_step graph` replays the optimisation step as one hipGraph (GraphedPriorStep; PixelCNN priors only).
 """
-import math
 import os
 
 import torch
 
+from . import capture
+from . import ops
+from .data import ResidentLoader, refuse_if_too_big
 from .models.pixelcnn_prior import HierarchicalPixelCNN, HierarchicalPixelSNAIL, PixelCNN, PixelSNAIL
 from .optim import FusedAdam, clip_grad_norm_
 
 #: what the last train_pixelcnn_prior call did (tests and callers that want the numbers; the reference only prints them)
 LAST_RUN = {}
+#: data.refuse_if_too_big's wording for a code store
+_TOO_BIG = ("the code grids need", "keep them on the host with --prior_loader host")
 
 
 class VQCodeDataset(torch.utils.data.Dataset):
@@ -50,14 +54,6 @@ class VQCodeDataset(torch.utils.data.Dataset):
         return t(z) if t is not None else z
 
 
-def _refuse_if_too_big(need, device):
-    """The rule of data.DeviceBatchLoader._upload: a resident store may take at most half of the memory free on the device."""
-    free, _ = torch.cuda.mem_get_info(device)
-    if need > free // 2:
-        raise RuntimeError(f"the code grids need {need} bytes on {device}, more than half of the {free} bytes free there; "
-                           "keep them on the host with --prior_loader host")
-
-
 @torch.no_grad()
 def extract_codes(net, train_loader, device, is_hierarchical, on_device=False):
     """One pass of the frozen VQ model over the training set (utils/vq_codes_lmdb.py:47-93): code grids on the host, or with
@@ -84,47 +80,30 @@ def extract_codes(net, train_loader, device, is_hierarchical, on_device=False):
                 total = len(train_loader.dataset)
             except (AttributeError, TypeError):
                 total = tops[0].size(0)
-            _refuse_if_too_big(2 * per * total, tops[0].device)  # twice: the pieces and, for a moment, their concatenation
+            refuse_if_too_big(2 * per * total, tops[0].device, *_TOO_BIG)  # twice: the pieces and, for a moment, their concatenation
     if is_hierarchical:
         return VQCodeDataset((torch.cat(tops), torch.cat(bots)), True)
     return VQCodeDataset((torch.cat(tops),), False)
 
 
-class DeviceCodeLoader:
-    """data.DeviceBatchLoader for code grids: an iterable over the batches of a VQCodeDataset whose int16 / int32 grids are resident
-    on the device (uploaded on first use when the dataset holds them on the host).  Each epoch's index list is uploaded once as int32
-    and every batch is ONE movae_codes_batch launch that gathers the rows of both levels and widens them to int64.  drop_last=False:
-    the last batch may be ragged.  Yields z for a flat dataset, (z_top, z_bottom) for a hierarchical one.
+class DeviceCodeLoader(ResidentLoader):
+    """data.ResidentLoader over the batches of a VQCodeDataset whose int16 / int32 grids are resident on the device (uploaded on first
+    use when the dataset holds them on the host).  Every batch is ONE movae_codes_batch launch that gathers the rows of both levels
+    and widens them to int64.  Yields z for a flat dataset, (z_top, z_bottom) for a hierarchical one.
 
     bind(out_top, out_bottom): full batches are written into these buffers (a captured step's static inputs) and the buffers
     themselves are yielded -- valid until the next batch; without it every batch is a fresh tensor."""
+
+    noun = "code grids"
 
     def __init__(self, ds, batch_size, device, shuffle=True, seed=0):
         if not isinstance(ds, VQCodeDataset):
             raise TypeError(f"DeviceCodeLoader needs a VQCodeDataset, got {type(ds).__name__}")
         if ds.transform_index is not None:
             raise TypeError("DeviceCodeLoader: a dataset with a per-item transform_index needs the host loader")
-        if batch_size <= 0:
-            raise ValueError(f"batch_size must be positive, got {batch_size}")
-        if len(ds) >= 2 ** 31:
-            raise ValueError(f"{len(ds)} code grids: row numbers are int32")
-        self.dataset, self.batch_size, self.device = ds, int(batch_size), torch.device(device)
-        self.shuffle, self.seed, self.epoch = bool(shuffle), int(seed), 0
+        super().__init__(ds, batch_size, device, shuffle, seed=seed)
         self._stores = None
         self._out = (None, None)
-        self._idx = (None, None)  # (epoch, device int32 list)
-
-    def set_epoch(self, epoch):
-        self.epoch = int(epoch)
-
-    def indices(self, epoch=None):
-        """The index list of `epoch` (default: the current one), on the host; no device is touched."""
-        from .data import shard_indices
-
-        return shard_indices(len(self.dataset), self.shuffle, self.seed, self.epoch if epoch is None else int(epoch))
-
-    def __len__(self):
-        return math.ceil(len(self.dataset) / self.batch_size)
 
     def bind(self, out_top, out_bottom=None):
         self._out = (out_top, out_bottom)
@@ -138,28 +117,16 @@ class DeviceCodeLoader:
         dt = torch.int16 if all(g.dtype == torch.int16 for g in grids) else torch.int32
         need = sum(g.numel() * (2 if dt == torch.int16 else 4) for g in grids if not g.is_cuda or g.dtype != dt)
         if need:
-            _refuse_if_too_big(need, self.device)
+            refuse_if_too_big(need, self.device, *_TOO_BIG)
         self._stores = [g.to(device=self.device, dtype=dt).contiguous() for g in grids]
 
-    def _device_indices(self):
-        if self._idx[0] != self.epoch:
-            from . import ops
+    def _checked(self, idx):
+        return ops.check_rows(idx, len(self.dataset))  # ValueError
 
-            rows = ops.check_rows(self.indices(), len(self.dataset))  # ValueError before anything reaches the device
-            self._idx = (self.epoch, rows.to(self.device))
-        return self._idx[1]
-
-    def __iter__(self):
-        from . import ops
-
-        idx = self._device_indices()
-        if self._stores is None:
-            self._upload()
+    def _batch(self, rows):
         top, bottom = self._stores[0], (self._stores[1] if len(self._stores) == 2 else None)
-        for s in range(0, idx.numel(), self.batch_size):
-            rows = idx[s:s + self.batch_size]
-            out_top, out_bottom = self._out if rows.numel() == self.batch_size else (None, None)
-            yield ops.codes_batch(top, rows, bottom, out_top=out_top, out_bottom=out_bottom)
+        out_top, out_bottom = self._out if rows.numel() == self.batch_size else (None, None)
+        return ops.codes_batch(top, rows, bottom, out_top=out_top, out_bottom=out_bottom)
 
 
 def _one_step(prior, opt, z_top, z_bottom=None):
@@ -176,21 +143,17 @@ def _one_step(prior, opt, z_top, z_bottom=None):
 
 
 class GraphedPriorStep:
-    """_one_step captured ONCE into a hipGraph and replayed per full batch (train.GraphedTrainStep for the prior stage): zero_grad,
-    the loss, its backward, clip_grad_norm_(max_norm=1.0) and the FusedAdam(device_step=True) step are a few hundred short launches
-    and a replay is one submission.  PixelCNN and HierarchicalPixelCNN only: they draw nothing in training, so the graph holds exactly
-    the launches the eager step makes.  The warm-up steps a capture needs are rewound (train._snapshot_state / _restore_state): the
-    first replay is step 1 of the stage, as the eager loop makes it.
+    """_one_step captured ONCE into a hipGraph and replayed per full batch, by the protocol of capture.py that train.GraphedTrainStep
+    follows too: zero_grad, the loss, its backward, clip_grad_norm_(max_norm=1.0) and the FusedAdam(device_step=True) step are a few
+    hundred short launches and a replay is one submission.  PixelCNN and HierarchicalPixelCNN only: they draw nothing in training, so
+    the graph holds exactly the launches the eager step makes.  The warm-up steps a capture needs are rewound (capture.snapshot /
+    restore): the first replay is step 1 of the stage, as the eager loop makes it.
 
     step(z_top, z_bottom=None) -> the step's loss (a fresh device scalar).  A batch of the captured shape replays -- with one copy_
     per level, or none when the batch IS the static input (DeviceCodeLoader.bind(step.static_top, step.static_bottom)); a batch of
     any other shape (the ragged last one) takes the eager step on the same optimizer state."""
 
     def __init__(self, prior, opt, example_top, example_bottom=None, warmup=3, record_calls=False):
-        from . import _lib as L
-        from . import ops
-        from .train import _restore_state, _snapshot_state
-
         if isinstance(prior, (PixelSNAIL, HierarchicalPixelSNAIL)) or not isinstance(prior, (PixelCNN, HierarchicalPixelCNN)):
             raise NotImplementedError(f"{type(prior).__name__}: only PixelCNN / HierarchicalPixelCNN replay (PixelSNAIL counts its dropout "
                                       "draws in a host integer, which a capture would freeze); use the eager step")
@@ -206,31 +169,18 @@ class GraphedPriorStep:
         prior.train()
         self.static_top = example_top.clone()
         self.static_bottom = example_bottom.clone() if example_bottom is not None else None
-        snap = _snapshot_state(prior, opt, dev)
+        step = lambda: _one_step(prior, opt, self.static_top, self.static_bottom)  # noqa: E731
+        snap = capture.snapshot(prior, opt, dev)
         try:
-            L.workspace(dev)  # allocate the scratch arena outside the capture
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    _one_step(prior, opt, self.static_top, self.static_bottom)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+            capture.warm_up(step, warmup, dev)
             self.graph = torch.cuda.CUDAGraph()
             opt.zero_grad(set_to_none=True)
             #: (name, args) of every C-ABI launch in the captured step (tools/prior_train_bench.py counts them)
             self.calls = []
-            if record_calls:
-                L.TRACE = lambda name, cargs: self.calls.append((name, cargs))
-            try:
-                ops.forget_nhwc()
-                with torch.cuda.graph(self.graph):
-                    self.loss = _one_step(prior, opt, self.static_top, self.static_bottom)
-                ops.forget_nhwc()
-            finally:
-                L.TRACE = None
+            with capture.recording(self.calls if record_calls else None), capture.capturing(self.graph):
+                self.loss = step()
         finally:
-            _restore_state(snap, prior, opt, dev)
+            capture.restore(snap, prior, opt, dev)
 
     def step(self, z_top, z_bottom=None):
         if z_top.shape != self.static_top.shape or (z_bottom is None) != (self.static_bottom is None) or \
@@ -340,30 +290,29 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None)
         eager_steps += 1
         return _one_step(prior, opt, z_top, z_bottom)
 
-    for epoch in range(1, epochs + 1):
-        prior.train()
-        losses = []  # device scalars: read once per epoch, not once per step (the reference calls .item() every step)
+    def batches(epoch):
+        """The epoch's (z_top, z_bottom or None) batches on the device, from whichever source the stage has."""
         if isinstance(codes_loader, DeviceCodeLoader):
             codes_loader.set_epoch(epoch)
             for batch in codes_loader:
-                losses.append(one_step(*batch) if hier else one_step(batch))
-        elif codes_loader is not None:
+                yield batch if hier else (batch, None)
+        elif codes_loader is not None:  # the host DataLoader over the cache
             for batch in codes_loader:
                 if hier:
-                    losses.append(one_step(batch[0].to(device), batch[1].to(device)))
+                    yield batch[0].to(device), batch[1].to(device)
                 else:
-                    z = batch if isinstance(batch, torch.Tensor) else batch[0]
-                    losses.append(one_step(z.to(device)))
-        else:
+                    yield (batch if isinstance(batch, torch.Tensor) else batch[0]).to(device), None
+        else:  # extracted on the fly
             for images, _ in train_loader:
                 images = images.to(device)
                 with torch.no_grad():
-                    if hier:
-                        cd = net.get_code_indices(images)
-                        zt, zb = cd["indices_top"], cd["indices_bottom"]
-                    else:
-                        zt, zb = net.get_code_indices(images), None
-                losses.append(one_step(zt, zb))
+                    codes = net.get_code_indices(images)
+                yield (codes["indices_top"], codes["indices_bottom"]) if hier else (codes, None)
+
+    for epoch in range(1, epochs + 1):
+        prior.train()
+        # device scalars: read once per epoch, not once per step (the reference calls .item() every step)
+        losses = [one_step(z_top, z_bottom) for z_top, z_bottom in batches(epoch)]
         sched.step()
         if hasattr(opt, "sync_hyper"):
             opt.sync_hyper()

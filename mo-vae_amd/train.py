@@ -20,13 +20,13 @@ import torch.optim as optim
 from . import _lib as L
 from . import aggregation
 from . import autojac
-from . import ops
+from . import capture
 from .aggregation import COMFORT, MGDA
 from .data import ALIASES, NPY_SETS, DeviceBatchLoader, ResidentImages, get_real_dataset
 from .metrics import ReconMetricAccumulator, build_hv_indicator
 from .models import get_network
 from .optim import FusedAdam, FusedAdamW, clip_grad_norm_
-from .parallel import DataParallelGrads
+from .parallel import DataParallelGrads, flatten_grads, unflatten_into_grads
 
 _current_step = 0
 _hook_values = {}
@@ -130,35 +130,9 @@ def train_step(net, images, optimizer, aggregator, args, dp=None):
 
 
 DP_OVERLAP_MIN_BYTES = 32 << 20
-
-
-def _state_tensors(net):
-    # BetaTC's device-side step counter; the in-kernel noise generator's {seed, draws} (models/_base.py)
-    extra = [t for t in (getattr(net, "_iter_dev", None), getattr(net, "_noise_state_t", None)) if isinstance(t, torch.Tensor)]
-    return list(net.parameters()) + list(net.buffers()) + extra
-
-
-def _snapshot_state(net, optimizer, device):
-    return {"tensors": [t.detach().clone() for t in _state_tensors(net)],
-            "opt": {id(p): {k: v.detach().clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in optimizer.state.items()},
-            "cuda_rng": torch.cuda.get_rng_state(device), "cpu_rng": torch.get_rng_state()}
-
-
-@torch.no_grad()
-def _restore_state(snap, net, optimizer, device):
-    torch.cuda.synchronize(device)
-    for t, s in zip(_state_tensors(net), snap["tensors"]):
-        t.copy_(s)
-    for p, st in optimizer.state.items():  # the state tensors keep their addresses (the captured graph points at them)
-        old = snap["opt"].get(id(p), {})
-        for k, v in st.items():
-            if torch.is_tensor(v):
-                if k in old:
-                    v.copy_(old[k])
-                else:
-                    v.zero_()
-    torch.cuda.set_rng_state(snap["cuda_rng"], device)
-    torch.set_rng_state(snap["cpu_rng"])
+# the process group's watchdog thread polls events of earlier collectives; under the default "global" capture mode
+# such a query from another thread invalidates the capture (seen at C4, whose capture is long enough to collide)
+_DP_CAPTURE = dict(capture_error_mode="thread_local")
 
 
 class GraphedTrainStep:
@@ -186,103 +160,93 @@ class GraphedTrainStep:
         # preserve_state: the warm-up steps a capture needs are real optimisation steps; with this flag everything they
         # touched (parameters, buffers, optimizer state, RNG streams) is rewound afterwards, so the first replay is step 1
         # of the run exactly as the eager loop would have made it (train_epoch uses this)
-        snap = _snapshot_state(net, optimizer, example.device) if preserve_state else None
+        snap = capture.snapshot(net, optimizer, example.device) if preserve_state else None
         try:
             self._build(net, optimizer, aggregator, args, example, warmup, dp, record_calls)
         finally:
             if snap is not None:
-                _restore_state(snap, net, optimizer, example.device)
+                capture.restore(snap, net, optimizer, example.device)
 
     def _build(self, net, optimizer, aggregator, args, example, warmup, dp, record_calls):
+        """The protocol of capture.py around one of the three forms of the step."""
         self.net, self.opt, self.agg, self.args, self.dp = net, optimizer, aggregator, args, dp
         self.static_x = example.clone()
-        from . import _lib as L
-        from .parallel import flatten_grads, unflatten_into_grads
-
-        L.workspace(example.device)  # allocate the scratch arena outside the capture
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                train_step(net, self.static_x, optimizer, aggregator, args, dp)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        capture.warm_up(lambda: train_step(net, self.static_x, optimizer, aggregator, args, dp), warmup, example.device)
         self.graph = torch.cuda.CUDAGraph()
         self.graph2 = None
-        self.dp_form = "single device"
         optimizer.zero_grad(set_to_none=True)
         #: (name, args) of every C-ABI launch in the captured step; the pointers stay valid (graph-pool memory) for the
         #: life of this object, which lets bench.py re-issue and time each launch on the step's real operands
         self.calls = []
-        if record_calls:
-            L.TRACE = lambda name, cargs: self.calls.append((name, cargs))
-        try:
-            if dp is None:
-                ops.forget_nhwc()
-                with torch.cuda.graph(self.graph):
-                    self.loss_dict, self.outputs = train_step(net, self.static_x, optimizer, aggregator, args)
-                ops.forget_nhwc()
-                return
-        finally:
-            L.TRACE = None
+        if dp is None:
+            self._capture_single(record_calls)
+            return
         params = [p for p in net.parameters() if p.requires_grad]
         # the bucket handed to the collective is an ordinary allocation (not graph-pool memory)
         self.flat = torch.zeros(sum(p.numel() for p in params) + 64, dtype=torch.float32, device=example.device)
         # RCCL averages inside the collective (ncclAvg); gloo (CPU rehearsal of the N>1 path) has no AVG: sum, then scale
         self._avg = dp.backend == "nccl"
-        # the process group's watchdog thread polls events of earlier collectives; under the default "global" capture mode
-        # such a query from another thread invalidates the capture (seen at C4, whose capture is long enough to collide)
-        cap = dict(capture_error_mode="thread_local")
         torch.cuda.synchronize()
         # splitting the step costs one more graph launch and two cross-stream waits (~60 us measured on MI355X); it pays
         # once the task-side bucket's exchange is longer than that, i.e. not for the 13 MB of the 32x32 VAEs
         mode = os.environ.get("MOVAE_DP_OVERLAP", "auto")
         overlap = mode == "1" or (mode == "auto" and self.flat.numel() * 4 >= DP_OVERLAP_MIN_BYTES)
-        # One bucket over RCCL: the collective is captured too, so the whole data-parallel step is ONE replay.  Three pieces
-        # (graph, eager all-reduce, graph) cost ~110 us per step in cross-queue hand-offs on MI355X (1.415 vs 1.306 ms with one
-        # hardware queue); inside one graph the collective is just another kernel node.  gloo cannot be captured, and
-        # MOVAE_DP_CAPTURE_COLLECTIVE=0 (or a failing capture) falls back to the pieces.
         # MOVAE_DP_CAPTURE_COLLECTIVE: "auto" (default) capture the collective and fall back to the pieces if that fails -- but
-        # only when EVERY rank agrees (MIN all-reduce of an ok-flag: a rank that fell back alone would issue collectives its
-        # peers never post: the pieces all-reduce while they are built); "1" capture it and RAISE if that fails (strict
-        # opt-in); "0" never capture it.  The form taken is recorded in self.dp_form and logged once on rank 0 (train.main).
+        # only when EVERY rank agrees; "1" capture it and RAISE if that fails (strict opt-in); "0" never capture it.  gloo cannot
+        # be captured.  The form taken is recorded in self.dp_form and logged once on rank 0 (train.main).
         cc_mode = os.environ.get("MOVAE_DP_CAPTURE_COLLECTIVE", "auto")
-        self.dp_form = "graph | all-reduce | graph"
-        if not overlap and dp.backend == "nccl" and cc_mode != "0":
-            err = None
-            try:
-                ops.forget_nhwc()
-                whole = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(whole, **cap):
-                    self.loss_dict, self.outputs = forward_backward(net, self.static_x, optimizer, aggregator)
-                    self.flat_a = self.flat[: sum(p.numel() for p in params)]
-                    flatten_grads(params, out=self.flat_a)
-                    self.reduce(self.flat_a)
-                    unflatten_into_grads(self.flat_a, params)
-                    if getattr(args, "max_grad_norm", None) is not None:
-                        clip_grad_norm_(params, max_norm=args.max_grad_norm)
-                    optimizer.step()
-                ops.forget_nhwc()
-            except Exception as e:  # noqa: BLE001
-                if cc_mode != "auto":
-                    raise
-                err = e
-            ok = torch.tensor([0 if err is not None else 1], device=example.device, dtype=torch.int32)
-            if cc_mode == "auto":  # agree on ONE form: every rank takes the pieces if any rank's capture failed
-                torch.cuda.synchronize()
-                torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN)
-            if int(ok.item()) == 1:
-                self.graph, self.graph_b, self.flat_b = whole, None, None
-                self.dp_form = "1 graph + captured all-reduce"
-                return
-            print(f"[movae] capturing the all-reduce failed on some rank ({type(err).__name__ if err else 'peer'}: {err}); "
-                  "all ranks use graph / all-reduce / graph", flush=True)
+        if overlap or dp.backend != "nccl" or cc_mode == "0" or not self._capture_whole(params, cc_mode):
+            self._capture_pieces(params, overlap)
+
+    def _capture_single(self, record_calls):
+        """Single device: the eager train_step, as it stands, in one graph."""
+        self.dp_form = "single device"
+        with capture.recording(self.calls if record_calls else None), capture.capturing(self.graph):
+            self.loss_dict, self.outputs = train_step(self.net, self.static_x, self.opt, self.agg, self.args)
+
+    def _capture_whole(self, params, cc_mode):
+        """One bucket over RCCL, the collective captured too: the whole data-parallel step is ONE replay.  -> whether it was taken."""
+        # Three pieces (graph, eager all-reduce, graph) cost ~110 us per step in cross-queue hand-offs on MI355X (1.415 vs 1.306 ms
+        # with one hardware queue); inside one graph the collective is just another kernel node.  False (cc_mode "auto" only) when
+        # the capture failed on ANY rank (MIN all-reduce of an ok-flag: a rank that fell back alone would issue collectives its
+        # peers never post: the pieces all-reduce while they are built); self.graph is then fresh for the pieces.
+        optimizer, args = self.opt, self.args
+        err, whole = None, torch.cuda.CUDAGraph()
+        try:
+            with capture.capturing(whole, **_DP_CAPTURE):
+                self.loss_dict, self.outputs = forward_backward(self.net, self.static_x, optimizer, self.agg)
+                self.flat_a = self.flat[: sum(p.numel() for p in params)]
+                flatten_grads(params, out=self.flat_a)
+                self.reduce(self.flat_a)
+                unflatten_into_grads(self.flat_a, params)
+                if getattr(args, "max_grad_norm", None) is not None:
+                    clip_grad_norm_(params, max_norm=args.max_grad_norm)
+                optimizer.step()
+        except Exception as e:  # noqa: BLE001
+            if cc_mode != "auto":
+                raise
+            err = e
+        ok = torch.tensor([0 if err is not None else 1], device=self.flat.device, dtype=torch.int32)
+        if cc_mode == "auto":  # agree on ONE form: every rank takes the pieces if any rank's capture failed
             torch.cuda.synchronize()
-            optimizer.zero_grad(set_to_none=True)
-            self.graph = torch.cuda.CUDAGraph()
-        ops.forget_nhwc()
-        with torch.cuda.graph(self.graph, **cap):
-            self.loss_dict, self.outputs, pending = forward_backward_begin(net, self.static_x, optimizer, aggregator)
+            torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN)
+        if int(ok.item()) == 1:
+            self.graph, self.graph_b, self.flat_b = whole, None, None
+            self.dp_form = "1 graph + captured all-reduce"
+            return True
+        print(f"[movae] capturing the all-reduce failed on some rank ({type(err).__name__ if err else 'peer'}: {err}); "
+              "all ranks use graph / all-reduce / graph", flush=True)
+        torch.cuda.synchronize()
+        optimizer.zero_grad(set_to_none=True)
+        self.graph = torch.cuda.CUDAGraph()
+        return False
+
+    def _capture_pieces(self, params, overlap):
+        """graph 1, eager all-reduce, graph 2; with `overlap` the shared trunk's backward is graph 1b between two all-reduces."""
+        net, optimizer, args, dp = self.net, self.opt, self.args, self.dp
+        self.dp_form = "graph | all-reduce | graph"
+        with capture.capturing(self.graph, **_DP_CAPTURE):
+            self.loss_dict, self.outputs, pending = forward_backward_begin(net, self.static_x, optimizer, self.agg)
             if pending is not None and overlap:
                 shared = {id(p) for p in pending.shared_params}
                 early = [p for p in params if p.grad is not None and id(p) not in shared]  # final already: task-side
@@ -292,7 +256,6 @@ class GraphedTrainStep:
             n_early = sum(p.numel() for p in early)
             self.flat_a = self.flat[:n_early]
             flatten_grads(early, out=self.flat_a)
-        ops.forget_nhwc()
         taken = {id(p) for p in early}
         late = [p for p in params if id(p) not in taken]
         self.graph_b, self.flat_b = None, None
@@ -301,7 +264,7 @@ class GraphedTrainStep:
             off = (n_early + 63) // 64 * 64  # keep the second bucket 256-byte aligned
             self.flat_b = self.flat[off: off + sum(p.numel() for p in late)]
             self.graph_b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_b, pool=self.graph.pool(), **cap):
+            with capture.capturing(self.graph_b, pool=self.graph.pool(), **_DP_CAPTURE):
                 forward_backward_finish(pending)
                 flatten_grads(late, out=self.flat_b)
         # the capture passes recorded but did not execute: materialise real gradients once
@@ -310,7 +273,7 @@ class GraphedTrainStep:
         if late:
             unflatten_into_grads(self.flat_b, late)
         self.graph2 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph2, pool=self.graph.pool(), **cap):
+        with capture.capturing(self.graph2, pool=self.graph.pool(), **_DP_CAPTURE):
             if not self._avg:
                 self.flat.div_(dp.world_size)
             if getattr(args, "max_grad_norm", None) is not None:  # same tail as train_step: clip the averaged gradient
