@@ -752,6 +752,30 @@ int movae_lpips_finalize(int layers, const double* const* partials, const int* h
 int movae_batch_u8(const uint8_t* store, const int* idx, int b, int h, int w, int c, const float* lut, int flip,
                    unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream);
 
+/* ---- batches from a device-resident RAGGED uint8 image set (csrc/data.hip; the reference's RandomResizedCrop(BICUBIC) ->
+ * RandomHorizontalFlip -> ToTensor -> Normalize on PIL images) ----
+ * blob: device uint8, the images back to back in HWC order, each starting at ANY byte.  offsets: device int64[n], the byte offset of
+ * every image (64-bit).  dims: device int[n][2] = (h, w).  boxes: device int[n][4] = (top, left, bh, bw), the crop of every image,
+ * inside it.  idx: device int[b], row numbers (the caller has range-checked rows and boxes).  lut: device float[c][256].
+ * out: device fp32 NHWC [b][s][s][c], 16-byte aligned.  out[j] = lut[ch][R], R = PIL's crop(box).resize((s, s), BICUBIC) of image
+ * idx[j] bit for bit: per axis a table of 22-bit fixed-point weights computed in fp64 (Keys' cubic a = -0.5 at
+ * (tap - center + 0.5) * (1 / filterscale), filterscale = max(1, crop side / s), taps clamped at the edges of the CROP), the
+ * horizontal pass rounded to uint8 before the vertical one, int32 accumulation.  With flip != 0 the output columns of image i are
+ * mirrored iff the Philox bit of movae_batch_u8 for (seed, epoch, i) is set.  kmax: the caller's bound on taps per output sample,
+ * 2 * ceil(2 * max(1, largest crop side / s)) + 1; a crop side may be at most 8 s (kmax 33).  The kernel cannot see a broken
+ * promise: a crop side over 8 s, or a kmax below that bound, stays inside its buffers but gives UNDEFINED pixels, not an error.
+ * One launch, a block per 32 x 32 output tile, 46.6 KB static LDS, no atomics, no workspace; capturable.
+ * Refused (MOVAE_EINVAL, nothing launched): a null pointer, b or s <= 0, c not in {1, 3}, kmax even or outside 5 .. 33, a misaligned
+ * out. */
+int movae_batch_rrc_u8(const uint8_t* blob, const long long* offsets, const int* dims, const int* boxes, const int* idx, int b, int s, int c,
+                       int kmax, const float* lut, int flip, unsigned long long seed, unsigned long long epoch, float* out,
+                       movae_stream_t stream);
+
+/* The table routine of movae_batch_rrc_u8 alone (a test entry): for each of n input sizes (device int[n]) and each of out_size output
+ * samples, k (device int[n][out_size][kmax]) = the fixed-point weights, zero past the last tap, and bounds (device
+ * int[n][out_size][2]) = (first tap, taps); taps are cut at kmax (odd, >= 5; no upper limit here: nothing is staged in LDS). */
+int movae_resample_coeffs(const int* in_sizes, int n, int out_size, int kmax, int* k, int* bounds, movae_stream_t stream);
+
 /* ---- batches of VQ code grids from device-resident stores (csrc/prior.hip; prior.DeviceCodeLoader) -----------------------------------
  * store_top: device [n][len_top], store_bottom: device [n][len_bottom] or NULL (one level only); both int16 (wide == 0) or both int32
  * (wide == 1).  idx: device int[b], row numbers into the stores.  out_top: device int64 [b][len_top]; out_bottom: int64 [b][len_bottom],

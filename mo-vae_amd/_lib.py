@@ -170,6 +170,8 @@ SIGNATURES = {
     "movae_lpips_layer": ([_p, _p, _i, _i, _i, _i, _f, _p, _z, _p], _i),
     "movae_lpips_finalize": ([_i, _p, _p, _p, _p, _i, _p, _p], _i),
     "movae_batch_u8": ([_p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
+    "movae_batch_rrc_u8": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
+    "movae_resample_coeffs": ([_p, _i, _i, _i, _p, _p, _p], _i),
     "movae_codes_batch": ([_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p], _i),
     "movae_bench_main_kernel_only": ([_i], _i),
     "movae_bench_last_kernel": ([], C.c_char_p),

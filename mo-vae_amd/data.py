@@ -5,7 +5,12 @@ Normalize(0.5, 0.5)).  Here the whole set is one uint8 array [N][H][W][C]; ToTen
 computed once with the reference's own torch expressions, and the flip of image i in epoch e is bit 31 of word 0 of
 Philox4x32-10(counter = (i, e), key = seed) -- a pure function of (seed, epoch, dataset index), the same on the host
 (ResidentImages.__getitem__) and on the device (DeviceBatchLoader -> ops.batch_u8 -> movae_batch_u8).  Nothing is downloaded: the
-readers take the files a user already has (the CIFAR pickles torchvision unpacks; .npy arrays written by tools/prepare_images.py)."""
+readers take the files a user already has (the CIFAR pickles torchvision unpacks; .npy arrays written by tools/prepare_images.py).
+
+A set whose pipeline starts with RandomResizedCrop (oxford-flower-102, utils/utils.py:367-397) is kept RAGGED instead: the images at
+their own sizes back to back in one uint8 blob (RaggedImages), the epoch's crop boxes drawn on the host from further Philox streams
+of the same counter (rrc_boxes), and the crop, PIL's 8-bit bicubic resample restated bit for bit (resize_u8), the flip and the table
+done per batch by one launch (RaggedBatchLoader -> ops.batch_rrc_u8 -> movae_batch_rrc_u8)."""
 import math
 import os
 import pickle
@@ -20,7 +25,12 @@ _M32 = np.uint64(0xFFFFFFFF)
 
 
 def philox_word0(counter_lo, counter_hi, key):
-    """Word 0 of Philox4x32-10 for the 64-bit counters (counter_lo, counter_hi) under the 64-bit key, vectorised over counter_lo
+    """Word 0 of philox_words."""
+    return philox_words(counter_lo, counter_hi, key)[0]
+
+
+def philox_words(counter_lo, counter_hi, key):
+    """The four words of Philox4x32-10 for the 64-bit counters (counter_lo, counter_hi) under the 64-bit key, vectorised over counter_lo
     (csrc/common.h: philox4x32_10 with c = (lo low word, lo high word, hi low word, hi high word), k = (key low word, key high word))."""
     lo = np.atleast_1d(np.asarray(counter_lo)).astype(np.uint64)
     hi, key = int(counter_hi) & (2 ** 64 - 1), int(key) & (2 ** 64 - 1)
@@ -33,7 +43,7 @@ def philox_word0(counter_lo, counter_hi, key):
         p0, p1 = m0 * c0, m1 * c2  # 32 x 32 bits: exact in 64
         c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & _M32, (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & _M32
         k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return c0
+    return c0, c1, c2, c3
 
 
 def flip_bits(indices, seed, epoch):
@@ -210,14 +220,255 @@ class DeviceBatchLoader(ResidentLoader):
         return out.permute(0, 3, 1, 2), self._zeros[:rows.numel()]
 
 
+# ---- ragged sets: RandomResizedCrop -----------------------------------------------------------------------
+#: RandomResizedCrop(size, scale=(0.7, 1.0), ratio=(3/4, 4/3)) of the reference's oxford-flower-102 pipeline (utils/utils.py:367-397)
+RRC_SCALE, RRC_RATIO, RRC_TRIES = (0.7, 1.0), (3.0 / 4.0, 4.0 / 3.0), 10
+#: a crop side may be at most RRC_MAX_SCALE times the output side: the filter scale is then at most 8 and a sample has at most 33 taps,
+#: which is what movae_batch_rrc_u8 sizes its LDS for
+RRC_MAX_SCALE = 8
+
+
+def rrc_boxes(dims, seed, epoch):
+    """int32 [N][4] = (top, left, bh, bw): the epoch's crop of every image of dims [N][2] = (h, w), torchvision's
+    RandomResizedCrop.get_params restated on Philox draws.  Try t = 0 .. 9 of index i reads the four words of counter
+    (i + ((t + 1) << 32), epoch) under key seed (stream t + 1 in the counter's second word; stream 0 is the flip's), as
+    u = (word + 0.5) / 2^32 in float64: area = h w (0.7 + 0.3 u0), ratio = exp(log 3/4 + u1 (log 4/3 - log 3/4)),
+    bw = rint(sqrt(area ratio)), bh = rint(sqrt(area / ratio)) (half to even, Python's round); the first try that fits the image is
+    taken, with top = (word2 (h - bh + 1)) >> 32 and left = (word3 (w - bw + 1)) >> 32.  Without one, the central crop at the nearest
+    allowed ratio.  A function of (seed, epoch, index, h, w) alone."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1, 2)
+    n = dims.shape[0]
+    h, w = dims[:, 0], dims[:, 1]
+    idx = np.arange(n, dtype=np.uint64)
+    done = np.zeros(n, dtype=bool)
+    out = np.zeros((n, 4), dtype=np.int64)
+    log_lo, log_hi = math.log(RRC_RATIO[0]), math.log(RRC_RATIO[1])
+    for t in range(RRC_TRIES):
+        w0, w1, w2, w3 = philox_words(idx + (np.uint64(t + 1) << np.uint64(32)), epoch, seed)
+        u0, u1 = (w0.astype(np.float64) + 0.5) / 2.0 ** 32, (w1.astype(np.float64) + 0.5) / 2.0 ** 32
+        area = (h * w).astype(np.float64) * (RRC_SCALE[0] + (RRC_SCALE[1] - RRC_SCALE[0]) * u0)
+        ratio = np.exp(log_lo + u1 * (log_hi - log_lo))
+        bw, bh = np.rint(np.sqrt(area * ratio)).astype(np.int64), np.rint(np.sqrt(area / ratio)).astype(np.int64)
+        ok = ~done & (0 < bw) & (bw <= w) & (0 < bh) & (bh <= h)
+        # (word * span) >> 32 with span < 2^31: exact in uint64
+        top = ((w2 * np.maximum(h - bh + 1, 1).astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
+        left = ((w3 * np.maximum(w - bw + 1, 1).astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
+        out[ok] = np.stack([top, left, bh, bw], 1)[ok]
+        done |= ok
+    if not done.all():
+        in_ratio = w.astype(np.float64) / h.astype(np.float64)
+        bw = np.where(in_ratio > RRC_RATIO[1], np.rint(h * RRC_RATIO[1]).astype(np.int64), w)
+        bh = np.where(in_ratio < RRC_RATIO[0], np.rint(w / RRC_RATIO[0]).astype(np.int64), h)
+        central = np.stack([(h - bh) // 2, (w - bw) // 2, bh, bw], 1)
+        out[~done] = central[~done]
+    return out.astype(np.int32)
+
+
+def _cubic(x):
+    """Keys' cubic, a = -0.5 (PIL's BICUBIC), in the operation order of PIL's C."""
+    a = -0.5
+    x = np.abs(x)
+    near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    far = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
+
+
+def resample_table(in_size, out_size):
+    """PIL's 8-bit coefficient table of one axis -> (k int32 [out][kmax], zero past the last tap; xmin int [out]; taps int [out]).
+    float64 throughout, the weights summed in tap order, then k = int(w / sum * 2^22 +- 0.5)."""
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support, ss = 2.0 * fs, 1.0 / fs
+    kmax = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)  # the cast truncates toward zero, like C's
+    count = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    taps = np.arange(kmax)[None, :]
+    live = taps < count[:, None]
+    wt = np.where(live, _cubic(((taps + xmin[:, None]) - center[:, None] + 0.5) * ss), 0.0)
+    ww = np.zeros(out_size)
+    for t in range(kmax):  # in tap order: numpy's own sum is pairwise
+        ww = ww + wt[:, t]
+    wt = np.where((ww != 0.0)[:, None], wt / np.where(ww != 0.0, ww, 1.0)[:, None], wt)
+    k = np.where(wt < 0, -0.5 + wt * (1 << 22), 0.5 + wt * (1 << 22)).astype(np.int64)  # truncation toward zero
+    return np.where(live, k, 0).astype(np.int32), xmin, count
+
+
+def _resample_axis1(img, out_size):
+    """uint8 [R][in][C] -> uint8 [R][out][C] along axis 1: clamp((2^21 + sum pixel * k) >> 22, 0, 255) in int32; unchanged where
+    in == out (PIL skips that pass)."""
+    if img.shape[1] == out_size:
+        return img
+    k, xmin, count = resample_table(img.shape[1], out_size)
+    acc = np.full((img.shape[0], out_size, img.shape[2]), 1 << 21, dtype=np.int32)
+    last = img.shape[1] - 1
+    for t in range(int(count.max())):  # (a tap past an output's window has weight 0: its clamped read adds nothing)
+        acc += img[:, np.minimum(xmin + t, last), :].astype(np.int32) * k[None, :, t, None]
+    return np.clip(acc >> 22, 0, 255).astype(np.uint8)
+
+
+def resize_u8(crop_hwc, size):
+    """uint8 [h][w][C] -> uint8 [size][size][C]: PIL's Image.resize((size, size), BICUBIC) of an 8-bit image, bit for bit.  The
+    horizontal pass first, rounded to uint8, then the vertical pass over it.  The host path's transform and the yardstick of
+    movae_batch_rrc_u8."""
+    crop = np.asarray(crop_hwc)
+    if crop.dtype != np.uint8 or crop.ndim != 3 or 0 in crop.shape:
+        raise ValueError(f"resize_u8: a non-empty uint8 [h][w][C] image, got {crop.dtype} {crop.shape}")
+    t = _resample_axis1(crop, size)
+    return np.ascontiguousarray(_resample_axis1(t.transpose(1, 0, 2), size).transpose(1, 0, 2))
+
+
+def rrc_kmax(max_side, size):
+    """The tap bound movae_batch_rrc_u8 takes for a set whose largest image side is max_side: 2 ceil(2 max(1, max_side / size)) + 1."""
+    return 2 * int(math.ceil(2.0 * max(1.0, max_side / size))) + 1
+
+
+class RaggedImages(torch.utils.data.Dataset):
+    """RGB images of their own sizes, back to back in HWC order in one flat uint8 `blob` (an array or a map), `index` int64 [N][3] =
+    (byte offset, h, w), with the reference's RandomResizedCrop(size, BICUBIC) -> RandomHorizontalFlip -> ToTensor -> Normalize
+    pipeline.  Item i is (CHW float32 [3][size][size], 0): the host form of what RaggedBatchLoader assembles on the device, bit for
+    bit, for the same (seed, epoch, index).  An evaluation set (train=False) resizes the whole image and never flips."""
+
+    channels = 3
+
+    def __init__(self, blob, index, size, normalize, train, seed=0):
+        index = np.asarray(index)
+        if index.ndim != 2 or index.shape[1] != 3 or index.shape[0] == 0 or index.dtype.kind not in "iu":
+            raise ValueError(f"RaggedImages: the index is a non-empty integer array [N][3] of (byte offset, h, w), got "
+                             f"{index.dtype} {index.shape}")
+        if not isinstance(blob, np.ndarray) or blob.dtype != np.uint8 or blob.ndim != 1:
+            raise ValueError(f"RaggedImages: the blob is a flat uint8 array, got {getattr(blob, 'dtype', type(blob))} "
+                             f"{getattr(blob, 'shape', None)}")
+        index = index.astype(np.int64)
+        off, h, w = index[:, 0], index[:, 1], index[:, 2]
+        bad = np.flatnonzero((h < 1) | (w < 1))
+        if bad.size:
+            raise ValueError(f"RaggedImages: index row {bad[0]} has h, w = {h[bad[0]]}, {w[bad[0]]}; both must be at least 1")
+        size = int(size)
+        over = np.flatnonzero(np.maximum(h, w) > RRC_MAX_SCALE * size)
+        if over.size:
+            r = over[0]
+            raise ValueError(f"RaggedImages: index row {r} is an image of {h[r]} x {w[r]}; a side may be at most {RRC_MAX_SCALE} x the "
+                             f"output side {size} = {RRC_MAX_SCALE * size} (the resample kernel holds at most 33 taps per sample)")
+        end = off + h * w * self.channels
+        bad = np.flatnonzero((off < 0) | (end > blob.shape[0]))
+        if bad.size:
+            raise ValueError(f"RaggedImages: index row {bad[0]} spans bytes {off[bad[0]]} .. {end[bad[0]]}, outside the blob's "
+                             f"{blob.shape[0]}")
+        order = np.argsort(off, kind="stable")
+        clash = np.flatnonzero(end[order][:-1] > off[order][1:])
+        if clash.size:
+            raise ValueError(f"RaggedImages: index rows {order[clash[0]]} and {order[clash[0] + 1]} overlap in the blob")
+        self.blob, self.offsets, self.dims = blob, np.ascontiguousarray(off), np.ascontiguousarray(index[:, 1:3]).astype(np.int32)
+        self.size, self.normalize, self.train, self.seed, self.epoch = size, bool(normalize), bool(train), int(seed), 0
+        self.kmax = rrc_kmax(int(self.dims.max()), size)
+        self.table = value_table(self.channels, normalize)
+        self._chan = torch.arange(self.channels).reshape(-1, 1, 1)
+        self._drawn = (None, None, None)  # ((seed, epoch), boxes, flips)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return self.dims.shape[0]
+
+    def boxes(self, epoch=None):
+        """int32 [N][4]: the crops of `epoch` (default: the current one); the whole image for an evaluation set."""
+        epoch = self.epoch if epoch is None else int(epoch)
+        if not self.train:
+            return np.concatenate([np.zeros_like(self.dims), self.dims], 1)
+        return rrc_boxes(self.dims, self.seed, epoch)
+
+    def _draws(self):
+        if self._drawn[0] != (self.seed, self.epoch):  # the whole epoch's boxes and bits at once: vectorised Philox passes
+            flips = flip_bits(np.arange(len(self)), self.seed, self.epoch) if self.train else np.zeros(len(self), dtype=bool)
+            self._drawn = ((self.seed, self.epoch), self.boxes(), flips)
+        return self._drawn[1], self._drawn[2]
+
+    def image(self, i):
+        """uint8 [h][w][3] of row i (a view of the blob)."""
+        h, w = self.dims[i]
+        o = int(self.offsets[i])
+        return self.blob[o:o + int(h) * int(w) * self.channels].reshape(int(h), int(w), self.channels)
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        boxes, flips = self._draws()
+        top, left, bh, bw = (int(v) for v in boxes[i])
+        img = resize_u8(np.array(self.image(i)[top:top + bh, left:left + bw]), self.size)
+        if flips[i]:
+            img = img[:, ::-1]  # after the crop and the resize: the OUTPUT columns
+        codes = torch.from_numpy(np.ascontiguousarray(img)).permute(2, 0, 1).long()
+        return self.table[self._chan, codes], 0
+
+
+class RaggedBatchLoader(ResidentLoader):
+    """ResidentLoader over the (images, labels) batches of a RaggedImages: the blob, its offsets and dims and the table are uploaded on
+    first use, the epoch's boxes with the epoch's index list, and every batch is ONE movae_batch_rrc_u8 launch into a fresh NHWC
+    buffer, handed out as its logical-NCHW view.  Labels are zeros, like item[1]."""
+
+    noun = "images"
+
+    def __init__(self, ds, batch_size, device, shuffle, rank=0, world_size=1, seed=0):
+        if not isinstance(ds, RaggedImages):
+            raise TypeError(f"RaggedBatchLoader needs a RaggedImages, got {type(ds).__name__}")
+        super().__init__(ds, batch_size, device, shuffle, rank, world_size, seed)
+        self._store = self._offsets = self._dims = self._boxes = self._lut = self._zeros = None
+
+    def _upload(self):
+        ds, blob = self.dataset, self.dataset.blob
+        key = (blob.__array_interface__["data"][0], blob.shape, blob.strides, str(self.device))  # (one copy per host blob: _STORES)
+        store = _STORES.get(key)
+        if store is None:
+            refuse_if_too_big(int(blob.nbytes) + len(ds) * 32 + ds.table.numel() * 4, self.device, "the image set needs",
+                              "keep it on the host with --data_loader host")
+            store = torch.empty(blob.shape, dtype=torch.uint8, device=self.device)
+            step = 256 << 20  # staged through <= 256 MB of host memory (the blob may be a map)
+            for s in range(0, blob.shape[0], step):
+                store[s:s + step].copy_(torch.from_numpy(np.array(blob[s:s + step])))
+            _STORES[key] = store
+        self._store = store
+        self._offsets = torch.from_numpy(ds.offsets).to(self.device)
+        self._dims = torch.from_numpy(ds.dims).to(self.device)
+        self._lut = ds.table.to(self.device)
+        self._zeros = torch.zeros(self.batch_size, dtype=torch.long, device=self.device)
+
+    def _checked(self, idx):
+        if idx and not 0 <= min(idx) <= max(idx) < len(self.dataset):
+            raise RuntimeError("RaggedBatchLoader: index list outside the set")
+        return torch.tensor(idx, dtype=torch.int32)
+
+    def _device_indices(self):
+        if self._idx[0] != self.epoch:  # the epoch's crops go up with its index list, checked on the host like it
+            ds = self.dataset
+            boxes = ds.boxes(self.epoch)
+            top, left, bh, bw = boxes.T
+            if not ((top >= 0) & (left >= 0) & (bh >= 1) & (bw >= 1) & (top + bh <= ds.dims[:, 0]) & (left + bw <= ds.dims[:, 1])).all():
+                raise RuntimeError("RaggedBatchLoader: a crop box outside its image")
+            rows = super()._device_indices()
+            self._boxes = torch.from_numpy(boxes).to(self.device)
+            return rows
+        return self._idx[1]
+
+    def _batch(self, rows):
+        ds = self.dataset
+        out = ops.batch_rrc_u8(self._store, self._offsets, self._dims, self._boxes, rows, ds.size, ds.channels, ds.kmax, self._lut,
+                               flip=ds.train, seed=ds.seed, epoch=self.epoch)
+        return out.permute(0, 3, 1, 2), self._zeros[:rows.numel()]
+
+
 # ---- readers -----------------------------------------------------------------------------------------------------------------------
 #: name -> image side of the .npy sets: <data_dir>/<name>_train_u8.npy and <name>_test_u8.npy, uint8 [N][S][S][3]
 NPY_SETS = {"celeba": 64, "celeba-128": 128, "celeba-hq": 256, "afhq": 256}
 ALIASES = {"animal-face": "afhq"}
 REFUSED = {
     "imagenet": "1.28 M images of 256 x 256 are 252 GB as uint8: they do not fit one device and would have to stream from host memory",
-    "oxford-flower-102": "its training transform is RandomResizedCrop, a per-item resample that the table-and-flip kernel does not do",
 }
+#: name -> image side of the ragged sets: <data_dir>/<name>_train_ragged_u8.npy + <name>_train_ragged_index.npy (the images at their
+#: own sizes, cropped and resampled per item) and <name>_test_u8.npy, uint8 [N][S][S][3]; written by tools/prepare_images.py --ragged
+RAGGED_SETS = {"oxford-flower-102": 256}
 
 
 def _need(path):
@@ -253,13 +504,41 @@ def _npy(path, size):
     return a
 
 
+def _ragged(name, key, data_dir, normalize, max_items):
+    size = RAGGED_SETS[key]
+    blob_path, index_path = (os.path.join(data_dir, f"{key}_train_ragged_{part}.npy") for part in ("u8", "index"))
+    for path in (blob_path, index_path):
+        if not os.path.isfile(path):
+            # NotImplementedError, not FileNotFoundError: without its prepared files this set is still "not available" to a caller
+            # written before the ragged path existed (tests/test_data_host.py pins type and the word RandomResizedCrop)
+            raise NotImplementedError(
+                f"dataset {name!r}: its RandomResizedCrop pipeline reads {path}, written by tools/prepare_images.py --ragged from the "
+                f"images on disk; that file is missing, and nothing is downloaded")
+    blob = np.load(blob_path, mmap_mode="r", allow_pickle=False)
+    index = np.load(index_path, allow_pickle=False)
+    if blob.dtype != np.uint8 or blob.ndim != 1:
+        raise ValueError(f"{blob_path}: expected a flat uint8 array, got {blob.dtype} {blob.shape}")
+    if index.dtype != np.int64 or index.ndim != 2 or index.shape[1] != 3 or index.shape[0] == 0:
+        raise ValueError(f"{index_path}: expected int64 [N][3] of (byte offset, h, w), got {index.dtype} {index.shape}")
+    test = _npy(os.path.join(data_dir, f"{key}_test_u8.npy"), size)
+    if max_items:
+        index, test = index[:max_items], test[:max(1, max_items // 10)]
+        # the blob up to the farthest end of a kept image (a view of the map): the device loader then checks the free memory for,
+        # and uploads, what the run can read, not the whole file
+        blob = blob[:max(0, int((index[:, 0] + 3 * index[:, 1] * index[:, 2]).max()))]
+    return RaggedImages(blob, index, size, normalize, train=True), ResidentImages(test, normalize, train=False), size
+
+
 def get_real_dataset(name, data_dir="./data", normalize=False, max_items=None):
-    """-> (train ResidentImages, test ResidentImages, image side) for a real dataset name of the reference (case-insensitive), or None
-    for a name this module does not know.  `max_items` keeps the first max_items train and the first max(1, max_items // 10) test images."""
+    """-> (train set, test ResidentImages, image side) for a real dataset name of the reference (case-insensitive), or None for a name
+    this module does not know.  The train set is a ResidentImages, or a RaggedImages for a set whose pipeline is RandomResizedCrop.
+    `max_items` keeps the first max_items train and the first max(1, max_items // 10) test images."""
     key = name.lower()
     key = ALIASES.get(key, key)
     if key in REFUSED:
         raise NotImplementedError(f"dataset {name!r}: {REFUSED[key]}")
+    if key in RAGGED_SETS:
+        return _ragged(name, key, data_dir, normalize, max_items)
     if key == "cifar10":
         root = os.path.join(data_dir, "cifar-10-batches-py")
         train, test = _cifar([os.path.join(root, f"data_batch_{i}") for i in range(1, 6)], [os.path.join(root, "test_batch")])

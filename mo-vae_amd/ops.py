@@ -2516,6 +2516,40 @@ def batch_u8(store, idx, lut, flip, seed, epoch):
     return out
 
 
+def batch_rrc_u8(blob, offsets, dims, boxes, idx, size, channels, kmax, lut, flip, seed, epoch):
+    """One RandomResizedCrop batch from a device-resident ragged image set (csrc/data.hip; data.RaggedBatchLoader): blob uint8 (the
+    images back to back, HWC), offsets int64 [N] (bytes), dims int32 [N][2] = (h, w), boxes int32 [N][4] = (top, left, bh, bw), idx
+    int32 [B] (rows and boxes range-checked by the caller), lut float32 [C][256] -> a fresh fp32 NHWC [B][size][size][C]:
+    out[j] = lut[ch][PIL's crop(box).resize((size, size), BICUBIC) of image idx[j]], bit for bit, its columns mirrored where the Philox
+    bit of (seed, epoch, idx[j]) says so and `flip` is set.  kmax: 2 ceil(2 max(1, largest crop side / size)) + 1.  The kernel cannot
+    check either promise: a crop side over 8 * size, or a kmax below that bound, gives undefined pixels (inside the buffers), not an
+    error -- data.RaggedImages is what guarantees both.  One launch; not differentiable (a data source)."""
+    L.require_gpu(blob)
+    n = offsets.numel()
+    assert blob.dtype == torch.uint8 and blob.dim() == 1 and blob.is_contiguous(), "batch_rrc_u8: blob is flat contiguous uint8"
+    for t, dt, shape, what in ((offsets, torch.int64, (n,), "offsets is int64 [N]"), (dims, torch.int32, (n, 2), "dims is int32 [N][2]"),
+                               (boxes, torch.int32, (n, 4), "boxes is int32 [N][4]"), (idx, torch.int32, (idx.numel(),), "idx is int32 [B]"),
+                               (lut, torch.float32, (channels, 256), f"lut is float32 [{channels}][256]")):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == blob.device, f"batch_rrc_u8: {what}"
+    out = torch.empty((idx.numel(), size, size, channels), dtype=torch.float32, device=blob.device)
+    _call("movae_batch_rrc_u8", blob.data_ptr(), offsets.data_ptr(), dims.data_ptr(), boxes.data_ptr(), idx.data_ptr(), idx.numel(), size,
+          channels, kmax, lut.data_ptr(), int(bool(flip)), int(seed), int(epoch), out.data_ptr(), _st(blob))
+    return out
+
+
+def resample_coeffs(in_sizes, out_size, kmax):
+    """The coefficient tables of batch_rrc_u8 for the input sizes `in_sizes` (device int32 [n]) at `out_size` output samples, computed
+    by the kernel's own routine -> (k int32 [n][out_size][kmax], zero past the last tap; bounds int32 [n][out_size][2] = (first tap,
+    taps))."""
+    L.require_gpu(in_sizes)
+    assert in_sizes.dtype == torch.int32 and in_sizes.dim() == 1 and in_sizes.is_contiguous(), "resample_coeffs: in_sizes is int32 [n]"
+    n = in_sizes.numel()
+    k = torch.empty((n, out_size, kmax), dtype=torch.int32, device=in_sizes.device)
+    bounds = torch.empty((n, out_size, 2), dtype=torch.int32, device=in_sizes.device)
+    _call("movae_resample_coeffs", in_sizes.data_ptr(), n, out_size, kmax, k.data_ptr(), bounds.data_ptr(), _st(in_sizes))
+    return k, bounds
+
+
 def check_rows(idx, n):
     """Host-side range check of a row list (a sequence or a CPU tensor) against a store of n rows: ValueError before anything is
     launched.  -> the list as a CPU int32 tensor."""

@@ -22,7 +22,8 @@ from . import aggregation
 from . import autojac
 from . import capture
 from .aggregation import COMFORT, MGDA
-from .data import ALIASES, NPY_SETS, DeviceBatchLoader, ResidentImages, get_real_dataset
+from .data import ALIASES, NPY_SETS, RAGGED_SETS, DeviceBatchLoader, RaggedBatchLoader, RaggedImages, ResidentImages, ResidentLoader, \
+    get_real_dataset
 from .metrics import ReconMetricAccumulator, build_hv_indicator
 from .models import get_network
 from .optim import FusedAdam, FusedAdamW, clip_grad_norm_
@@ -508,8 +509,9 @@ class SyntheticImages(torch.utils.data.Dataset):
 
 def get_dataset(name, data_dir="./data", normalize=False, max_items=None):
     """utils/utils.py:144-426 -> (train set, test set, image side).  The reference's names (case-insensitive) are read from files
-    already under `data_dir` as uint8 sets (data.get_real_dataset: nothing is downloaded; imagenet and oxford-flower-102 are refused,
-    with the reason); synthetic_* names give seeded shape-compatible data."""
+    already under `data_dir` as uint8 sets (data.get_real_dataset: nothing is downloaded; oxford-flower-102 is a ragged set, its images
+    at their own sizes for the per-item RandomResizedCrop, written by tools/prepare_images.py --ragged; imagenet is refused, with the
+    reason); synthetic_* names give seeded shape-compatible data."""
     key = name.lower()
     if key in SYNTHETIC:
         size, n = SYNTHETIC[key]
@@ -519,21 +521,23 @@ def get_dataset(name, data_dir="./data", normalize=False, max_items=None):
     if real is not None:
         return real
     raise NotImplementedError(
-        f"dataset {name!r} is not known; use one of {sorted(['cifar10', 'cifar100', *NPY_SETS, *ALIASES])} (read from --data_dir) or "
-        f"{sorted(SYNTHETIC)}")
+        f"dataset {name!r} is not known; use one of {sorted(['cifar10', 'cifar100', *NPY_SETS, *RAGGED_SETS, *ALIASES])} "
+        f"(read from --data_dir) or {sorted(SYNTHETIC)}")
 
 
 def make_loader(ds, batch_size, device, args, shuffle, sampler=None, dp=None):
     """The loader of one stage.  `--data_loader auto` (default): a ResidentImages set gets the device loader (data.DeviceBatchLoader:
-    the set in HBM, one launch per batch), anything else the DataLoader this build always used; `host` forces the DataLoader, `device`
+    the set in HBM, one launch per batch), a RaggedImages set its own (data.RaggedBatchLoader: the same, the launch also crops and
+    resamples), anything else the DataLoader this build always used; `host` forces the DataLoader, `device`
     insists on the device loader.  `dp` (with the device loader) / `sampler` (with the DataLoader) shard a training set over the ranks."""
     if uses_device_loader(ds, args):
         rank, world = (dp.rank, dp.world_size) if dp is not None else (0, 1)
-        return DeviceBatchLoader(ds, batch_size, device, shuffle, rank=rank, world_size=world, seed=args.seed or 0)
+        cls = RaggedBatchLoader if isinstance(ds, RaggedImages) else DeviceBatchLoader
+        return cls(ds, batch_size, device, shuffle, rank=rank, world_size=world, seed=args.seed or 0)
     # pinning in the main thread (num_workers == 0) allocates and frees page-locked memory per batch: ~20 ms per batch on ROCm.
-    # A ResidentImages set gets fresh workers per epoch: a worker holds a COPY of the set, taken when it starts, and persistent
-    # workers would keep the epoch of that moment -- every later epoch would repeat its flips
-    persistent = args.num_workers > 0 and not isinstance(ds, ResidentImages)
+    # A ResidentImages or RaggedImages set gets fresh workers per epoch: a worker holds a COPY of the set, taken when it starts, and
+    # persistent workers would keep the epoch of that moment -- every later epoch would repeat its flips (and crops)
+    persistent = args.num_workers > 0 and not isinstance(ds, (ResidentImages, RaggedImages))
     kw = dict(num_workers=args.num_workers, pin_memory=args.num_workers > 0, drop_last=False, persistent_workers=persistent)
     return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=shuffle and sampler is None, sampler=sampler, **kw)
 
@@ -541,7 +545,7 @@ def make_loader(ds, batch_size, device, args, shuffle, sampler=None, dp=None):
 def uses_device_loader(ds, args):
     """Whether make_loader gives `ds` the device loader under `--data_loader` (ValueError: `device` asked for a set with no uint8 form)."""
     mode = getattr(args, "data_loader", "auto")
-    resident = isinstance(ds, ResidentImages)
+    resident = isinstance(ds, (ResidentImages, RaggedImages))
     if mode == "device" and not resident:
         raise ValueError(f"--data_loader device needs a dataset held as uint8 images; {type(ds).__name__} is generated on the host")
     return resident and mode in ("auto", "device")
@@ -734,8 +738,8 @@ def main(args):
         sampler = torch.utils.data.distributed.DistributedSampler(train_ds, num_replicas=dp.world_size, rank=dp.rank,
                                                                   shuffle=True, seed=args.seed or 0)
     for ds in (train_ds, test_ds):
-        if isinstance(ds, ResidentImages):
-            ds.seed = args.seed or 0  # the flips follow --seed, on the device and on the host alike
+        if isinstance(ds, (ResidentImages, RaggedImages)):
+            ds.seed = args.seed or 0  # the flips (and crops) follow --seed, on the device and on the host alike
     train_loader = make_loader(train_ds, per_rank_bs, device, args, shuffle=True, sampler=sampler, dp=dp)
     test_loader = make_loader(test_ds, per_rank_bs, device, args, shuffle=False)
     args.dataset_size = len(train_ds)
@@ -786,10 +790,10 @@ def main(args):
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
-        if isinstance(train_loader, DeviceBatchLoader):
-            train_loader.set_epoch(epoch)  # the epoch's shuffle and flips
-        elif isinstance(train_ds, ResidentImages):
-            train_ds.set_epoch(epoch)  # the host path's flips (its order is the DataLoader's / the sampler's)
+        if isinstance(train_loader, ResidentLoader):
+            train_loader.set_epoch(epoch)  # the epoch's shuffle, flips and crops
+        elif isinstance(train_ds, (ResidentImages, RaggedImages)):
+            train_ds.set_epoch(epoch)  # the host path's flips and crops (its order is the DataLoader's / the sampler's)
         if isinstance(aggregator, COMFORT):  # main.py:1290-1291
             aggregator.set_epoch(epoch, args.epochs)
         t0 = time.time()

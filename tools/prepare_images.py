@@ -5,6 +5,13 @@
 Per image: RGB, an optional centre crop, then Image.resize((S, S), Image.BICUBIC) -- what the reference's CenterCrop + Resize(BICUBIC,
 antialias=True) do to a PIL image (utils/utils.py:262-274).  Files are taken in sorted order.  --split F sends the first F of them to
 the train file and the rest to the test file; --split_list FILE names the TRAIN files, one per line (the others are the test set).
+
+    python tools/prepare_images.py --src jpg --out data --name oxford-flower-102 --size 256 --ragged --split_list trnval.txt
+
+--ragged is for a set whose training pipeline is RandomResizedCrop (oxford-flower-102: train + validation images as the train part).
+The TRAIN images are not resampled: <name>_train_ragged_u8.npy holds them back to back as RGB bytes in HWC order, one flat uint8
+array, and <name>_train_ragged_index.npy int64 [N][3] = (byte offset, h, w); the crop and the resample happen per item at training
+time.  The test part is written as always (the reference's Resize((S, S)) of the whole image).
 Pure host code; nothing is downloaded."""
 import argparse
 import os
@@ -66,21 +73,63 @@ def convert(src, out, name, size, center_crop=None, split=None, split_list=None)
     return written
 
 
+def convert_ragged(src, out, name, size, split=None, split_list=None):
+    """Writes <out>/<name>_train_ragged_u8.npy and <name>_train_ragged_index.npy (the train images at their own sizes) and, when the
+    split leaves any, <out>/<name>_test_u8.npy (the test images resized whole).  -> the paths written."""
+    names = list_images(src)
+    if not names:
+        raise FileNotFoundError(f"no images ({', '.join(EXTENSIONS)}) in {src}")
+    os.makedirs(out, exist_ok=True)
+    train, test = split_names(names, split, split_list)
+    if not train:
+        raise ValueError("the split leaves no train images")
+    index = np.zeros((len(train), 3), dtype=np.int64)
+    for i, n in enumerate(train):  # a first pass over the headers alone: the sizes give the offsets
+        with Image.open(os.path.join(src, n)) as img:
+            w, h = img.size
+        index[i] = (index[i - 1, 0] + 3 * index[i - 1, 1] * index[i - 1, 2] if i else 0, h, w)
+    total = int(index[-1, 0] + 3 * index[-1, 1] * index[-1, 2])
+    blob_path, index_path = (os.path.join(out, f"{name}_train_ragged_{part}.npy") for part in ("u8", "index"))
+    blob = np.lib.format.open_memmap(blob_path, mode="w+", dtype=np.uint8, shape=(total,))
+    for (off, h, w), n in zip(index, train):
+        px = np.asarray(Image.open(os.path.join(src, n)).convert("RGB"), dtype=np.uint8)
+        assert px.shape == (h, w, 3), (n, px.shape, h, w)
+        blob[off:off + 3 * h * w] = px.reshape(-1)
+    blob.flush()
+    del blob
+    np.save(index_path, index, allow_pickle=False)
+    written = [blob_path, index_path]
+    if test:
+        path = os.path.join(out, f"{name}_test_u8.npy")
+        arr = np.lib.format.open_memmap(path, mode="w+", dtype=np.uint8, shape=(len(test), size, size, 3))
+        for i, n in enumerate(test):
+            arr[i] = load_image(os.path.join(src, n), size)
+        arr.flush()
+        del arr
+        written.append(path)
+    return written
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--src", required=True, help="folder of images")
     p.add_argument("--out", required=True, help="the --data_dir of training")
-    p.add_argument("--name", required=True, help="celeba | celeba-128 | celeba-hq | afhq")
+    p.add_argument("--name", required=True, help="celeba | celeba-128 | celeba-hq | afhq | oxford-flower-102 (with --ragged)")
     p.add_argument("--size", type=int, required=True, help="S: 64 / 128 / 256")
     p.add_argument("--center_crop", type=int, default=None, help="148 (celeba), 178 (celeba-128)")
     p.add_argument("--split", type=float, default=None, help="fraction of the sorted files that goes to the train file")
     p.add_argument("--split_list", type=str, default=None, help="text file naming the train files, one per line")
+    p.add_argument("--ragged", action="store_true", help="keep the train images at their own sizes (a RandomResizedCrop set)")
     a = p.parse_args(argv)
     listed = None
     if a.split_list:
         with open(a.split_list) as f:
             listed = [line.strip() for line in f if line.strip()]
-    for path in convert(a.src, a.out, a.name, a.size, a.center_crop, a.split, listed):
+    if a.ragged and a.center_crop:
+        p.error("--ragged keeps whole images: it takes no --center_crop")
+    paths = convert_ragged(a.src, a.out, a.name, a.size, a.split, listed) if a.ragged else \
+        convert(a.src, a.out, a.name, a.size, a.center_crop, a.split, listed)
+    for path in paths:
         print(path)
 
 
