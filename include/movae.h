@@ -788,6 +788,37 @@ int movae_resample_coeffs(const int* in_sizes, int n, int out_size, int kmax, in
 int movae_codes_batch(const void* store_top, const void* store_bottom, int wide, int n, int len_top, int len_bottom, const int* idx, int b,
                       int64_t* out_top, int64_t* out_bottom, movae_stream_t stream);
 
+/* ---- forward-only inference kernels of the Inception-v3 feature stack behind rFID (csrc/inception.hip; the reference's
+ * utils/metrics.py:360-450 InceptionV3, :513-615 calculate_fid) ------------------------------------------------------------------------
+ * All tensors fp32; activations NHWC; no workspace, no atomics, one launch each, bit-identical from run to run; capturable.
+ *
+ * movae_infer_conv2d: y[n][ho][wo][coff + o] = max(0, scale[o] * sum_{kh,kw,c} x[n][ho*stride - pad_h + kh][wo*stride - pad_w + kw][c]
+ * * w[o][kh][kw][c] + shift[o]) with ho = (h + 2 pad_h - kh) / stride + 1 (likewise wo), zero padding.  x [n][h][w][ci] contiguous,
+ * w [co][kh][kw][ci] contiguous, scale / shift [co] (an eval-mode BatchNorm folded by the caller; the ReLU is always applied).  y is a
+ * buffer of `ldy` channels per pixel ([n][ho][wo][ldy]); the result goes to channels coff .. coff + co - 1 and no other element of y
+ * is written (a branch writes its slice of a concat buffer).  An implicit GEMM (M = n ho wo, N = co, K = kh kw ci) on the exact-fp32
+ * MFMA: every product is rounded once and summed in k order.  Any ci, co >= 1; 16-byte loads where ci % 4 == 0 and x, w are 16-byte
+ * aligned.  Refused (MOVAE_EINVAL, nothing launched): a null pointer, a dimension <= 0, kh or kw above 7, a pad >= its kernel side,
+ * an empty output, ldy < coff + co or coff < 0, n ho wo or an operand's element count at or above 2^31.
+ *
+ * movae_infer_pool3x3: a 3x3 window over x [n][h][w][c] into channels coff .. coff + c - 1 of y [n][ho][wo][ldy].  mode 0: maximum,
+ * stride 2, no padding (ho = (h - 3) / 2 + 1; h, w >= 3).  mode 1: average, stride 1, padding 1, the sum of the in-bounds taps divided
+ * by 9 everywhere (count_include_pad), summed in fp64 and rounded once (ho = h).
+ * movae_infer_global_mean: y[n][c] = mean over the hw pixels of x [n][hw][c], summed in fp64 in pixel order, rounded once.
+ *
+ * movae_inception_prep: x [n][3][h][w] contiguous NCHW (h, w <= 299) -> y [n][299][299][3] NHWC: v = clamp(0.5 x + 0.5, 0, 1) ALWAYS
+ * (calculate_fid's `denormalize`, applied to [0, 1] data too); the shorter side resized to 299 (the other to floor(299 * long / short))
+ * with the antialiased bicubic of F.interpolate -- for an enlargement the separable Keys kernel, a = -0.5, at (tap - scale * (i + 0.5)
+ * + 0.5), taps cut at the border and the weights renormalised, no clamp afterwards; the 299 x 299 centre crop (offset round-half-even
+ * of (side - 299) / 2); then (v - mean_c) / std_c with the ImageNet mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225).  Weights
+ * and sums are fp64, the result is rounded once.  Refused: a null pointer, n, h or w <= 0, a side above 299 (that needs a true
+ * antialiasing filter). */
+int movae_infer_conv2d(const float* x, const float* w, const float* scale, const float* shift, float* y, int n, int h, int wd, int ci,
+                       int co, int kh, int kw, int stride, int pad_h, int pad_w, int ldy, int coff, movae_stream_t stream);
+int movae_infer_pool3x3(const float* x, float* y, int n, int h, int w, int c, int mode, int ldy, int coff, movae_stream_t stream);
+int movae_infer_global_mean(const float* x, float* y, int n, int hw, int c, movae_stream_t stream);
+int movae_inception_prep(const float* x, float* y, int n, int h, int w, movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

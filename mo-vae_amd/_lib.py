@@ -169,6 +169,10 @@ SIGNATURES = {
     "movae_lpips_ws_bytes": ([_i, _i, _i, _i], _z),
     "movae_lpips_layer": ([_p, _p, _i, _i, _i, _i, _f, _p, _z, _p], _i),
     "movae_lpips_finalize": ([_i, _p, _p, _p, _p, _i, _p, _p], _i),
+    "movae_infer_conv2d": ([_p, _p, _p, _p, _p] + [_i] * 12 + [_p], _i),
+    "movae_infer_pool3x3": ([_p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
+    "movae_infer_global_mean": ([_p, _p, _i, _i, _i, _p], _i),
+    "movae_inception_prep": ([_p, _p, _i, _i, _i, _p], _i),
     "movae_batch_u8": ([_p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_batch_rrc_u8": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_resample_coeffs": ([_p, _i, _i, _i, _p, _p, _p], _i),

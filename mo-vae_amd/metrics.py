@@ -10,6 +10,10 @@ normalisation, the fused SSIM / MSE / signal-variance pass, and a fixed-order fi
 input normalisation and the feature stack of the perceptual loss, extended to relu4_3 (perceptual.LpipsFeatures), then one
 movae_lpips_layer per tapped layer and one movae_lpips_finalize (csrc/lpips.hip); `lpips_into` is the form without a host read.
 
+`fid` is the reference's calculate_fid (utils/metrics.py:513-615) on Inception-v3 weights the caller registered
+(inception.use_inception_weights): `inception_features` runs the input pipeline and the feature stack on the forward-only kernels of
+csrc/inception.hip, `fid_from_features` is the Frechet distance of the two feature sets in float64.
+
 `ReconMetricAccumulator` is the collection of main.py:376-463 without the host copies: (real, recon) pairs are taken batch by
 batch up to `max_samples`, cut into the reference's 128-sample chunks (the chunks of the concatenated collection, so they
 straddle loader batches), and each chunk is scored on the device as soon as it is complete.  `result()` is the one host read.
@@ -218,6 +222,106 @@ def lpips(img1, img2, device=None, net='vgg'):
     return float(lpips_into(out, img1, img2)[0].item())
 
 
+# ---- FID ------------------------------------------------------------------------------------------------------------------
+_inception_features = {}  # device -> (the registered weights, the InceptionFeatures built from them)
+
+
+def _inception_weights():
+    from . import inception
+
+    return inception.registered_inception_weights()
+
+
+def _inception_on(device, weights):
+    """The Inception extractor of this device, built once per registration (a new registration is a new object)."""
+    from . import inception
+
+    key = (device.type, device.index)
+    hit = _inception_features.get(key)
+    if hit is None or hit[0] is not weights:
+        hit = (weights, inception.InceptionFeatures(weights, device))
+        _inception_features[key] = hit
+    return hit[1]
+
+
+def release_inception_buffers(device=None):
+    """Drops the extractor's cached activation buffers (several GB for a 128-image chunk at the real widths) of one device or of
+    all; the weights stay, and the next call allocates the buffers again.  The final evaluation calls it when it is done."""
+    want = None if device is None else torch.device(device)
+    for (kind, index), (_, net) in _inception_features.items():
+        if want is None or (kind == want.type and want.index in (None, index)):
+            net.release()
+
+
+@torch.no_grad()
+def inception_features_into(out, images, chunk=CHUNK):
+    """The pooled Inception-v3 features of `images` ([N, 3, h, w] on the device, any float dtype, h, w <= 299) into out
+    ([N, D] fp32 on the same device), `chunk` images at a time: calculate_fid's input pipeline in one launch (ops.inception_prep:
+    the unconditional 0.5 x + 0.5 and clamp, the antialiased bicubic resize to 299 with the centre crop, the ImageNet
+    normalisation), then the stack (inception.InceptionFeatures).  No host read.  A side above 299 raises NotImplementedError."""
+    weights = _inception_weights()
+    if weights is None:
+        raise RuntimeError("FID needs Inception-v3 weights: register them with inception.use_inception_weights(path, state_dict or "
+                           "module); nothing is downloaded")
+    images = _operand(images)
+    if images.size(1) != 3:
+        raise ValueError(f"the Inception features take 3-channel images, got shape {tuple(images.shape)}")
+    n = images.size(0)
+    net = _inception_on(images.device, weights)
+    if tuple(out.shape) != (n, net.feature_dim) or out.dtype != torch.float32 or out.device != images.device:
+        raise ValueError(f"out must be a float32 [{n}, {net.feature_dim}] tensor on the images' device")
+    for lo in range(0, n, int(chunk)):
+        part = images[lo: lo + int(chunk)]
+        out[lo: lo + part.size(0)].copy_(net.features_of(part))
+    return out
+
+
+def inception_features(images, chunk=CHUNK):
+    """-> [N, D] fp32 on the device (D = 2048 at the real widths): extract_inception_features of utils/metrics.py:618-653 without
+    the host copy."""
+    from . import inception
+
+    weights = _inception_weights()
+    dim = weights.feature_dim if weights is not None else inception.InceptionWeights.feature_dim
+    out = torch.empty((images.size(0), dim), dtype=torch.float32, device=images.device)
+    return inception_features_into(out, images, chunk) if images.size(0) else out
+
+
+def _sqrt_psd(m):
+    lam, vec = torch.linalg.eigh(m)
+    return (vec * lam.clamp_min(0).sqrt()) @ vec.T
+
+
+def fid_from_features(real, fake):
+    """utils/metrics.py:656-679 fid_from_features: |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2), means and covariances
+    (divisor N - 1, np.cov's) in float64.  The trace term is the sum of the square roots of the eigenvalues of the symmetric
+    S1^(1/2) S2 S1^(1/2) -- the same spectrum as S1 S2 -- from two torch.linalg.eigh calls in float64 on the host, negative
+    eigenvalues (rounding of a singular covariance) clamped to 0; no scipy.  Accepts tensors (any device) or arrays [N, D]."""
+    f = [torch.as_tensor(t).detach().to(dtype=torch.float64) for t in (real, fake)]
+    if f[0].numel() == 0 or f[1].numel() == 0:
+        return float("nan")
+    mu, cov = [], []
+    for t in f:
+        m = t.mean(dim=0)
+        d = t - m
+        mu.append(m.cpu())
+        cov.append(((d.T @ d) / (t.size(0) - 1)).cpu())
+    diff = mu[0] - mu[1]
+    root = _sqrt_psd(cov[0])
+    inner = root @ cov[1] @ root
+    lam = torch.linalg.eigvalsh((inner + inner.T) * 0.5)
+    tr = lam.clamp_min(0).sqrt().sum()
+    return float(diff.dot(diff) + torch.trace(cov[0]) + torch.trace(cov[1]) - 2.0 * tr)
+
+
+def fid(real, fake, chunk=CHUNK):
+    """utils/metrics.py:513-615 calculate_fid on the registered Inception-v3 weights: NaN for an empty operand, else
+    fid_from_features of the two sets' inception_features."""
+    if real.numel() == 0 or fake.numel() == 0:
+        return float("nan")
+    return fid_from_features(inception_features(real, chunk), inception_features(fake, chunk))
+
+
 # ---- collection in the reference's chunks ------------------------------------------------------------------------------
 class ChunkPlanner:
     """Host-side bookkeeping of main.py:376-463 + :335-373: which samples of each loader batch are taken (the `take` cut at
@@ -253,8 +357,12 @@ def plan_chunks(batch_sizes, max_samples, chunk=CHUNK):
 
 
 class ReconMetricAccumulator:
-    """(real, recon) batches -> the reference's rFID / PSNR / SSIM / LPIPS dict.  rFID needs a pretrained Inception: NaN, as the
-    reference gives when it cannot load it.  LPIPS is scored per chunk (lpips_into) when VGG16 weights with the conv4 block are
+    """(real, recon) batches -> the reference's rFID / PSNR / SSIM / LPIPS dict.  rFID needs a pretrained Inception: with weights
+    registered (inception.use_inception_weights) the [N, D] features of real and recon are extracted chunk by chunk and kept on the
+    device (2 x 10 000 x 2048 fp32 = 164 MB), and result() gives fid_from_features of the two sets under the reference's conditions
+    (main.py:368: width >= min_size_for_lpips, n >= 2; 3 channels -- its TF.normalize raises on 1-channel images and the except
+    leaves NaN); with nothing registered it is NaN, as the reference gives when it cannot load the network, and the Inception path
+    allocates nothing.  LPIPS is scored per chunk (lpips_into) when VGG16 weights with the conv4 block are
     registered (perceptual.use_vgg16_weights) and the images are at least 32 wide, the reference's min_size_for_lpips; else NaN.
     At most one chunk is staged on the device (a chunk that lies inside one batch is scored straight from the batch's
     tensors); every chunk is scored when it completes and its ssim / psnr / lpips stay on the device until result()."""
@@ -268,6 +376,8 @@ class ReconMetricAccumulator:
         self._fill = 0
         self._outs = []
         self._lpips = None
+        self._fid = None   # decided at the first chunk, like _lpips
+        self._feats = ([], [])  # per chunk: the [n, D] features of real / recon
 
     @property
     def full(self):
@@ -286,6 +396,15 @@ class ReconMetricAccumulator:
             lp = lpips_into(torch.empty(1 + real.size(0), dtype=torch.float32, device=real.device), real, recon)
             vals = torch.cat([vals, lp[:1]])
         self._outs.append(vals)
+        if self._fid is None:
+            self._fid = _inception_weights() is not None and real.size(-1) >= LPIPS_MIN_WIDTH and real.size(1) == 3
+        if self._fid:
+            try:
+                for keep, images in zip(self._feats, (real, recon)):
+                    keep.append(inception_features(images, self.chunk))
+            except NotImplementedError as e:  # (a side above 299: main.py:371-372 prints a warning and leaves NaN)
+                print(f"Warning: rFID computation failed: {e}")
+                self._fid, self._feats = False, ([], [])
 
     @torch.no_grad()
     def add(self, real, recon):
@@ -321,6 +440,10 @@ class ReconMetricAccumulator:
             out["psnr"] = float(np.mean(vals[:, 1]))
             if vals.shape[1] > 2:
                 out["lpips"] = float(np.mean(vals[:, 2]))
+        if self._fid and self.count >= 2:
+            out["rfid"] = fid_from_features(torch.cat(self._feats[0]), torch.cat(self._feats[1]))
+        if self._fid:
+            release_inception_buffers(self.device)
         return out
 
 

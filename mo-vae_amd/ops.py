@@ -2634,3 +2634,98 @@ class MaxPool2x2(Function):
 
 def max_pool2x2(x):
     return MaxPool2x2.apply(x)
+
+
+# ---- forward-only inference kernels of the Inception-v3 feature stack (csrc/inception.hip; inception.py, metrics.fid) ------------------
+# No autograd: the operands are frozen weights and images nobody differentiates.  `out` / `offset`: the NHWC buffer a result is written
+# into and the first of its channels the result takes -- a branch of an Inception block writes its slice of the block's concat buffer.
+def _infer_operand(t, what):
+    L.require_gpu(t)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor, got {t.dtype} {tuple(t.shape)} (contiguous: {t.is_contiguous()})")
+    return t
+
+
+def _infer_out(out, offset, shape, like):
+    n, ho, wo, c = shape
+    if out is None:
+        if offset:
+            raise ValueError("a channel offset needs the buffer it points into")
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    _infer_operand(out, "out")
+    if out.dim() != 4 or tuple(out.shape[:3]) != (n, ho, wo) or offset < 0 or out.size(3) < offset + c or out.device != like.device:
+        raise ValueError(f"out {tuple(out.shape)} cannot take channels {offset} .. {offset + c} of a [{n}, {ho}, {wo}, .] result")
+    return out
+
+
+def infer_conv2d(x, weight, scale, shift, stride=1, pad=(0, 0), out=None, offset=0):
+    """relu(conv(x, weight) * scale + shift) without autograd (movae_infer_conv2d): x NHWC [n, h, w, ci], weight the MEMORY image
+    [co, kh, kw, ci], scale / shift [co]; pad = (pad_h, pad_w).  -> out ([n, ho, wo, co] when not given)."""
+    x, weight = _infer_operand(x, "x"), _infer_operand(weight, "weight")
+    scale, shift = _infer_operand(scale, "scale"), _infer_operand(shift, "shift")
+    if x.dim() != 4 or weight.dim() != 4 or weight.size(3) != x.size(3):
+        raise ValueError(f"infer_conv2d: x {tuple(x.shape)} (NHWC) and weight {tuple(weight.shape)} ([co, kh, kw, ci]) do not match")
+    n, h, w, ci = x.shape
+    co, kh, kw, _ = weight.shape
+    if scale.numel() != co or shift.numel() != co:
+        raise ValueError(f"infer_conv2d: scale / shift must hold {co} elements")
+    ph, pw = pad
+    ho, wo = conv_out_size(h, kh, stride, ph), conv_out_size(w, kw, stride, pw)
+    if ho < 1 or wo < 1:
+        raise ValueError(f"infer_conv2d: a {kh} x {kw} kernel (padding {ph}, {pw}) does not fit {h} x {w}")
+    out = _infer_out(out, offset, (n, ho, wo, co), x)
+    _call("movae_infer_conv2d", x.data_ptr(), weight.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr(), n, h, w, ci, co, kh, kw,
+          int(stride), int(ph), int(pw), out.size(3), int(offset), _st(x))
+    return out
+
+
+def infer_pool3x3(x, mode, out=None, offset=0):
+    """mode "max": F.max_pool2d(x, 3, stride=2); mode "avg": F.avg_pool2d(x, 3, stride=1, padding=1) (count_include_pad), on NHWC
+    (movae_infer_pool3x3)."""
+    x = _infer_operand(x, "x")
+    if mode not in ("max", "avg") or x.dim() != 4:
+        raise ValueError(f"infer_pool3x3: mode 'max' or 'avg' on an NHWC tensor, got {mode!r} {tuple(x.shape)}")
+    n, h, w, c = x.shape
+    if mode == "max" and min(h, w) < 3:
+        raise ValueError(f"infer_pool3x3: the unpadded 3x3 window does not fit {h} x {w}")
+    ho, wo = ((h - 3) // 2 + 1, (w - 3) // 2 + 1) if mode == "max" else (h, w)
+    out = _infer_out(out, offset, (n, ho, wo, c), x)
+    _call("movae_infer_pool3x3", x.data_ptr(), out.data_ptr(), n, h, w, c, 0 if mode == "max" else 1, out.size(3), int(offset), _st(x))
+    return out
+
+
+def infer_global_mean(x, out=None):
+    """NHWC [n, h, w, c] -> [n, c], the mean over the pixels (movae_infer_global_mean)."""
+    x = _infer_operand(x, "x")
+    n, h, w, c = x.shape
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    elif tuple(_infer_operand(out, "out").shape) != (n, c) or out.device != x.device:
+        raise ValueError(f"infer_global_mean: out must be [{n}, {c}] on the input's device")
+    _call("movae_infer_global_mean", x.data_ptr(), out.data_ptr(), n, h * w, c, _st(x))
+    return out
+
+
+INCEPTION_SIDE = 299
+
+
+def inception_prep(x, out=None):
+    """calculate_fid's input pipeline (utils/metrics.py:542-553) in one launch: NCHW [n, 3, h, w] -> NHWC [n, 299, 299, 3] =
+    normalize(center_crop(resize(clamp(0.5 x + 0.5, 0, 1), 299, BICUBIC, antialias=True))).  A side above 299 raises
+    NotImplementedError (reducing needs a true antialiasing filter)."""
+    L.require_gpu(x)
+    if x.dim() != 4 or x.size(1) != 3:
+        raise ValueError(f"inception_prep takes [n, 3, h, w] images, got {tuple(x.shape)}")
+    n, _, h, w = x.shape
+    if max(h, w) > INCEPTION_SIDE:
+        raise NotImplementedError(f"inception_prep: {h} x {w} has a side above {INCEPTION_SIDE}; reducing an image needs an antialiasing "
+                                  "filter this build does not have")
+    x = x if x.dtype == torch.float32 else x.float()
+    x = x.contiguous()
+    shape = (n, INCEPTION_SIDE, INCEPTION_SIDE, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(_infer_operand(out, "out").shape) != shape or out.device != x.device:
+        raise ValueError(f"inception_prep: out must be {shape} on the input's device")
+    _call("movae_inception_prep", x.data_ptr(), out.data_ptr(), n, h, w, _st(x))
+    return out

@@ -458,7 +458,8 @@ def evaluate_with_recon_metrics(net, loader, device, args):
     """main.py:376-463: `evaluate`'s meters and the reconstruction metrics from ONE pass over the loader -> (meters,
     {'rfid', 'psnr', 'ssim', 'lpips'}).  The first `--max_fid_samples` (real, recon) pairs are scored in the reference's
     128-sample chunks on the device (metrics.ReconMetricAccumulator) instead of being copied to the host; LPIPS is scored
-    there too when VGG16 weights with the conv4 block are registered (perceptual.use_vgg16_weights), else NaN; rFID is NaN."""
+    there too when VGG16 weights with the conv4 block are registered (perceptual.use_vgg16_weights), else NaN; rFID likewise when Inception-v3 weights are registered
+    (inception.use_inception_weights), else NaN."""
     acc = ReconMetricAccumulator(device, getattr(args, "max_fid_samples", 5000))
     meters = _eval_loop(net, loader, device, on_batch=lambda images, out: acc.add(images, out.get("recons")))
     return meters, acc.result()
