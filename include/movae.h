@@ -819,6 +819,49 @@ int movae_infer_pool3x3(const float* x, float* y, int n, int h, int w, int c, in
 int movae_infer_global_mean(const float* x, float* y, int n, int hw, int c, movae_stream_t stream);
 int movae_inception_prep(const float* x, float* y, int n, int h, int w, movae_stream_t stream);
 
+/* ---- the generative evaluation: gFID / Inception Score / KID / precision and recall (csrc/gen_metrics.hip, and the second filter of
+ * the input pipeline in csrc/inception.hip; the reference's main.py:695-887, utils/metrics.py:682-736, :835-914) ------------------------
+ * Forward only, fp32 operands, no atomics, bit-identical from run to run; capturable.
+ *
+ * movae_inception_prep_filter: movae_inception_prep with the resize filter named.  MOVAE_RESIZE_BICUBIC is movae_inception_prep itself,
+ * bit for bit.  MOVAE_RESIZE_BILINEAR is calculate_inception_score's TF.resize(batch, 299, antialias=True) -- the default filter: the
+ * antialiased bilinear of F.interpolate, for an enlargement the triangle 1 - |t| of support 1 at (tap - scale * (i + 0.5) + 0.5), at
+ * most 3 taps per axis, cut at the border and renormalised; everything else (0.5 x + 0.5, clamp, centre crop, ImageNet normalisation,
+ * NHWC output, fp64 weights and sums) as in movae_inception_prep.  Refused as there, and any other filter value.
+ *
+ * movae_linear_softmax: probs[i][c] = softmax_c(sum_k feat[i][k] * weight[c][k] + bias[c]), feat [n][D], weight [C][D], bias [C],
+ * probs [n][C], all contiguous; fp32 throughout, the row maximum subtracted before expf.  Four rows per block are staged in LDS once;
+ * weight rows are read with 16-byte loads where D % 4 == 0 and weight is 16-byte aligned.  Refused: a null pointer, a dimension <= 0,
+ * 4 * (D + C) floats above 64 KB (D = 2048 with C = 1000 takes 48 KB).
+ *
+ * movae_inception_score: utils/metrics.py:895-914 on probs [n][C]: split i is rows i * (n / splits) .. (i + 1) * (n / splits) - 1
+ * (integer division: the remainder rows belong to no split); with p = clip(probs, 1e-16, 1) and p_y = clip(mean over the split's rows
+ * of p, 1e-16, 1), scores[i] = exp(mean over the rows of sum_c p (log p - log p_y)).  One block per split; every sum, logarithm and
+ * the exponential in fp64.  scores [splits] fp64 on the device; mean and standard deviation over the splits are the caller's.
+ * Refused: n / splits == 0 (every split empty -- the caller reports NaN), C above 7000, a misaligned scores.
+ *
+ * movae_kid_subsets: utils/metrics.py:682-709 for S subsets at once.  real [nr][D], fake [nf][D]; idx_real / idx_fake [S][m] int32 row
+ * numbers (the caller draws them).  Per subset, with r / f the gathered rows: K(x, y) = (gamma x.y + 1)^degree, mmd2[s] =
+ * max(0, sum_{i != j} K(r_i, r_j) / (m (m - 1)) + sum_{i != j} K(f_i, f_j) / (m (m - 1)) - 2 sum_{i, j} K(r_i, f_j) / m^2).  Dots,
+ * powers and sums in fp64 (operands widened before the product).  One block per subset.  An index outside its set contributes a
+ * zero row (the caller validates the indices).  Refused: m < 2, m above 240 or above a set's size, degree outside 1 .. 16.
+ *
+ * movae_knn_rows: for every row i of a [na][D] its k smallest squared Euclidean distances to the rows of b [nb][D], ascending, into
+ * dist2 [na][k], clamped below at 0, and the row number of the nearest into idx [na]; exclude_diag = 1 leaves j == i out (a against
+ * itself: the reference's fill_diagonal(inf)).  Gram form |a_i|^2 + |b_j|^2 - 2 a_i.b_j: the norms are summed in fp64 and rounded
+ * once into norms [na + nb] (scratch of the caller), the dots run on the exact-fp32 MFMA, k ascending.  No na x nb matrix is formed:
+ * a block owns `tile` rows (64 or 128; 0: chosen here) for all of b and keeps the candidates in registers.  Equal distances: the
+ * smaller row number of b is reported.  Refused: k outside 1 .. 8, fewer than k candidates per row, any other tile. */
+#define MOVAE_RESIZE_BICUBIC 0
+#define MOVAE_RESIZE_BILINEAR 1
+int movae_inception_prep_filter(const float* x, float* y, int n, int h, int w, int filter, movae_stream_t stream);
+int movae_linear_softmax(const float* feat, const float* weight, const float* bias, float* probs, int n, int C, int D, movae_stream_t stream);
+int movae_inception_score(const float* probs, int n, int C, int splits, double* scores, movae_stream_t stream);
+int movae_kid_subsets(const float* real, const float* fake, const int* idx_real, const int* idx_fake, int nr, int nf, int S, int m, int D,
+                      double gamma, int degree, double* mmd2, movae_stream_t stream);
+int movae_knn_rows(const float* a, const float* b, int na, int nb, int D, int k, int exclude_diag, int tile, float* norms, float* dist2,
+                   int* idx, movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

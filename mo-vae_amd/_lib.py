@@ -173,6 +173,11 @@ SIGNATURES = {
     "movae_infer_pool3x3": ([_p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "movae_infer_global_mean": ([_p, _p, _i, _i, _i, _p], _i),
     "movae_inception_prep": ([_p, _p, _i, _i, _i, _p], _i),
+    "movae_inception_prep_filter": ([_p, _p, _i, _i, _i, _i, _p], _i),
+    "movae_linear_softmax": ([_p, _p, _p, _p, _i, _i, _i, _p], _i),
+    "movae_inception_score": ([_p, _i, _i, _i, _p, _p], _i),
+    "movae_kid_subsets": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, _i, _p, _p], _i),
+    "movae_knn_rows": ([_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p], _i),
     "movae_batch_u8": ([_p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_batch_rrc_u8": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_resample_coeffs": ([_p, _i, _i, _i, _p, _p, _p], _i),

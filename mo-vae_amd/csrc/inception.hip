@@ -17,8 +17,9 @@
 //                               output element (per four channels where c, the output row and the offset allow 16-byte accesses),
 //                               c fastest.
 //   infer_gmean_k               mean over the pixels, one thread per (image, channel).
-//   inception_prep_k            calculate_fid's denormalize + TF.resize(299, BICUBIC, antialias) + centre crop + normalize, one
-//                               thread per output pixel, NCHW in, NHWC out.
+//   inception_prep_k<FILTER>    calculate_fid's denormalize + TF.resize(299, BICUBIC, antialias) + centre crop + normalize, one
+//                               thread per output pixel, NCHW in, NHWC out.  FILTER 1: the same with TF.resize's default BILINEAR
+//                               (the triangle filter), calculate_inception_score's pipeline.
 #include "common.h"
 
 #include <math.h>
@@ -294,20 +295,31 @@ __device__ __forceinline__ double keys(double x) {
     return 0.0;
 }
 
-// taps and normalised weights of output sample `o` (of the resized axis) over an input axis of `in` samples; scale = in / out <= 1
+// the triangle filter of the antialiased bilinear resize
+__device__ __forceinline__ double triangle(double x) {
+    x = fabs(x);
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+// taps and normalised weights of output sample `o` (of the resized axis) over an input axis of `in` samples; scale = in / out <= 1.
+// FILTER 0: Keys' cubic, support 2 (at most 5 taps); FILTER 1: the triangle, support 1 (at most 3 taps)
+template <int FILTER>
 __device__ __forceinline__ void taps_of(int o, double scale, int in, int& first, int& count, double (&wt)[5]) {
+    constexpr double S = FILTER == 0 ? 2.0 : 1.0;
+    constexpr int MAXT = FILTER == 0 ? 5 : 3;
     const double center = scale * (o + 0.5);
-    int lo = (int)(center - 2.0 + 0.5);  // (truncation, as the int64 cast of the ATen routine)
+    int lo = (int)(center - S + 0.5);  // (truncation, as the int64 cast of the ATen routine)
     lo = lo < 0 ? 0 : lo;
-    int hi = (int)(center + 2.0 + 0.5);
+    int hi = (int)(center + S + 0.5);
     hi = hi > in ? in : hi;
     first = lo;
     count = hi - lo;
-    count = count > 5 ? 5 : count;
+    count = count > MAXT ? MAXT : count;
     double total = 0.0;
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-        wt[j] = j < count ? keys((double)(j + lo) - center + 0.5) : 0.0;
+        if constexpr (FILTER == 0) wt[j] = j < count ? keys((double)(j + lo) - center + 0.5) : 0.0;
+        else wt[j] = j < count ? triangle((double)(j + lo) - center + 0.5) : 0.0;
         total += wt[j];
     }
     const double inv = total != 0.0 ? 1.0 / total : 0.0;
@@ -315,6 +327,7 @@ __device__ __forceinline__ void taps_of(int o, double scale, int in, int& first,
     for (int j = 0; j < 5; ++j) wt[j] *= inv;
 }
 
+template <int FILTER>
 __global__ __launch_bounds__(256) void inception_prep_k(const float* __restrict__ x, float* __restrict__ y, int n, int h, int w, int rh,
                                                         int rw, int top, int left) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -324,8 +337,8 @@ __global__ __launch_bounds__(256) void inception_prep_k(const float* __restrict_
     const int oy = (int)(q % IC_OUT), img = (int)(q / IC_OUT);
     int fy, cy, fx, cx;
     double wy[5], wx[5];
-    taps_of(oy + top, (double)h / (double)rh, h, fy, cy, wy);
-    taps_of(ox + left, (double)w / (double)rw, w, fx, cx, wx);
+    taps_of<FILTER>(oy + top, (double)h / (double)rh, h, fy, cy, wy);
+    taps_of<FILTER>(ox + left, (double)w / (double)rw, w, fx, cx, wx);
     const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -417,11 +430,13 @@ extern "C" int movae_infer_global_mean(const float* x, float* y, int n, int hw, 
     return MOVAE_OK;
 }
 
-extern "C" int movae_inception_prep(const float* x, float* y, int n, int h, int w, movae_stream_t stream) {
+extern "C" int movae_inception_prep_filter(const float* x, float* y, int n, int h, int w, int filter, movae_stream_t stream) {
     MOVAE_CHECK_ARG(x && y, "movae_inception_prep: null pointer");
     MOVAE_CHECK_ARG(n > 0 && h > 0 && w > 0, "movae_inception_prep: empty shape %d x 3 x %d x %d", n, h, w);
     MOVAE_CHECK_ARG(h <= IC_OUT && w <= IC_OUT, "movae_inception_prep: %d x %d has a side above %d (reducing needs a true antialiasing filter)", h,
                     w, IC_OUT);
+    MOVAE_CHECK_ARG(filter == MOVAE_RESIZE_BICUBIC || filter == MOVAE_RESIZE_BILINEAR, "movae_inception_prep: filter %d (0 bicubic, 1 bilinear)",
+                    filter);
     MOVAE_CHECK_ARG((long long)n * IC_OUT * IC_OUT * 3 < IC_LIMIT * 4, "movae_inception_prep: n %d is too large", n);
     // TF.resize(299): the shorter side to 299, the other to int(299 * long / short); TF.center_crop: round-half-even offsets
     int rh, rw;
@@ -429,8 +444,14 @@ extern "C" int movae_inception_prep(const float* x, float* y, int n, int h, int 
     else rw = IC_OUT, rh = (int)((long long)IC_OUT * h / w);
     const int top = (int)nearbyint((rh - IC_OUT) / 2.0), left = (int)nearbyint((rw - IC_OUT) / 2.0);
     const long long total = (long long)n * IC_OUT * IC_OUT;
-    hipLaunchKernelGGL(inception_prep_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, n, h, w, rh,
-                       rw, top, left);
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (filter == MOVAE_RESIZE_BICUBIC) hipLaunchKernelGGL(inception_prep_k<0>, grid, block, 0, st, x, y, n, h, w, rh, rw, top, left);
+    else hipLaunchKernelGGL(inception_prep_k<1>, grid, block, 0, st, x, y, n, h, w, rh, rw, top, left);
     MOVAE_CHECK_LAUNCH("inception_prep_k");
     return MOVAE_OK;
+}
+
+extern "C" int movae_inception_prep(const float* x, float* y, int n, int h, int w, movae_stream_t stream) {
+    return movae_inception_prep_filter(x, y, n, h, w, MOVAE_RESIZE_BICUBIC, stream);
 }

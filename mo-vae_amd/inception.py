@@ -7,7 +7,9 @@ or the environment variable MOVAE_INCEPTION_WEIGHTS=/path as the fallback -- and
 produce numbers; with nothing registered rFID stays NaN, as the reference gives when it cannot load the network.
 
 The accepted source is a torchvision inception_v3 state_dict: every BasicConv2d is `<name>.conv.weight` (no bias) plus
-`<name>.bn.{weight, bias, running_mean, running_var}`; AuxLogits.*, fc.* and *.num_batches_tracked are ignored.  The eval-mode
+`<name>.bn.{weight, bias, running_mean, running_var}`; AuxLogits.* and *.num_batches_tracked are ignored.  `fc.weight` / `fc.bias`, the
+classifier the Inception Score needs, are kept when the source has them (InceptionWeights.fc_weight / fc_bias; rFID does not use
+them and a source without them loads all the same).  The eval-mode
 BatchNorm (eps 1e-3) is folded at load, in float64, into a per-channel scale and shift applied in the convolution's epilogue; the
 convolution weight itself stays as stored.
 
@@ -100,9 +102,14 @@ def conv_layers():
 
 
 class InceptionWeights(OrderedDict):
-    """load_inception_weights' result; feature_dim: the channels of Mixed_7c's output (2048 at the real widths)."""
+    """load_inception_weights' result; feature_dim: the channels of Mixed_7c's output (2048 at the real widths).  The classifier is
+    carried in attributes, not items (the items are the 94 layers): fc_weight [num_classes, feature_dim] and fc_bias [num_classes]
+    fp32, or None / None / 0 for a source without `fc`."""
 
     feature_dim = 0
+    fc_weight = None
+    fc_bias = None
+    num_classes = 0
 
 
 def _open(src):
@@ -148,8 +155,9 @@ def load_inception_weights(src):
     BatchNorm, eps 1e-3, folded in float64: s = gamma / sqrt(var + eps), t = beta - mean * s, rounded to fp32 once)} for the 94
     layers of conv_layers(), from a path (read with torch.load(..., weights_only=True)), a mapping or a module.  Accepted key forms:
     `<layer>.conv.weight` / `<layer>.bn.*` bare (a torchvision inception_v3 state_dict) or under `model.` (the reference's wrapper).
-    AuxLogits.*, fc.* and *.num_batches_tracked are ignored.  Any channel widths that chain through the topology are accepted; a
-    missing key or a wrong shape raises ValueError naming the key."""
+    AuxLogits.* and *.num_batches_tracked are ignored; fc.weight [C, feature_dim] and fc.bias [C] go, when both are present, into the
+    result's fc_weight / fc_bias / num_classes attributes (not its items).  Any channel widths that chain through the topology are
+    accepted; a missing key or a wrong shape raises ValueError naming the key."""
     src = _open(src)
     out = InceptionWeights()
     c = 3
@@ -170,7 +178,25 @@ def load_inception_weights(src):
             total += cp
         c = total
     out.feature_dim = c
+    _take_fc(src, out)
     return out
+
+
+def _take_fc(src, out):
+    """The classifier, when the source has one: validated against feature_dim and kept in out's attributes."""
+    found = {leaf: next((p + f"fc.{leaf}" for p in _PREFIXES if p + f"fc.{leaf}" in src), None) for leaf in ("weight", "bias")}
+    if found["weight"] is None and found["bias"] is None:
+        return
+    for leaf, key in found.items():
+        if key is None:
+            raise ValueError(f"Inception-v3 weights: fc.{leaf} is missing while fc.{'bias' if leaf == 'weight' else 'weight'} is present")
+    w = torch.as_tensor(src[found["weight"]]).detach().to(device="cpu")
+    b = torch.as_tensor(src[found["bias"]]).detach().to(device="cpu")
+    if w.dim() != 2 or w.size(0) < 1 or w.size(1) != out.feature_dim:
+        raise ValueError(f"Inception-v3 weights: {found['weight']} has shape {tuple(w.shape)}, expected [C, {out.feature_dim}]")
+    if tuple(b.shape) != (w.size(0),):
+        raise ValueError(f"Inception-v3 weights: {found['bias']} has shape {tuple(b.shape)}, expected [{w.size(0)}]")
+    out.fc_weight, out.fc_bias, out.num_classes = w.float().contiguous(), b.float().contiguous(), int(w.size(0))
 
 
 _registered = [None]
@@ -267,6 +293,8 @@ class InceptionFeatures:
         for name, _ in conv_layers():
             w = weights[f"{name}.weight"].permute(0, 2, 3, 1).contiguous().to(self.device)  # [Co][KH][KW][Ci]
             self.layers[name] = (w, weights[f"{name}.scale"].to(self.device), weights[f"{name}.shift"].to(self.device))
+        self.num_classes = weights.num_classes
+        self.fc = None if not weights.num_classes else (weights.fc_weight.to(self.device), weights.fc_bias.to(self.device))
         self._cache, self._bufs = OrderedDict(), {}  # input shape -> its buffers (the two most recent: a full and a partial chunk)
 
     def _select(self, shape):
@@ -285,6 +313,22 @@ class InceptionFeatures:
         shape = (images.size(0), ops.INCEPTION_SIDE, ops.INCEPTION_SIDE, 3)
         self._select(shape)
         return self.forward(ops.inception_prep(images, self._buf("prep", shape)))
+
+    @property
+    def has_classifier(self):
+        return self.fc is not None
+
+    def probs_of(self, images):
+        """NCHW [n, 3, h, w] images (h, w <= 299) -> their [n, C] class probabilities, calculate_inception_score's pass
+        (utils/metrics.py:872-889): the BILINEAR input pipeline, the stack, the classifier (eval-mode dropout is the identity) and the
+        softmax.  A cached buffer, like features_of's result."""
+        if self.fc is None:
+            raise RuntimeError("the registered Inception-v3 weights have no classifier (fc.weight / fc.bias): the Inception Score "
+                               "cannot be computed from them")
+        shape = (images.size(0), ops.INCEPTION_SIDE, ops.INCEPTION_SIDE, 3)
+        self._select(shape)
+        feats = self.forward(ops.inception_prep(images, self._buf("prep", shape), filter="bilinear"))
+        return ops.linear_softmax(feats, self.fc[0], self.fc[1], self._buf("probs", (images.size(0), self.num_classes)))
 
     def _buf(self, key, shape):
         t = self._bufs.get(key)

@@ -322,6 +322,121 @@ def fid(real, fake, chunk=CHUNK):
     return fid_from_features(inception_features(real, chunk), inception_features(fake, chunk))
 
 
+# ---- the generative evaluation: Inception Score, KID, precision / recall (gFID is fid_from_features) ---------------------------------
+def _device_matrix(t):
+    """A feature or probability set as the kernels take it: contiguous fp32 [N, D] on its device."""
+    t = torch.as_tensor(t)
+    L.require_gpu(t)
+    return t.detach().to(dtype=torch.float32).contiguous()
+
+
+@torch.no_grad()
+def inception_probs(images, chunk=CHUNK):
+    """-> [N, C] fp32 on the device: the class probabilities of calculate_inception_score's pass (utils/metrics.py:861-890) --
+    the unconditional 0.5 x + 0.5 and clamp, the antialiased BILINEAR resize to 299 (TF.resize's default filter, not rFID's
+    bicubic), centre crop, ImageNet normalisation, the stack, `fc` and the softmax -- `chunk` images at a time, without a host
+    read.  Needs registered weights that carry the classifier."""
+    weights = _inception_weights()
+    if weights is None or not weights.num_classes:
+        raise RuntimeError("the Inception Score needs Inception-v3 weights with the classifier (fc.weight, fc.bias): register them with "
+                           "inception.use_inception_weights(path, state_dict or module); nothing is downloaded")
+    images = _operand(images)
+    if images.size(1) != 3:
+        raise ValueError(f"the Inception classifier takes 3-channel images, got shape {tuple(images.shape)}")
+    n = images.size(0)
+    out = torch.empty((n, weights.num_classes), dtype=torch.float32, device=images.device)
+    net = _inception_on(images.device, weights)
+    for lo in range(0, n, int(chunk)):
+        part = images[lo: lo + int(chunk)]
+        out[lo: lo + part.size(0)].copy_(net.probs_of(part))
+    return out
+
+
+def inception_score_from_probs(probs, splits=10):
+    """utils/metrics.py:895-914 on [N, C] probabilities on the device -> (mean, std) over the splits (np.std: the population
+    form).  Every split's score comes from one launch (ops.inception_score_splits, fp64); (nan, nan) for an empty set and for
+    N < splits, where every split of the reference is empty."""
+    probs = torch.as_tensor(probs)
+    if probs.dim() != 2 or probs.numel() == 0 or probs.size(0) // int(splits) < 1:
+        return float("nan"), float("nan")
+    from . import ops
+
+    scores = ops.inception_score_splits(_device_matrix(probs), splits).cpu().numpy()
+    return float(np.mean(scores)), float(np.std(scores))
+
+
+def inception_score(images, splits=10, chunk=CHUNK):
+    """utils/metrics.py:835-914 calculate_inception_score on the registered weights -> (mean, std); (nan, nan) for empty input,
+    for N < splits and when no classifier weights are registered."""
+    weights = _inception_weights()
+    if images.numel() == 0 or images.size(0) // int(splits) < 1 or weights is None or not weights.num_classes:
+        return float("nan"), float("nan")
+    return inception_score_from_probs(inception_probs(images, chunk), splits)
+
+
+def kid_subset_indices(n_real, n_fake, subset_size, n_subsets, seed=None):
+    """The subsets of utils/metrics.py:695-699 from np.random.default_rng(seed), in the reference's order: per subset,
+    choice(n_real, m, replace=False) then choice(n_fake, m, replace=False).  -> (idx_real, idx_fake), int64 [n_subsets, m]."""
+    rng = np.random.default_rng(seed)
+    idx_real = np.empty((n_subsets, subset_size), dtype=np.int64)
+    idx_fake = np.empty((n_subsets, subset_size), dtype=np.int64)
+    for s in range(n_subsets):
+        idx_real[s] = rng.choice(n_real, size=subset_size, replace=False)
+        idx_fake[s] = rng.choice(n_fake, size=subset_size, replace=False)
+    return idx_real, idx_fake
+
+
+def kid_from_features(real, fake, subset_size=50, n_subsets=50, degree=3, gamma=None, seed=None, subsets=None):
+    """utils/metrics.py:682-709 kid_from_features on [N, D] feature sets on the device: the mean over the subsets of the clamped
+    unbiased MMD^2 under (gamma x.y + 1)^degree, gamma = 1 / D by default, every subset in one launch (ops.kid_subsets, fp64).
+    The subsets are drawn on the host (kid_subset_indices; the reference seeds nothing, `seed` makes the draw repeatable) or given
+    as subsets=(idx_real, idx_fake), [S, m] each.  NaN for an empty set or m = min(subset_size, n_real, n_fake) < 2."""
+    if len(real) == 0 or len(fake) == 0:
+        return float("nan")
+    n_real, dim = real.shape
+    n_fake = fake.shape[0]
+    m = min(int(subset_size), n_real, n_fake)
+    if subsets is not None:
+        idx_real, idx_fake = (np.asarray(torch.as_tensor(t).cpu()) for t in subsets)
+        if idx_real.ndim != 2 or idx_real.shape != idx_fake.shape:
+            raise ValueError(f"subsets must be two [S, m] index arrays, got {idx_real.shape} and {idx_fake.shape}")
+        m = idx_real.shape[1]
+    if m < 2:
+        return float("nan")
+    if subsets is None:
+        idx_real, idx_fake = kid_subset_indices(n_real, n_fake, m, int(n_subsets), seed)
+    if idx_real.shape[0] == 0:
+        return float("nan")  # (np.mean of no values)
+    for idx, n, what in ((idx_real, n_real, "real"), (idx_fake, n_fake, "fake")):
+        if idx.min() < 0 or idx.max() >= n:
+            raise ValueError(f"a subset index of the {what} set lies outside 0 .. {n - 1}")
+    real, fake = _device_matrix(real), _device_matrix(fake)
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(real.device)  # noqa: E731
+    from . import ops
+
+    vals = ops.kid_subsets(real, fake, to_dev(idx_real), to_dev(idx_fake), 1.0 / dim if gamma is None else float(gamma), degree)
+    return float(vals.mean().item())
+
+
+def precision_recall_from_features(real, fake, k=3):
+    """utils/metrics.py:712-736 precision_recall_from_features on [N, D] feature sets on the device -> (precision, recall): a
+    generated sample counts when its distance to the nearest real sample is at most that real sample's k-th neighbour radius among
+    the real set, and the other way round.  Four ops.knn_rows calls (R/R and F/F with k, diagonal excluded; F->R and R->F with
+    k = 1) instead of four N x N cdist matrices; the comparison stays on the device.  (nan, nan) for an empty set or len <= k."""
+    if len(real) == 0 or len(fake) == 0 or len(real) <= k or len(fake) <= k:
+        return float("nan"), float("nan")
+    from . import ops
+
+    real, fake = _device_matrix(real), _device_matrix(fake)
+    radius_real = ops.knn_rows(real, real, k, exclude_diag=True)[0][:, k - 1].clamp_min(0).sqrt()
+    radius_fake = ops.knn_rows(fake, fake, k, exclude_diag=True)[0][:, k - 1].clamp_min(0).sqrt()
+    d_fr, i_fr = ops.knn_rows(fake, real, 1)
+    d_rf, i_rf = ops.knn_rows(real, fake, 1)
+    precision = (d_fr[:, 0].clamp_min(0).sqrt() <= radius_real[i_fr.long()]).float().mean()
+    recall = (d_rf[:, 0].clamp_min(0).sqrt() <= radius_fake[i_rf.long()]).float().mean()
+    return float(precision.item()), float(recall.item())
+
+
 # ---- collection in the reference's chunks ------------------------------------------------------------------------------
 class ChunkPlanner:
     """Host-side bookkeeping of main.py:376-463 + :335-373: which samples of each loader batch are taken (the `take` cut at

@@ -2709,11 +2709,17 @@ def infer_global_mean(x, out=None):
 INCEPTION_SIDE = 299
 
 
-def inception_prep(x, out=None):
+RESIZE_FILTERS = {"bicubic": 0, "bilinear": 1}  # include/movae.h: MOVAE_RESIZE_*
+
+
+def inception_prep(x, out=None, filter="bicubic"):
     """calculate_fid's input pipeline (utils/metrics.py:542-553) in one launch: NCHW [n, 3, h, w] -> NHWC [n, 299, 299, 3] =
-    normalize(center_crop(resize(clamp(0.5 x + 0.5, 0, 1), 299, BICUBIC, antialias=True))).  A side above 299 raises
+    normalize(center_crop(resize(clamp(0.5 x + 0.5, 0, 1), 299, BICUBIC, antialias=True))).  filter="bilinear": the same with
+    TF.resize's default filter, calculate_inception_score's pipeline (utils/metrics.py:872-875).  A side above 299 raises
     NotImplementedError (reducing needs a true antialiasing filter)."""
     L.require_gpu(x)
+    if filter not in RESIZE_FILTERS:
+        raise ValueError(f"inception_prep: filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
     if x.dim() != 4 or x.size(1) != 3:
         raise ValueError(f"inception_prep takes [n, 3, h, w] images, got {tuple(x.shape)}")
     n, _, h, w = x.shape
@@ -2727,5 +2733,88 @@ def inception_prep(x, out=None):
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
     elif tuple(_infer_operand(out, "out").shape) != shape or out.device != x.device:
         raise ValueError(f"inception_prep: out must be {shape} on the input's device")
-    _call("movae_inception_prep", x.data_ptr(), out.data_ptr(), n, h, w, _st(x))
+    if filter == "bicubic":
+        _call("movae_inception_prep", x.data_ptr(), out.data_ptr(), n, h, w, _st(x))
+    else:
+        _call("movae_inception_prep_filter", x.data_ptr(), out.data_ptr(), n, h, w, RESIZE_FILTERS[filter], _st(x))
     return out
+
+
+# ---- feature-space kernels of the generative evaluation (csrc/gen_metrics.hip; metrics.inception_score / kid_from_features /
+# precision_recall_from_features) -------------------------------------------------------------------------------------------------------
+def _matrix(t, what):
+    _infer_operand(t, what)
+    if t.dim() != 2 or t.size(0) < 1 or t.size(1) < 1:
+        raise ValueError(f"{what} must be a non-empty [rows, columns] matrix, got {tuple(t.shape)}")
+    return t
+
+
+def linear_softmax(feat, weight, bias, out=None):
+    """softmax(feat @ weight.T + bias, dim=1) in fp32 (movae_linear_softmax): feat [n, D], weight [C, D], bias [C] -> [n, C]."""
+    feat, weight = _matrix(feat, "feat"), _matrix(weight, "weight")
+    _infer_operand(bias, "bias")
+    n, d = feat.shape
+    c = weight.size(0)
+    if weight.size(1) != d or tuple(bias.shape) != (c,) or weight.device != feat.device or bias.device != feat.device:
+        raise ValueError(f"linear_softmax: feat {tuple(feat.shape)}, weight {tuple(weight.shape)} and bias {tuple(bias.shape)} do not match")
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float32, device=feat.device)
+    elif tuple(_infer_operand(out, "out").shape) != (n, c) or out.device != feat.device:
+        raise ValueError(f"linear_softmax: out must be [{n}, {c}] on the input's device")
+    _call("movae_linear_softmax", feat.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), n, c, d, _st(feat))
+    return out
+
+
+def inception_score_splits(probs, splits=10):
+    """-> [splits] fp64 on the device: exp(mean KL(p(y|x) || p(y))) of every split of probs [n, C] (movae_inception_score; split i is
+    rows i (n // splits) .. (i + 1) (n // splits), both distributions clipped to [1e-16, 1]).  n >= splits."""
+    probs = _matrix(probs, "probs")
+    n, c = probs.shape
+    splits = int(splits)
+    if splits < 1 or n // splits < 1:
+        raise ValueError(f"inception_score_splits: {n} rows leave every one of {splits} splits empty")
+    out = torch.empty(splits, dtype=torch.float64, device=probs.device)
+    _call("movae_inception_score", probs.data_ptr(), n, c, splits, out.data_ptr(), _st(probs))
+    return out
+
+
+def kid_subsets(real, fake, idx_real, idx_fake, gamma, degree=3):
+    """-> [S] fp64 on the device: the clamped unbiased MMD^2 of every subset under the kernel (gamma x.y + 1)^degree
+    (movae_kid_subsets).  real [nr, D], fake [nf, D]; idx_real / idx_fake [S, m] int32 row numbers on the same device."""
+    real, fake = _matrix(real, "real"), _matrix(fake, "fake")
+    if real.size(1) != fake.size(1) or fake.device != real.device:
+        raise ValueError(f"kid_subsets: real {tuple(real.shape)} and fake {tuple(fake.shape)} do not match")
+    for t, what in ((idx_real, "idx_real"), (idx_fake, "idx_fake")):
+        L.require_gpu(t)
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 2 or t.shape != idx_real.shape or t.device != real.device:
+            raise ValueError(f"kid_subsets: {what} must be a contiguous int32 [S, m] tensor on the features' device, got {t.dtype} {tuple(t.shape)}")
+    s, m = idx_real.shape
+    if s < 1 or m < 2:
+        raise ValueError(f"kid_subsets: needs at least one subset of at least two rows, got [{s}, {m}]")
+    out = torch.empty(s, dtype=torch.float64, device=real.device)
+    _call("movae_kid_subsets", real.data_ptr(), fake.data_ptr(), idx_real.data_ptr(), idx_fake.data_ptr(), real.size(0), fake.size(0), s, m,
+          real.size(1), float(gamma), int(degree), out.data_ptr(), _st(real))
+    return out
+
+
+KNN_MAX_K = 8
+
+
+def knn_rows(a, b, k, exclude_diag=False, tile=None):
+    """-> (dist2 [na, k] fp32: every row's k smallest SQUARED Euclidean distances to the rows of b, ascending, clamped at 0;
+    idx [na] int32: the row of b nearest to each row of a) without the na x nb matrix (movae_knn_rows).  exclude_diag: leave j == i
+    out (a against itself).  tile: 64 or 128 rows of a per block; None lets the library choose."""
+    a, b = _matrix(a, "a"), _matrix(b, "b")
+    if a.size(1) != b.size(1) or a.device != b.device:
+        raise ValueError(f"knn_rows: a {tuple(a.shape)} and b {tuple(b.shape)} do not match")
+    na, nb, k = a.size(0), b.size(0), int(k)
+    if not 1 <= k <= KNN_MAX_K or nb - int(bool(exclude_diag)) < k:
+        raise ValueError(f"knn_rows: k must be 1 .. {KNN_MAX_K} and at most the candidates per row, got k {k} for {nb} rows of b")
+    if tile not in (None, 64, 128):
+        raise ValueError(f"knn_rows: tile must be None, 64 or 128, got {tile!r}")
+    norms = torch.empty(na + nb, dtype=torch.float32, device=a.device)
+    dist2 = torch.empty((na, k), dtype=torch.float32, device=a.device)
+    idx = torch.empty(na, dtype=torch.int32, device=a.device)
+    _call("movae_knn_rows", a.data_ptr(), b.data_ptr(), na, nb, a.size(1), k, int(bool(exclude_diag)), int(tile or 0), norms.data_ptr(),
+          dist2.data_ptr(), idx.data_ptr(), _st(a))
+    return dist2, idx

@@ -2,8 +2,9 @@
 :1088-1497 (main) and :1500-1670 (argparse), restricted to what the per-step path needs.
 
 Differences that are by design: the step's device->host reads (losses, hook values) are
-batched into ONE copy per step instead of ~K+5 `.item()` syncs; evaluation metrics that need a
-pretrained Inception (FID/IS) and dataset downloads are out of scope -- the reference's datasets are
+batched into ONE copy per step instead of ~K+5 `.item()` syncs; the metrics that need a pretrained
+Inception (rFID; gFID / IS / KID / precision-recall with --gen_metrics on) run on weights the caller
+registers, and weight and dataset downloads are out of scope -- the reference's datasets are
 read from files already on disk and held on the device as uint8 (data.py), `--dataset synthetic_*`
 provides seeded in-memory data of the right shape; with torchrun (WORLD_SIZE>1) the batch is sharded
 and the aggregated gradient is all-reduced once per step over RCCL.
@@ -478,8 +479,79 @@ def evaluate_recon_metrics(net, loader, device, args):
     return acc.result()
 
 
+GEN_METRIC_KEYS = ("gfid", "inception_score_mean", "inception_score_std", "precision", "recall", "kid")
+GEN_MIN_SIDE = 32  # main.py:826 min_size_for_imagenet_metrics
+#: what the last evaluate_generative_metrics call scored (tests and callers that want the sets): {"n", "real_features",
+#: "fake_features", "probs"} on the device; empty when the stage returned NaN without generating
+LAST_GEN = {}
+
+
+@torch.no_grad()
+def evaluate_generative_metrics(net, test_loader, device, args, prior=None):
+    """main.py:695-887 -> {'gfid', 'inception_score_mean', 'inception_score_std', 'precision', 'recall', 'kid'}.  Images never go to
+    the host: samples are drawn batch by batch at --batch_size (through `prior` with --prior_sampler / --pixelcnn_temperature where one
+    is given, else net.sample) and each batch is scored at once -- its bicubic-pipeline features (gFID, KID, precision / recall) and
+    its bilinear-pipeline class probabilities (IS) are all that is kept; the real images of test_loader give features only.  Both
+    sets are cut to n = min(generated, real, --max_gen_metrics_samples).  Everything is NaN, and nothing is generated, for a sample
+    count <= 0 or without registered Inception-v3 weights; likewise for a side below 32 or above 299 or a channel count other than 3
+    (seen on the first batch).  IS alone is NaN when the weights carry no classifier.  Precision / recall (k = 3) only with
+    --gen_precision_recall: the reference has the call commented out as expensive."""
+    from . import metrics as M
+    from . import prior as _prior
+
+    out = {k: float("nan") for k in GEN_METRIC_KEYS}
+    LAST_GEN.clear()
+    num = int(getattr(args, "max_gen_metrics_samples", 0))
+    weights = M._inception_weights()
+    if num <= 0 or weights is None:
+        return out
+    device = torch.device(device)
+    net.eval()
+    fake_feats, probs, real_feats = [], [], []
+    try:
+        made = 0
+        while made < num:
+            b = min(args.batch_size, num - made)
+            if prior is not None:
+                samples = _prior.generate_samples_vq_with_prior(net, prior, b, device, temperature=getattr(args, "pixelcnn_temperature", 1.0),
+                                                                cached=_prior.PRIOR_SAMPLERS[getattr(args, "prior_sampler", "full")])
+            else:
+                samples = net.sample(num_samples=b, device=device)
+            if samples is None or samples.numel() == 0:
+                break
+            if samples.size(1) != 3 or samples.size(-1) < GEN_MIN_SIDE or max(samples.shape[-2:]) > 299:
+                print(f"Warning: generative metrics skipped for samples of shape {tuple(samples.shape)} (3 channels, sides {GEN_MIN_SIDE} .. 299)")
+                return out
+            fake_feats.append(M.inception_features(samples))
+            if weights.num_classes:
+                probs.append(M.inception_probs(samples))
+            made += samples.size(0)
+        got = 0
+        for images, _ in test_loader:
+            if got >= num:
+                break
+            images = images[: num - got].to(device)
+            if images.size(0):
+                real_feats.append(M.inception_features(images))
+                got += images.size(0)
+        n = min(made, got)
+        if n > 0:
+            real_f, fake_f = torch.cat(real_feats)[:n], torch.cat(fake_feats)[:n]
+            LAST_GEN.update(n=n, real_features=real_f, fake_features=fake_f, probs=torch.cat(probs)[:n] if probs else None)
+            out["gfid"] = M.fid_from_features(real_f, fake_f)
+            out["kid"] = M.kid_from_features(real_f, fake_f, seed=getattr(args, "seed", None))
+            if getattr(args, "gen_precision_recall", False):
+                out["precision"], out["recall"] = M.precision_recall_from_features(real_f, fake_f, k=3)
+            if probs:
+                out["inception_score_mean"], out["inception_score_std"] = M.inception_score_from_probs(LAST_GEN["probs"])
+    finally:
+        M.release_inception_buffers(device)
+    return out
+
+
 #: the final evaluation of the last train.main run on rank 0 (main.py:1457-1470): {"losses": {key: avg}, "recon": {rfid, psnr,
-#: ssim, lpips}}; empty when it did not run (--max_fid_samples 0, other ranks)
+#: ssim, lpips}, "gen": evaluate_generative_metrics' dict (only with --gen_metrics on)}; empty when it did not run
+#: (--max_fid_samples 0, other ranks)
 LAST_FINAL = {}
 
 
@@ -669,6 +741,13 @@ def build_parser():
                    help="auto (default): a real image set is kept on the device as uint8 and each batch is assembled there by one "
                         "kernel (gather, flip, ToTensor / Normalize); synthetic sets keep the host DataLoader.  host: the DataLoader "
                         "for every set (a set too large for the device).  device: refuse a set that has no uint8 form")
+    p.add_argument("--gen_metrics", choices=["off", "on"], default="off",
+                   help="on: after the final reconstruction pass, draw --max_gen_metrics_samples images from the model (VQ "
+                        "architectures through the trained prior) and report gFID, Inception Score and KID against as many test "
+                        "images (main.py:1458 evaluate_generative_metrics; needs registered Inception-v3 weights, else NaN).  off "
+                        "(default): no generation, no extra output")
+    p.add_argument("--gen_precision_recall", action="store_true",
+                   help="with --gen_metrics on: precision and recall (k = 3) too, which the reference leaves commented out as expensive")
     p.add_argument("--max_items", type=int, default=None, help="cap the dataset length (test set: a tenth of it)")
     p.add_argument("--max_steps", type=int, default=None, help="stop after this many optimisation steps")
     return p
@@ -835,6 +914,7 @@ def main(args):
         if scheduler is not None:
             ckpt["scheduler_state_dict"] = scheduler.state_dict()
         torch.save(ckpt, os.path.join(save_root, "checkpoints", "final_checkpoint.pth"))
+    trained_prior = None  # (kept for the generative evaluation: VQ architectures sample through it)
     if rank0 and _is_vq_arch(args.arch) and not getattr(args, "skip_pixelcnn", False):  # main.py:1438-1497
         from . import prior as _prior
 
@@ -843,7 +923,7 @@ def main(args):
         prior_loader = train_loader
         if dp is not None:
             prior_loader = make_loader(train_ds, args.batch_size, device, args, shuffle=True)
-        _prior.train_pixelcnn_prior(net, prior_loader, device, args, save_root)
+        trained_prior = _prior.train_pixelcnn_prior(net, prior_loader, device, args, save_root)
     if rank0 and getattr(args, "max_fid_samples", 0) > 0:  # main.py:1457-1470, after the prior stage like the reference
         final_meters, recon = evaluate_with_recon_metrics(net, test_loader, device, args)
         losses = {k: m.avg for k, m in final_meters.items()}
@@ -853,6 +933,13 @@ def main(args):
             log({**{f"final/eval_{k}": v for k, v in losses.items()}, **{f"final/{k}": recon[k] for k in ("rfid", "psnr", "ssim", "lpips")}},
                 step)
         LAST_FINAL.update(losses=losses, recon=recon)
+    if rank0 and getattr(args, "gen_metrics", "off") == "on":  # main.py:1458-1470, after the reconstruction pass
+        gen = evaluate_generative_metrics(net, test_loader, device, args, prior=trained_prior)
+        order = ("gfid", "inception_score_mean", "inception_score_std", "kid", "precision", "recall")
+        print("generative: " + ", ".join(f"{k}: {gen[k]:.6f}" for k in order))
+        if log is not None:
+            log({f"final/{k}": gen[k] for k in order}, step)
+        LAST_FINAL["gen"] = gen
     if dp is not None:
         dp.shutdown()
     return history
