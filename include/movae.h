@@ -862,6 +862,28 @@ int movae_kid_subsets(const float* real, const float* fake, const int* idx_real,
 int movae_knn_rows(const float* a, const float* b, int na, int nb, int D, int k, int exclude_diag, int tile, float* norms, float* dist2,
                    int* idx, movae_stream_t stream);
 
+/* ---- image grids as bytes (csrc/visual.hip; the figures of main.py:511-656) -------------------------------------------------------
+ * A float image batch x, logical [n][c][h][w] given by pointer and four element strides (NCHW, channels_last and sliced views alike, no
+ * copy), becomes the finished picture out [H][W][3] uint8: torchvision's make_grid followed by save_image's quantisation.
+ *   xmaps = min(nrow, n), ymaps = ceil(n / xmaps); H = ymaps * (h + padding) + padding, W = xmaps * (w + padding) + padding; image k has
+ *   its top-left corner at ((k / xmaps) * (h + padding) + padding, (k % xmaps) * (w + padding) + padding); every byte outside an image,
+ *   whole cells beyond n included, is pad_value, quantised and never normalised; n == 1 gives the image itself (H = h, W = w, no
+ *   border); c == 1 is written to all three channels.
+ * Per pixel, in fp32 and in this order: mode RAW: v = x; mode RANGE: v = (min(max(x, lo), hi) - lo) / max(hi - lo, 1e-5f) with the
+ * given lo, hi; mode MINMAX: the same with lo, hi the minimum and maximum over the whole batch, found on the device (lo, hi ignored);
+ * then byte = (uint8) min(max(v * 255 + 0.5f, 0), 255), truncating; a NaN pixel gives 0.  The division is an IEEE division.
+ * Mode MINMAX is two launches (per-block partials into ws, folded by every block of the second launch) and needs
+ * ws >= movae_image_grid_ws_bytes bytes (the 4096-byte header included; only the scratch behind it is used); the other modes are one
+ * launch and ignore ws.  No atomics, no host read; capturable.  Refused (MOVAE_EINVAL, nothing launched): a null x or out; n, h, w or
+ * nrow <= 0; padding < 0; c not in {1, 3}; a mode outside 0 .. 2; hi < lo in mode RANGE; in mode MINMAX a null or too small workspace. */
+#define MOVAE_GRID_RAW 0
+#define MOVAE_GRID_RANGE 1
+#define MOVAE_GRID_MINMAX 2
+size_t movae_image_grid_ws_bytes(int n, int c, int h, int w);
+int movae_image_grid_u8(const float* x, long long sn, long long sc, long long sh, long long sw, int n, int c, int h, int w, int nrow,
+                        int padding, float pad_value, int mode, float lo, float hi, uint8_t* out, void* ws, size_t ws_bytes,
+                        movae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

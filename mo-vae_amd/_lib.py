@@ -182,6 +182,8 @@ SIGNATURES = {
     "movae_batch_rrc_u8": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_resample_coeffs": ([_p, _i, _i, _i, _p, _p, _p], _i),
     "movae_codes_batch": ([_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p], _i),
+    "movae_image_grid_ws_bytes": ([_i, _i, _i, _i], _z),
+    "movae_image_grid_u8": ([_p] + [C.c_longlong] * 4 + [_i] * 6 + [_f, _i, _f, _f, _p, _p, _z, _p], _i),
     "movae_bench_main_kernel_only": ([_i], _i),
     "movae_bench_last_kernel": ([], C.c_char_p),
     "movae_bench_last_reduce": ([], C.c_char_p),

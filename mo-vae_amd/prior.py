@@ -331,6 +331,7 @@ def train_pixelcnn_prior(net, train_loader, device, args, save_root, prior=None)
                                              cached=PRIOR_SAMPLERS[getattr(args, "prior_sampler", "full")])
     LAST_RUN.clear()
     LAST_RUN.update(net=net, prior=prior, epoch_losses=epoch_losses, use_cache=use_cache, n_codes=n_codes, samples=samples.detach().cpu(),
+                    samples_device=samples.detach(),  # the same draw where it was made (train.main's "with prior" grid)
                     num_embeddings=K, loader=loader_mode, step_mode=step_mode,
                     replayed_steps=graphed.replayed_steps if graphed is not None else 0,
                     eager_steps=eager_steps + (graphed.eager_steps if graphed is not None else 0))

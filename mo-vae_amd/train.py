@@ -553,6 +553,9 @@ def evaluate_generative_metrics(net, test_loader, device, args, prior=None):
 #: ssim, lpips}, "gen": evaluate_generative_metrics' dict (only with --gen_metrics on)}; empty when it did not run
 #: (--max_fid_samples 0, other ranks)
 LAST_FINAL = {}
+#: the last train.main call: {"save_root": its run directory (<save_path>/<dataset>/<arch>/<optimizer>/<aggregator>/<stamp>),
+#: "net": the trained model as the run left it}
+LAST_RUN = {}
 
 
 # ---- data ----------------------------------------------------------------------------------------
@@ -748,6 +751,11 @@ def build_parser():
                         "(default): no generation, no extra output")
     p.add_argument("--gen_precision_recall", action="store_true",
                    help="with --gen_metrics on: precision and recall (k = 3) too, which the reference leaves commented out as expensive")
+    p.add_argument("--vis", choices=["off", "on"], default="off",
+                   help="on: rank 0 writes image grids under <run>/figures/ for epoch 1, every --save_freq-th epoch and the last one "
+                        "(--num_vis_samples random samples, test and train reconstructions; main.py:1391-1420) and, after the prior "
+                        "stage, the samples that stage draws (visual.py).  The pass does not move the training trajectory.  off "
+                        "(default): no pictures, no figures directory")
     p.add_argument("--max_items", type=int, default=None, help="cap the dataset length (test set: a tenth of it)")
     p.add_argument("--max_steps", type=int, default=None, help="stop after this many optimisation steps")
     return p
@@ -867,6 +875,9 @@ def main(args):
     objective_keys = list(net.objectives.keys())
     hv_indicator = build_hv_indicator(objective_keys, args)  # main.py:1283
     LAST_FINAL.clear()
+    vis_on = getattr(args, "vis", "off") == "on"
+    if vis_on:
+        from . import visual as _visual
     for epoch in range(1, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -902,13 +913,17 @@ def main(args):
                       + (f", HV: {eval_hv:.2e}" if eval_hv is not None else ""))
         if log is not None and rank0:
             log(epoch_log, step)
+        if rank0 and vis_on and (epoch == 1 or (args.save_freq and epoch % args.save_freq == 0) or epoch == args.epochs):
+            _visual.write_epoch_figures(net, train_loader, test_loader, device, args, save_root, epoch, step=step,
+                                        log_to_wandb=log is not None)
         if scheduler is not None:
             scheduler.step()
         if args.max_steps is not None and step >= args.max_steps:
             break
     if rank0:  # main.py:1422-1436: save-only checkpoint with the reference's keys and value shapes
         ckpt = {"epoch": args.epochs, "model_state_dict": {k: v.contiguous() for k, v in net.state_dict().items()},
-                "args": vars(args), "train_losses": dict(history[-1]) if history else {}, "eval_losses": dict(eval_rec),
+                "args": vars(args), "input_size": input_size,  # (checkpoint.load_run rebuilds the net without the dataset)
+                "train_losses": dict(history[-1]) if history else {}, "eval_losses": dict(eval_rec),
                 "best_eval_loss": best,
                 "train_history": history}  # addition of this build: every epoch's averages (the reference keeps the last only)
         if scheduler is not None:
@@ -924,6 +939,9 @@ def main(args):
         if dp is not None:
             prior_loader = make_loader(train_ds, args.batch_size, device, args, shuffle=True)
         trained_prior = _prior.train_pixelcnn_prior(net, prior_loader, device, args, save_root)
+        if vis_on:  # main.py:1480-1497, from the samples the stage has just drawn (no second draw)
+            _visual.write_random_samples(_prior.LAST_RUN["samples_device"],
+                                         os.path.join(save_root, "figures", "generated", "final_random_samples_with_prior.png"))
     if rank0 and getattr(args, "max_fid_samples", 0) > 0:  # main.py:1457-1470, after the prior stage like the reference
         final_meters, recon = evaluate_with_recon_metrics(net, test_loader, device, args)
         losses = {k: m.avg for k, m in final_meters.items()}
@@ -942,6 +960,8 @@ def main(args):
         LAST_FINAL["gen"] = gen
     if dp is not None:
         dp.shutdown()
+    LAST_RUN.clear()
+    LAST_RUN.update(save_root=save_root, net=net)
     return history
 
 
