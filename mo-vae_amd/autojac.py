@@ -90,7 +90,6 @@ def _accumulate(p, g, taken=()):
 
 #: MOVAE_PERSISTENT_J=0: a fresh zero-filled Jacobian arena per step (A/B knob)
 PERSISTENT_J = os.environ.get("MOVAE_PERSISTENT_J", "1") != "0"
-_J_CACHE = {}  # (device, K, parameter identities) -> JacobianBuffer, the few most recently used
 
 
 class JacobianBuffer:
@@ -103,6 +102,7 @@ class JacobianBuffer:
 
     def __init__(self, params, k, device):
         self.params = params
+        self.key = (k, str(device), [p.numel() for p in params])  # what `persistent` matches besides the parameters themselves
         self.offsets, off = [], 0
         for p in params:
             self.offsets.append(off)
@@ -115,16 +115,19 @@ class JacobianBuffer:
 
     @classmethod
     def persistent(cls, params, k, device):
+        """The arena of (k, these very parameters), kept across steps on the first of them (`_movae_j_arenas`, as _task_grad_buffer
+        keeps a gradient buffer on its parameter): it lives as long as the parameters it describes -- hence as long as any captured
+        graph that holds its address, a GraphedTrainStep keeps its model -- and is released with them; nothing else refers to it."""
         if not PERSISTENT_J:
             return cls(params, k, device)
-        key = (str(device), k, tuple((id(p), p.numel()) for p in params))
-        jb = _J_CACHE.pop(key, None)
-        if jb is None or any(a is not b for a, b in zip(jb.params, params)):
-            jb = cls(list(params), k, device)
+        params = list(params)
+        arenas = params[0].__dict__.setdefault("_movae_j_arenas", []) if params else []
+        key = (k, str(device), [p.numel() for p in params])
+        jb = next((a for a in arenas if a.key == key and all(p is q for p, q in zip(a.params, params))), None)
+        if jb is None:
+            jb = cls(params, k, device)
             jb.dirty = {}
-        _J_CACHE[key] = jb  # (re-inserted last: most recently used)
-        while len(_J_CACHE) > 4:
-            _J_CACHE.pop(next(iter(_J_CACHE)))
+            arenas.append(jb)
         jb.copied = set()
         ops.SINK_LOG.clear()
         ops.SINK_ZERO_LOG.clear()
@@ -460,6 +463,7 @@ def _mtl_backward_finish(st):
             ops.GRAD_SINK.clear()
         jb.write_row(i, js)
     if shared_params:
+        ops.flush_deferred()  # the last weight gradient's reduce may still be parked; the aggregator may start with a torch op on J
         jb.settle()
         _aggregate_into_grads(jb, st.aggregator)
 

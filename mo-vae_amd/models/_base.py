@@ -34,19 +34,20 @@ def resolve_lambda_weights(owner, objectives, lambda_weights, defaults, list_ord
 
 
 class LazyDict(dict):
-    """A forward() result whose function-valued entries are computed on first read.  VQ-VAE-2's `commitment_loss` /
-    `embedding_loss` are sums of the two codebooks' terms (models/vq_vae2.py:291-292): loss_function consumes the four terms
-    directly, so in a training step nobody reads the sums and their launches are never made; any other reader (`out[key]`,
-    .get, .items(), .values()) sees ordinary tensors."""
-
-    def _resolve(self, key, v):
-        if callable(v) and not isinstance(v, torch.Tensor) and getattr(v, "__name__", "") == "<lambda>":
-            v = v()
-            dict.__setitem__(self, key, v)
-        return v
+    """A forward() result whose function-valued entries are computed when they are read, on EVERY read: a captured step hands out
+    the same dict after each replay, and the tensors the functions close over have new values then.  VQ-VAE-2's `commitment_loss`
+    / `embedding_loss` are sums of the two codebooks' terms (models/vq_vae2.py:291-292): loss_function consumes the four terms
+    directly, so in a training step nobody reads the sums and their launches are never made; any other reader (`out[key]`, .get,
+    .items(), .values(), .copy(), dict(out), {**out}) sees ordinary tensors -- no way out of the dict hands over a function."""
 
     def __getitem__(self, key):
-        return self._resolve(key, dict.__getitem__(self, key))
+        v = dict.__getitem__(self, key)
+        if callable(v) and not isinstance(v, torch.Tensor) and getattr(v, "__name__", "") == "<lambda>":
+            v = v()
+        return v
+
+    def __iter__(self):  # (defined here: dict(out) and {**out} copy a dict subclass's raw values unless it has its own __iter__)
+        return dict.__iter__(self)
 
     def get(self, key, default=None):
         return self[key] if key in self else default
@@ -56,6 +57,9 @@ class LazyDict(dict):
 
     def values(self):
         return [self[k] for k in self.keys()]
+
+    def copy(self):
+        return dict(self.items())
 
 
 class LazyScalar:
@@ -152,11 +156,19 @@ class HotPathModel(tnn.Module):
     noise_on_device = False
     _noise_state_t = None
 
-    def _recon(self, fn, inputs, recons, weight, plain_cls):
+    #: the ops.ActLink of the decoder's last conv + tanh / sigmoid pair: decode() moves it here from the nn.Stack that produced
+    #: `recons` (its `_out_link`), loss_function takes it -- a model holds at most its latest forward's, none once the loss is built
+    _recons_link = None
+
+    def _take_recons_link(self):
+        link, self._recons_link = self._recons_link, None
+        return link
+
+    def _recon(self, fn, inputs, recons, weight, plain_cls, link):
         """The reconstruction objective; in the PLAIN model `plain_cls` (not a subclass that adds losses on `recons`: those would be
-        further readers) it is told that it is the one reader of the decoder's output activation (objectives._make: out_act)."""
+        further readers) it is the one reader of the decoder's output activation and gets that pair's `link` (objectives._make)."""
         if type(self) is plain_cls and getattr(fn, "kind", None) in ops.L.RECON:
-            return fn(inputs, recons, weight, out_act=True)
+            return fn(inputs, recons, weight, act_link=link)
         return fn(inputs, recons, weight)
 
     def _noise_state(self, device):

@@ -54,7 +54,9 @@ class BetaTCVAE(HotPathModel):
 
     def decode(self, z):
         h = ops.unflatten_nchw(self.decoder_input(z), self.hidden_dims[-1], self._sp, self._sp)
-        return nchw_view(mnn.chain(h, self.decoder, self.final_layer))
+        y = mnn.chain(h, self.decoder, self.final_layer)
+        self._recons_link, self.final_layer._out_link = self.final_layer._out_link, None  # the output activation's link, for _recon
+        return nchw_view(y)
 
     graph_safe = True
     _iter_dev = None
@@ -91,7 +93,8 @@ class BetaTCVAE(HotPathModel):
     def loss_function(self, inputs, args: dict) -> dict:
         lw = self.lambda_weights
         z = args["z"]
-        rec = self._recon(self.objectives["reconstruction_loss"], inputs, args["recons"], lw["reconstruction_loss"], BetaTCVAE)
+        rec = self._recon(self.objectives["reconstruction_loss"], inputs, args["recons"], lw["reconstruction_loss"], BetaTCVAE,
+                          self._take_recons_link())
         terms = ops.tc_decomposition(z, args["mu"], args["log_var"], self._log_importance_weights(z.shape[0], z.device))
         if os.environ.get("MOVAE_FUSE_LOSSES", "1") != "0" and rec.is_cuda:
             # weights, annealing and the total in one launch (ops.CombineLosses) instead of eight; the annealing counter is

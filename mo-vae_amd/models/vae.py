@@ -94,14 +94,14 @@ class VAE(HotPathModel):
 
     def loss_function(self, inputs, args: dict) -> dict:
         lw = self.lambda_weights
+        link = self._take_recons_link()
         rec_fn, kld_fn = self.objectives["reconstruction_loss"], self.objectives["kld_loss"]
         if (type(self) is VAE and getattr(rec_fn, "kind", None) in ops.L.RECON and kld_fn is O.kl_divergence and inputs.dim() == 4
                 and args["mu"].dim() == 2 and os.environ.get("MOVAE_FUSE_LOSSES", "1") != "0"):
             # both terms and their sum from one final kernel (ops.VAELosses): the same values, two launches fewer
             x, r = ops.to_nhwc(inputs), ops.to_nhwc(args["recons"])
-            link = getattr(self, "_recons_link", None)
             rec, kld, total = ops.vae_losses(r, x, rec_fn.kind, lw["reconstruction_loss"], args["mu"], args["log_var"], lw["kld_loss"],
-                                             act_link=link if (link is not None and link.y is not None and link.y.data_ptr() == r.data_ptr()) else None)
+                                             act_link=link)
             return {"reconstruction_loss": rec, "kld_loss": kld, "total_loss": total}
         rec = self.objectives["reconstruction_loss"](inputs, args["recons"], lw["reconstruction_loss"])
         kld = self.objectives["kld_loss"](args["mu"], args["log_var"], lw["kld_loss"])

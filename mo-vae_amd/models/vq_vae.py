@@ -116,7 +116,9 @@ class VQVAE(HotPathModel):
         return nchw_view(self.encoder(ops.to_nhwc(x)))
 
     def decode(self, z):
-        return nchw_view(self.decoder(ops.to_nhwc(z)))
+        y = self.decoder(ops.to_nhwc(z))
+        self._recons_link, self.decoder._out_link = self.decoder._out_link, None  # the output activation's link, for _recon
+        return nchw_view(y)
 
     def forward(self, x, **kwargs):
         encoding = self.encode(x)
@@ -133,11 +135,12 @@ class VQVAE(HotPathModel):
 
     def loss_function(self, inputs, args: dict) -> dict:
         lw, ld = self.lambda_weights, {}
+        link = self._take_recons_link()
         keys = list(self.objectives)
         if keys == ["reconstruction_loss", "embedding_loss", "commitment_loss"] and os.environ.get("MOVAE_FUSE_LOSSES", "1") != "0" \
                 and args["recons"].is_cuda:
             # the two weights and the total in one launch (ops.CombineLosses) instead of four
-            rec = self._recon(self.objectives["reconstruction_loss"], inputs, args["recons"], lw["reconstruction_loss"], VQVAE)
+            rec = self._recon(self.objectives["reconstruction_loss"], inputs, args["recons"], lw["reconstruction_loss"], VQVAE, link)
             coef = [[1.0, 0, 0], [0, lw["embedding_loss"], 0], [0, 0, lw["commitment_loss"]]]
             rec, emb, com, total = ops.combine_losses([rec, args["embedding_loss"], args["commitment_loss"]], coef)
             return {"reconstruction_loss": rec, "embedding_loss": emb, "commitment_loss": com, "total_loss": total}

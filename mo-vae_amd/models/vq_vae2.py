@@ -1,6 +1,7 @@
 """Hierarchical VQ-VAE-2 on the HIP kernels -- drop-in for the reference's models/vq_vae2.py
 (ResBlock :12-28, Encoder :31-58, Decoder :61-103, VQVAE2 :106-390)."""
 import os
+import weakref
 
 import torch
 
@@ -67,11 +68,14 @@ class Decoder(torch.nn.Module):
         self.blocks = mnn.Stack(*blocks)
 
     def forward(self, x):
-        return self.blocks(x)
+        y = self.blocks(x)
+        self._out_link, self.blocks._out_link = self.blocks._out_link, None  # exposed like an nn.Stack's own
+        return y
 
 
 class VQVAE2(HotPathModel):
     graph_safe = True  # codebook usage stays on the device (LazyScalar)
+    _vq_terms = None  # (c_t, c_b, e_t, e_b) of the latest forward, for loss_function
 
     def __init__(self, in_channels, embedding_dim, num_embeddings, hidden_dims=(128, 256), num_residual_layers=2,
                  input_size=64, layer_norm="none", recons_activation="tanh", recons_objective="mse", lambda_weights=None,
@@ -120,7 +124,9 @@ class VQVAE2(HotPathModel):
 
     def decode(self, quant_t, quant_b):
         up = self.upsample_t(ops.to_nhwc(quant_t))
-        return nchw_view(self.dec(ops.concat_channels(up, ops.to_nhwc(quant_b))))
+        y = self.dec(ops.concat_channels(up, ops.to_nhwc(quant_b)))
+        self._recons_link, self.dec._out_link = self.dec._out_link, None  # the output activation's link, for _recon
+        return nchw_view(y)
 
     def decode_code(self, code_t, code_b):
         q_t = self.quantize_t.embed_code(code_t).permute(0, 3, 1, 2)
@@ -133,11 +139,12 @@ class VQVAE2(HotPathModel):
         K = self.num_embeddings
         used_t, used_b = self._used
         usage = LazyScalar([used_t, used_b], 100.0 / K / 2.0)  # mean of the two codebooks' usage, read lazily
-        # the two sums are formed only if somebody reads them: loss_function takes the four terms (one launch for all of it)
+        # the two sums are formed only if somebody reads them: loss_function takes the four terms (one launch for all of it),
+        # kept on the model with a weak reference to the `recons` they came with
+        self._vq_terms, self._vq_terms_of = (c_t, c_b, e_t, e_b), weakref.ref(recons)
         out = LazyDict({"recons": recons, "encoding_top": enc_t, "encoding_bottom": enc_b, "quantized_top": quant_t,
                         "quantized_bottom": quant_b, "commitment_loss": lambda: c_t + c_b, "embedding_loss": lambda: e_t + e_b,
-                        "codebook_usage_percentage": usage, "encoding_inds_top": i_t, "encoding_inds_bottom": i_b,
-                        "_vq_terms": (c_t, c_b, e_t, e_b)})
+                        "codebook_usage_percentage": usage, "encoding_inds_top": i_t, "encoding_inds_bottom": i_b})
         return out["recons"] if self._summary_mode else out
 
     def get_code_indices(self, x):
@@ -150,8 +157,9 @@ class VQVAE2(HotPathModel):
 
     def loss_function(self, inputs, args: dict) -> dict:
         lw = self.lambda_weights
-        rec = self._recon(self.recon_obj, inputs, args["recons"], lw["reconstruction_loss"], VQVAE2)
-        terms = args.get("_vq_terms") if os.environ.get("MOVAE_FUSE_LOSSES", "1") != "0" and rec.is_cuda else None
+        rec = self._recon(self.recon_obj, inputs, args["recons"], lw["reconstruction_loss"], VQVAE2, self._take_recons_link())
+        terms = self._vq_terms if (os.environ.get("MOVAE_FUSE_LOSSES", "1") != "0" and rec.is_cuda and self._vq_terms is not None
+                                   and self._vq_terms_of() is args["recons"]) else None
         if terms is not None:
             # top + bottom, the weights and the total in one launch (ops.CombineLosses); `terms` = (c_t, c_b, e_t, e_b)
             wc, we = lw["commitment_loss"], lw["embedding_loss"]

@@ -257,12 +257,13 @@ class Stack(tnn.Sequential):
 def chain(x, *stacks):
     """stacks[-1](... stacks[0](x)) for Stacks that a model keeps as separate attributes (decoder -> final_layer): the activation
     link of each Stack's output is handed to the next one, as an enclosing Stack would.  Each intermediate result must have no other
-    reader (ops.ActLink)."""
+    reader (ops.ActLink).  The last Stack's link stays on it (`stacks[-1]._out_link`), as after a call of that Stack alone: it is
+    the caller's to take."""
     link = None
-    for s in stacks:
+    for s in stacks[:-1]:
         x = s(x, link)
         link, s._out_link = s._out_link, None
-    return x
+    return stacks[-1](x, link)
 
 
 class Codebook(tnn.Module):

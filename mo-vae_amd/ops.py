@@ -120,21 +120,17 @@ def _stacked(t, G):
     return _c(t)
 
 
-_ZERO_GRADS = {}
-
-
 def _sink_zeros(g, param, shape):
     """An all-zero gradient: sinks are zero-initialised by their owner (autojac.JacobianBuffer) and written at most
     once, so a registered sink is returned untouched -- no fill launch.  Without a sink the parameter gets ONE persistent
-    zero tensor for life (a bias in front of a training-mode BatchNorm: its gradient is identically zero, so whatever is
-    accumulated into this tensor later is zero as well); nothing here launches a fill per step."""
+    zero tensor for life, kept on the parameter itself (a bias in front of a training-mode BatchNorm: its gradient is identically
+    zero, so whatever is accumulated into this tensor later is zero as well); nothing here launches a fill per step."""
     dst = _registered(GRAD_SINK, param, shape, SINK_ZERO_LOG)
     if dst is not None:
         return dst
-    key = (param.data_ptr(), param.numel(), param.dtype)
-    z = _ZERO_GRADS.get(key)
-    if z is None or z.device != param.device:
-        z = _ZERO_GRADS[key] = torch.zeros(param.numel(), dtype=param.dtype, device=param.device)
+    z = getattr(param, "_movae_zero_grad", None)
+    if z is None or z.numel() != param.numel() or z.dtype != param.dtype or z.device != param.device:
+        z = param._movae_zero_grad = torch.zeros(param.numel(), dtype=param.dtype, device=param.device)
     return z.view(shape)
 
 
@@ -307,7 +303,8 @@ class deferred_reduces:
     entry points) is not launched on the spot: the library parks it and the next implicit-GEMM launch of the backward carries it
     as extra blocks (include/movae.h: movae_reduce_defer).  The block's exit -- and every library call that
     is not one of the backward's own ops (_lib.DEFER_PASS) -- launches a reduce that is still parked; code that hands a weight
-    gradient to anything else (torch arithmetic, a collective) inside the block calls flush_deferred() first."""
+    gradient to anything else (torch arithmetic, a collective, a caller's aggregator) inside the block calls flush_deferred()
+    first: autojac does so before it adds two gradients with torch and, once the pull-back is done, before the aggregator sees J."""
 
     def __init__(self, enabled=True):
         self.enabled = enabled and DEFER_REDUCE
@@ -335,18 +332,6 @@ def _defer_ws(t, sunk):
     if sunk and L.DEFER_ON[0]:
         return L.defer_arm(t.device)
     return None
-
-
-#: data_ptr of the output of a conv + tanh / sigmoid pair that ends its nn.Stack -> that pair's ActLink: a reconstruction loss that is the
-#: output's one reader looks the link up (out_act_link) and applies the derivative in its own backward kernel
-OUT_ACT_LINKS = {}
-
-
-def out_act_link(recons):
-    link = OUT_ACT_LINKS.get(recons.data_ptr()) if FUSE_ACT else None
-    if link is None or link.y is None or link.y.data_ptr() != recons.data_ptr() or link.y.shape != recons.shape:
-        return None
-    return link
 
 
 class ActLink:
@@ -636,10 +621,6 @@ class Conv(Function):
         if fusion is not None and fusion.act_out is not None and L.ACT[act]:
             ctx.act_out = fusion.act_out
             ctx.act_out.y, ctx.act_out.act, ctx.act_out.slope, ctx.act_out.applied = y.detach(), act, slope, None
-            if act in ("tanh", "sigmoid"):
-                if len(OUT_ACT_LINKS) > 64:
-                    OUT_ACT_LINKS.clear()
-                OUT_ACT_LINKS[y.data_ptr()] = ctx.act_out
         ctx.save_for_backward(x, w, y if L.ACT[act] else None, b, *(in_norm[:2] if in_norm is not None else ()))
         return y
 
@@ -1359,6 +1340,13 @@ def reparameterize_prior_rng(mu, log_var, state, n_prior):
 
 
 # ---------------------------------------------------------------------------------------------
+def _links_output(link, recons):
+    """Is `link` the ActLink of the conv + tanh / sigmoid pair that produced this very `recons`?  (The caller vouches that the loss
+    is the one reader of `recons` on the tape; whether the link it took from its decoder belongs to this tensor is checked here.)"""
+    return (FUSE_ACT and link is not None and link.act in ("tanh", "sigmoid") and link.y is not None
+            and link.y.data_ptr() == recons.data_ptr() and link.y.shape == recons.shape)
+
+
 class ReconLoss(Function):
     """scale * mean(objective(recons, inputs)); both tensors must share one memory order."""
 
@@ -1374,8 +1362,7 @@ class ReconLoss(Function):
               float(scale), wsp, wsb, _st(recons))
         ctx.kind, ctx.scale = kind, scale
         # recons = act(pre), this loss its one reader (ActLink): the backward kernel hands the producing conv the PRE-activation gradient
-        ctx.act_link = act_link if (FUSE_ACT and act_link is not None and act_link.act in ("tanh", "sigmoid") and act_link.y is not None
-                                    and act_link.y.data_ptr() == recons.data_ptr()) else None
+        ctx.act_link = act_link if _links_output(act_link, recons) else None
         ctx.save_for_backward(recons, inputs)
         return out
 
@@ -1529,7 +1516,7 @@ class VAELosses(Function):
         ctx.kind, ctx.scale_r, ctx.scale_k = kind, scale_r, scale_k
         # recons = act(pre) is the decoder's output activation and this loss its one reader (ActLink): the backward kernel applies
         # act'(pre) and hands the producing conv the PRE-activation gradient
-        ctx.act_link = act_link if (FUSE_ACT and act_link is not None and act_link.act in ("tanh", "sigmoid")) else None
+        ctx.act_link = act_link if _links_output(act_link, recons) else None
         ctx.save_for_backward(recons, inputs, mu, log_var)
         return out[0], out[1], out[2]
 

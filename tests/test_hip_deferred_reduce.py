@@ -155,14 +155,12 @@ def test_flush_paths(gpu_device, park_any_size):
     assert lib.movae_reduce_defer(0) == 0
 
 
-@pytest.mark.parametrize("tag,batch", [("C2", 64), ("C3", 8), ("C4", 2), ("C5", 4)])
-def test_aggregated_step_identical_with_and_without_deferral(tag, batch, gpu_device, monkeypatch, park_any_size):
-    """One aggregated step (forward, per-loss backward, batched pull-back, UPGrad) of every BASELINE architecture -- the
-    configuration's layer shapes at a reduced batch -- with and without deferral: the same gradients bit for bit, and the
-    deferral did happen (reduces were parked, and carried by later launches)."""
+def _aggregated_step(tag, batch, on, make_aggregator, gpu_device, monkeypatch):
+    """One aggregated step (forward, per-loss backward, batched pull-back, aggregation) of a BASELINE architecture -- the
+    configuration's layer shapes at a reduced batch -- with deferral `on` or off -> ({parameter name: gradient}, deferral statistics)"""
     import movae_amd  # noqa: F401
     from movae_amd import _lib as L
-    from movae_amd import aggregation, autojac, ops
+    from movae_amd import autojac, ops
     from movae_amd.models import get_network
     from movae_amd.models.betatc_vae import BetaTCVAE
     from conftest import cfg_from_meta
@@ -172,31 +170,38 @@ def test_aggregated_step_identical_with_and_without_deferral(tag, batch, gpu_dev
     fx, m = _full_case(tag)
     c = cfg_from_meta(m)
     size = int(m["input_size"])
-    res = {}
-    for on in (True, False):
-        monkeypatch.setattr(ops, "DEFER_REDUCE", on)
-        args = Args(arch=c["arch"], batch_size=batch, dataset_size=c["dataset_size"], recons_objective="mse", recons_activation=None,
-                    loss_weights=None, **{k: v for k, v in c.items() if k in ("latent_dim", "hidden_dims", "embedding_dim",
-                                                                             "num_embeddings", "num_residual_layers", "anneal_steps")})
-        torch.manual_seed(3)
-        BetaTCVAE.num_iter = 0
-        net = get_network(size, num_channels=3, args=args, device=gpu_device).to(gpu_device).train()
-        x = torch.rand(batch, 3, size, size, generator=torch.Generator().manual_seed(4)).to(gpu_device)
-        if "latent_dim" in c:
-            net.eps_override = torch.randn(batch, c["latent_dim"], generator=torch.Generator().manual_seed(5)).to(gpu_device)
-        _stats(lib, reset=True)
-        out = net(x)
-        ld = net.loss_function(x, args=out)
-        comp = [v for k, v in ld.items() if k != "total_loss"]
-        autojac.mtl_backward(losses=comp, features=[out[f] for f in net.features], aggregator=aggregation.UPGrad())
-        torch.cuda.synchronize()
-        s, pending = _stats(lib)
-        assert pending == 0
-        if not on:
-            assert s == [0, 0, 0]
-        res[on] = ({n: (None if p.grad is None else p.grad.detach().cpu().numpy().copy()) for n, p in net.named_parameters()}, s)
-        del net, out, ld, comp
+    monkeypatch.setattr(ops, "DEFER_REDUCE", on)
+    args = Args(arch=c["arch"], batch_size=batch, dataset_size=c["dataset_size"], recons_objective="mse", recons_activation=None,
+                loss_weights=None, **{k: v for k, v in c.items() if k in ("latent_dim", "hidden_dims", "embedding_dim",
+                                                                         "num_embeddings", "num_residual_layers", "anneal_steps")})
+    torch.manual_seed(3)
     BetaTCVAE.num_iter = 0
+    net = get_network(size, num_channels=3, args=args, device=gpu_device).to(gpu_device).train()
+    x = torch.rand(batch, 3, size, size, generator=torch.Generator().manual_seed(4)).to(gpu_device)
+    if "latent_dim" in c:
+        net.eps_override = torch.randn(batch, c["latent_dim"], generator=torch.Generator().manual_seed(5)).to(gpu_device)
+    _stats(lib, reset=True)
+    out = net(x)
+    ld = net.loss_function(x, args=out)
+    comp = [v for k, v in ld.items() if k != "total_loss"]
+    autojac.mtl_backward(losses=comp, features=[out[f] for f in net.features], aggregator=make_aggregator())
+    torch.cuda.synchronize()
+    s, pending = _stats(lib)
+    assert pending == 0
+    if not on:
+        assert s == [0, 0, 0]
+    BetaTCVAE.num_iter = 0
+    return {n: (None if p.grad is None else p.grad.detach().cpu().numpy().copy()) for n, p in net.named_parameters()}, s
+
+
+@pytest.mark.parametrize("tag,batch", [("C2", 64), ("C3", 8), ("C4", 2), ("C5", 4)])
+def test_aggregated_step_identical_with_and_without_deferral(tag, batch, gpu_device, monkeypatch, park_any_size):
+    """One aggregated step (forward, per-loss backward, batched pull-back, UPGrad) of every BASELINE architecture -- the
+    configuration's layer shapes at a reduced batch -- with and without deferral: the same gradients bit for bit, and the
+    deferral did happen (reduces were parked, and carried by later launches)."""
+    from movae_amd import aggregation
+
+    res = {on: _aggregated_step(tag, batch, on, aggregation.UPGrad, gpu_device, monkeypatch) for on in (True, False)}
     (g1, s1), (g0, _) = res[True], res[False]
     parked, carried, alone = s1
     nonfinite = {on: [n for n, g in res[on][0].items() if g is not None and not np.isfinite(g).all()] for on in (True, False)}
@@ -207,3 +212,17 @@ def test_aggregated_step_identical_with_and_without_deferral(tag, batch, gpu_dev
         if g0[n] is not None:
             assert np.isfinite(g1[n]).all(), n
             assert np.array_equal(g0[n], g1[n]), f"{tag} {n}: deferral changed the gradient (stats {s1})"
+
+
+def test_pure_torch_aggregator_sees_settled_rows(gpu_device, monkeypatch, park_any_size):
+    """mtl_backward takes any callable as its aggregator, like torchjd's: one whose FIRST action is a torch op on J (`J.sum(0)`,
+    Sum's arithmetic) makes no library call that would launch a still-parked reduce, so autojac launches it once the pull-back
+    is done (ops.flush_deferred in _mtl_backward_finish).  The smallest aggregated step above (C2's layers at batch 64): the
+    same gradients bit for bit with and without deferral, and reduces were parked."""
+    res = {on: _aggregated_step("C2", 64, on, lambda: (lambda J: J.sum(0)), gpu_device, monkeypatch) for on in (True, False)}
+    (g1, s1), (g0, _) = res[True], res[False]
+    assert s1[0] >= 2, f"deferral statistics {s1}"
+    assert [n for n in g0 if g0[n] is None] == [n for n in g1 if g1[n] is None]
+    for n in g0:
+        if g0[n] is not None:
+            assert np.isfinite(g0[n]).all() and np.array_equal(g0[n], g1[n]), f"{n}: deferral changed the gradient (stats {s1})"

@@ -295,7 +295,7 @@ def test_fused_loss_arithmetic_equals_tensor_arithmetic(tag, gpu_device, monkeyp
             if tag == "vq_vae2_tiny":  # the lazily formed sums are ordinary tensors for any other reader
                 assert callable(dict.__getitem__(out, "commitment_loss")) and not isinstance(dict.__getitem__(out, "commitment_loss"), torch.Tensor)
                 c = out["commitment_loss"]
-                assert isinstance(c, torch.Tensor) and float(c.detach()) == float((out["_vq_terms"][0] + out["_vq_terms"][1]).detach())
+                assert isinstance(c, torch.Tensor) and float(c.detach()) == float((net._vq_terms[0] + net._vq_terms[1]).detach())
                 assert isinstance(dict(out.items())["embedding_loss"], torch.Tensor)
     BetaTCVAE.num_iter = 0
     (lf, gf, names), (lu, gu, _) = res["1"], res["0"]
