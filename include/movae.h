@@ -752,6 +752,14 @@ int movae_lpips_finalize(int layers, const double* const* partials, const int* h
 int movae_batch_u8(const uint8_t* store, const int* idx, int b, int h, int w, int c, const float* lut, int flip,
                    unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream);
 
+/* The device step of a STREAMED batch (data.StreamedBatchLoader: a set that stays in host memory).  stage: device uint8 [b][h][w][c],
+ * the batch's images already in batch order (gathered on the host, copied up).  ids: device int[b], the dataset index of every row.
+ * out[j][y][x][ch] = lut[ch][stage[j][y][x'][ch]], x' mirrored iff row ids[j] is flipped under (seed, epoch) by the rule above:
+ * movae_batch_u8 with the source row (j) and the flip key (ids[j]) separated, so stage = store[ids] gives movae_batch_u8's bits.
+ * The same kernel body, paths (w % 4 == 0 and a 4-byte-aligned stage: 4 pixels per thread), checks and refusals. */
+int movae_batch_u8_staged(const uint8_t* stage, const int* ids, int b, int h, int w, int c, const float* lut, int flip,
+                          unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream);
+
 /* ---- batches from a device-resident RAGGED uint8 image set (csrc/data.hip; the reference's RandomResizedCrop(BICUBIC) ->
  * RandomHorizontalFlip -> ToTensor -> Normalize on PIL images) ----
  * blob: device uint8, the images back to back in HWC order, each starting at ANY byte.  offsets: device int64[n], the byte offset of

@@ -179,6 +179,7 @@ SIGNATURES = {
     "movae_kid_subsets": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_double, _i, _p, _p], _i),
     "movae_knn_rows": ([_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p], _i),
     "movae_batch_u8": ([_p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
+    "movae_batch_u8_staged": ([_p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_batch_rrc_u8": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, C.c_ulonglong, C.c_ulonglong, _p, _p], _i),
     "movae_resample_coeffs": ([_p, _i, _i, _i, _p, _p, _p], _i),
     "movae_codes_batch": ([_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p], _i),

@@ -9,6 +9,9 @@
 //                group start at multiples of 4 * c bytes) and writes c 16-byte stores, consecutive threads consecutive 16 c bytes of
 //                out; with a flip it reads the mirrored group and emits its pixels in reverse.  Any other w, or an unaligned store,
 //                takes one thread per element.  No atomics, no workspace, no device globals.  Bytes: b h w c read + 4 b h w c written.
+//   batch_u8_staged  the same kernel body for a STREAMED set (data.py: StreamedBatchLoader): the batch's rows were gathered on the host
+//                and copied into a device staging buffer in batch order, so the source row of out[j] is stage[j] while the flip is
+//                still keyed by the dataset index ids[j].  The same (seed, epoch, index) gives the same pixels as batch_u8.
 //   batch_rrc_u8 the same for a RAGGED set (data.py: RaggedBatchLoader): images of their own sizes back to back in one blob, and per
 //                image a crop box that is resampled to s x s exactly as PIL's crop(box).resize((s, s), BICUBIC) does it, then mirrored
 //                and sent through the table.  One launch, a block per 32 x 32 output tile; described at the kernel below.
@@ -34,7 +37,8 @@ __device__ __forceinline__ bool row_flipped(const BatchU8Args& a, int i) {
     return (r[0] >> 31) != 0;
 }
 
-template <int C, bool FAST>
+// STAGED: the source row of out[j] is store[j] (a staging buffer in batch order) and idx[j] only keys the flip; otherwise store[idx[j]].
+template <int C, bool FAST, bool STAGED>
 __global__ __launch_bounds__(256) void batch_u8_k(BatchU8Args a) {
     __shared__ float slut[C * 256];
 #pragma unroll
@@ -51,7 +55,8 @@ __global__ __launch_bounds__(256) void batch_u8_k(BatchU8Args a) {
             const int i = a.idx[j];
             const bool fl = a.flip != 0 && row_flipped(a, i);
             const int sgx = fl ? gw - 1 - gx : gx;
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(a.store + (size_t)i * image_bytes + ((size_t)y * a.w + 4 * sgx) * C);
+            const size_t row = STAGED ? (size_t)j : (size_t)i;
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(a.store + row * image_bytes + ((size_t)y * a.w + 4 * sgx) * C);
             uint32_t wd[C];
 #pragma unroll
             for (int q = 0; q < C; ++q) wd[q] = src[q];
@@ -78,7 +83,8 @@ __global__ __launch_bounds__(256) void batch_u8_k(BatchU8Args a) {
             const int i = a.idx[j];
             const bool fl = a.flip != 0 && row_flipped(a, i);
             const int sx = fl ? a.w - 1 - x : x;
-            a.out[e] = slut[ch * 256 + a.store[(size_t)i * image_bytes + ((size_t)y * a.w + sx) * C + ch]];
+            const size_t row = STAGED ? (size_t)j : (size_t)i;
+            a.out[e] = slut[ch * 256 + a.store[row * image_bytes + ((size_t)y * a.w + sx) * C + ch]];
         }
     }
 }
@@ -289,12 +295,14 @@ int movae_resample_coeffs(const int* in_sizes, int n, int out_size, int kmax, in
     return MOVAE_OK;
 }
 
-int movae_batch_u8(const uint8_t* store, const int* idx, int b, int h, int w, int c, const float* lut, int flip,
-                   unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream) {
-    MOVAE_CHECK_ARG(store && idx && lut && out, "movae_batch_u8: null pointer");
-    MOVAE_CHECK_ARG(b > 0 && h > 0 && w > 0, "movae_batch_u8: b, h, w must be positive (got %d, %d, %d)", b, h, w);
-    MOVAE_CHECK_ARG(c == 1 || c == 3, "movae_batch_u8: 1 or 3 channels (got %d)", c);
-    MOVAE_CHECK_ARG(((uintptr_t)out & 15) == 0, "movae_batch_u8: out must be 16-byte aligned");
+// movae_batch_u8 and movae_batch_u8_staged: the same checks and the same launch, `name` in the messages
+template <bool STAGED>
+static int batch_u8_launch(const char* name, const uint8_t* store, const int* idx, int b, int h, int w, int c, const float* lut, int flip,
+                           unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream) {
+    MOVAE_CHECK_ARG(store && idx && lut && out, "%s: null pointer", name);
+    MOVAE_CHECK_ARG(b > 0 && h > 0 && w > 0, "%s: b, h, w must be positive (got %d, %d, %d)", name, b, h, w);
+    MOVAE_CHECK_ARG(c == 1 || c == 3, "%s: 1 or 3 channels (got %d)", name, c);
+    MOVAE_CHECK_ARG(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", name);
     const bool fast = w % 4 == 0 && ((uintptr_t)store & 3) == 0;
     BatchU8Args a;
     a.store = store, a.idx = idx, a.lut = lut, a.out = out;
@@ -305,12 +313,22 @@ int movae_batch_u8(const uint8_t* store, const int* idx, int b, int h, int w, in
     const dim3 grid((unsigned)(want < 2048 ? want : 2048));  // grid-stride past 2048 blocks
     hipStream_t st = (hipStream_t)stream;
     if (c == 3) {
-        if (fast) batch_u8_k<3, true><<<grid, 256, 0, st>>>(a);
-        else batch_u8_k<3, false><<<grid, 256, 0, st>>>(a);
+        if (fast) batch_u8_k<3, true, STAGED><<<grid, 256, 0, st>>>(a);
+        else batch_u8_k<3, false, STAGED><<<grid, 256, 0, st>>>(a);
     } else {
-        if (fast) batch_u8_k<1, true><<<grid, 256, 0, st>>>(a);
-        else batch_u8_k<1, false><<<grid, 256, 0, st>>>(a);
+        if (fast) batch_u8_k<1, true, STAGED><<<grid, 256, 0, st>>>(a);
+        else batch_u8_k<1, false, STAGED><<<grid, 256, 0, st>>>(a);
     }
-    MOVAE_CHECK_LAUNCH("batch_u8");
+    MOVAE_CHECK_LAUNCH(name);
     return MOVAE_OK;
+}
+
+int movae_batch_u8(const uint8_t* store, const int* idx, int b, int h, int w, int c, const float* lut, int flip,
+                   unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream) {
+    return batch_u8_launch<false>("movae_batch_u8", store, idx, b, h, w, c, lut, flip, seed, epoch, out, stream);
+}
+
+int movae_batch_u8_staged(const uint8_t* stage, const int* ids, int b, int h, int w, int c, const float* lut, int flip,
+                          unsigned long long seed, unsigned long long epoch, float* out, movae_stream_t stream) {
+    return batch_u8_launch<true>("movae_batch_u8_staged", stage, ids, b, h, w, c, lut, flip, seed, epoch, out, stream);
 }

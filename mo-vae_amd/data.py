@@ -10,10 +10,15 @@ readers take the files a user already has (the CIFAR pickles torchvision unpacks
 A set whose pipeline starts with RandomResizedCrop (oxford-flower-102, utils/utils.py:367-397) is kept RAGGED instead: the images at
 their own sizes back to back in one uint8 blob (RaggedImages), the epoch's crop boxes drawn on the host from further Philox streams
 of the same counter (rrc_boxes), and the crop, PIL's 8-bit bicubic resample restated bit for bit (resize_u8), the flip and the table
-done per batch by one launch (RaggedBatchLoader -> ops.batch_rrc_u8 -> movae_batch_rrc_u8)."""
+done per batch by one launch (RaggedBatchLoader -> ops.batch_rrc_u8 -> movae_batch_rrc_u8).
+
+A set that does not fit the device (imagenet) STREAMS from host memory instead: its shards stay np.load maps (ShardedImages), pool
+threads gather each batch's rows into page-locked slots, and the device step is one copy and one launch (StreamedBatchLoader ->
+ops.batch_u8_staged -> movae_batch_u8_staged), the same pixels for the same (seed, epoch, dataset index)."""
 import math
 import os
 import pickle
+import re
 import weakref
 
 import numpy as np
@@ -62,25 +67,53 @@ def value_table(channels, normalize):
     return t.contiguous()
 
 
-class ResidentImages(torch.utils.data.Dataset):
-    """A uint8 image set [N][H][W][C] (C in {1, 3}; a numpy array or an np.load(mmap_mode="r") map) with the reference's transforms as
-    a table.  Item i is (CHW float tensor, 0): the host form of what DeviceBatchLoader assembles on the device, bit for bit, for the
-    same (index, epoch) -- flipped only when `train`."""
+def _is_u8_images(u8):
+    return isinstance(u8, np.ndarray) and u8.dtype == np.uint8 and u8.ndim == 4 and u8.shape[3] in (1, 3) and 0 not in u8.shape
 
-    def __init__(self, u8, normalize, train, seed=0):
-        if not isinstance(u8, np.ndarray) or u8.dtype != np.uint8 or u8.ndim != 4 or u8.shape[3] not in (1, 3) or 0 in u8.shape:
-            raise ValueError(f"ResidentImages: a non-empty uint8 array [N][H][W][C] with C in (1, 3), got "
-                             f"{getattr(u8, 'dtype', type(u8))} {getattr(u8, 'shape', None)}")
-        self.u8, self.normalize, self.train, self.seed, self.epoch = u8, bool(normalize), bool(train), int(seed), 0
-        self.table = value_table(u8.shape[3], normalize)
-        self._chan = torch.arange(u8.shape[3]).reshape(-1, 1, 1)
+
+class _TableImages(torch.utils.data.Dataset):
+    """What ResidentImages and ShardedImages share: a uint8 set [N][H][W][C] held as `shards` (arrays [n_k][H][W][C], in order) with
+    the reference's transforms as a table and the Philox flip rule.  Item i of the set is row `i - starts[k]` of shard k (locate)."""
+
+    def _setup(self, normalize, train, seed):
+        channels = self.shards[0].shape[3]
+        self.normalize, self.train, self.seed, self.epoch = bool(normalize), bool(train), int(seed), 0
+        self.table = value_table(channels, normalize)
+        self._chan = torch.arange(channels).reshape(-1, 1, 1)
         self._flips = (None, None)  # ((seed, epoch), bool[N])
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
 
-    def __len__(self):
-        return self.u8.shape[0]
+    @property
+    def image_shape(self):
+        """(H, W, C) of every image."""
+        return tuple(self.shards[0].shape[1:])
+
+    def locate(self, i):
+        """-> (shard number, row in that shard) of image i."""
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        k = int(np.searchsorted(self.starts, i, side="right")) - 1
+        return k, i - int(self.starts[k])
+
+    def gather(self, indices, out):
+        """Fills the numpy uint8 array out[j] ([len(indices)][H][W][C]) with image indices[j] as it is stored (no flip, no table), in the
+        order given; any order, repeats allowed.  IndexError for an index outside the set.  Host memory only: this is the one function
+        StreamedBatchLoader's pool threads call."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size and not 0 <= idx.min() <= idx.max() < len(self):
+            raise IndexError(f"gather: index outside the set of {len(self)} images")
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or tuple(out.shape) != (idx.size, *self.image_shape):
+            raise ValueError(f"gather: out is a numpy uint8 array {(idx.size, *self.image_shape)}, got "
+                             f"{getattr(out, 'dtype', type(out))} {getattr(out, 'shape', None)}")
+        starts, shards = self.starts, self.shards
+        ks = np.searchsorted(starts, idx, side="right") - 1
+        rows = idx - starts[ks]
+        for j in range(idx.size):  # one copy per image, straight from the array or the map into `out`: no intermediate batch
+            out[j] = shards[ks[j]][rows[j]]
+        return out
 
     def flipped(self, i):
         if not self.train:
@@ -91,13 +124,65 @@ class ResidentImages(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         i = int(i)
-        if not 0 <= i < len(self):
-            raise IndexError(i)
-        img = np.array(self.u8[i])  # HWC (a copy: a read-only map stays untouched)
+        k, row = self.locate(i)  # (IndexError outside the set)
+        img = np.array(self.shards[k][row])  # HWC (a copy: a read-only map stays untouched)
         if self.flipped(i):
             img = img[:, ::-1]
         codes = torch.from_numpy(np.ascontiguousarray(img)).permute(2, 0, 1).long()
         return self.table[self._chan, codes], 0
+
+
+class ResidentImages(_TableImages):
+    """A uint8 image set [N][H][W][C] (C in {1, 3}; a numpy array or an np.load(mmap_mode="r") map) with the reference's transforms as
+    a table.  Item i is (CHW float tensor, 0): the host form of what DeviceBatchLoader assembles on the device, bit for bit, for the
+    same (index, epoch) -- flipped only when `train`."""
+
+    def __init__(self, u8, normalize, train, seed=0):
+        if not _is_u8_images(u8):
+            raise ValueError(f"ResidentImages: a non-empty uint8 array [N][H][W][C] with C in (1, 3), got "
+                             f"{getattr(u8, 'dtype', type(u8))} {getattr(u8, 'shape', None)}")
+        self.u8 = u8
+        self._setup(normalize, train, seed)
+
+    # one shard: the array itself (read from self.u8 at every use, so the set is whatever self.u8 is)
+    @property
+    def shards(self):
+        return (self.u8,)
+
+    @property
+    def starts(self):
+        return np.array([0, self.u8.shape[0]], dtype=np.int64)
+
+    def locate(self, i):
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return 0, i
+
+    def __len__(self):
+        return self.u8.shape[0]
+
+
+class ShardedImages(_TableImages):
+    """A uint8 image set split over `shards`, arrays (or np.load(mmap_mode="r") maps) [n_k][H][W][C] of one image shape: ResidentImages'
+    item contract and attributes over their concatenation, which is never made.  The set for StreamedBatchLoader, for a set too large
+    for the device (imagenet) or for host memory (the maps are read through the page cache)."""
+
+    def __init__(self, shards, normalize, train, seed=0):
+        shards = list(shards)
+        if not shards:
+            raise ValueError("ShardedImages: no shards")
+        for k, s in enumerate(shards):
+            if not _is_u8_images(s) or s.shape[1:] != shards[0].shape[1:]:
+                raise ValueError(f"ShardedImages: shard {k} is not a non-empty uint8 array [n][H][W][C] with C in (1, 3) of shard 0's image "
+                                 f"shape {getattr(shards[0], 'shape', (None,))[1:]}: got {getattr(s, 'dtype', type(s))} "
+                                 f"{getattr(s, 'shape', None)}")
+        self.shards = shards
+        self.starts = np.concatenate([[0], np.cumsum([s.shape[0] for s in shards])]).astype(np.int64)
+        self._setup(normalize, train, seed)
+
+    def __len__(self):
+        return int(self.starts[-1])
 
 
 def shard_indices(n, shuffle, seed, epoch, rank=0, world_size=1):
@@ -132,7 +217,8 @@ class ResidentLoader:
 
     # what a subclass gives --
     # noun: what a row is, for the messages
-    # _upload(): make the set resident (called once, on first use); refuses a set that does not fit (refuse_if_too_big)
+    # _upload(): make the set resident (called once, on first use); refuses a set that does not fit (refuse_if_too_big).  The streamed
+    #            loader, whose set stays on the host, allocates its ring of host slots and its device staging buffer here instead
     # _batch(rows): the batch of the device int32 row numbers `rows` -- what the iteration yields
     # _checked(idx): the host index list as a CPU int32 tensor, refused unless every entry is a row of the set
     noun = "rows"
@@ -199,7 +285,7 @@ class DeviceBatchLoader(ResidentLoader):
         store = _STORES.get(key)
         if store is None:
             refuse_if_too_big(int(u8.nbytes) + self.dataset.table.numel() * 4, self.device, "the image set needs",
-                              "keep it on the host with --data_loader host")
+                              "keep it on the host with --data_loader host, or stream it with --data_loader stream")
             store = torch.empty(u8.shape, dtype=torch.uint8, device=self.device)
             rows = max(1, (256 << 20) // max(1, int(u8[0].nbytes)))  # staged through <= 256 MB of host memory (the array may be a map)
             for s in range(0, u8.shape[0], rows):
@@ -218,6 +304,102 @@ class DeviceBatchLoader(ResidentLoader):
         ds = self.dataset
         out = ops.batch_u8(self._store, rows, self._lut, flip=ds.train, seed=ds.seed, epoch=self.epoch)
         return out.permute(0, 3, 1, 2), self._zeros[:rows.numel()]
+
+
+class StreamedBatchLoader(ResidentLoader):
+    """ResidentLoader's index rule over a ResidentImages or ShardedImages that STAYS IN HOST MEMORY: yields
+    what DeviceBatchLoader yields, bit for bit, but the set is never uploaded.  Batch k of the epoch is gathered by a pool thread
+    (ds.gather, numpy only) into slot k % depth of a ring of page-locked host buffers; next(), in the main thread and on the current
+    stream, waits for it, copies the slot into the ONE device staging buffer, records an event and launches ops.batch_u8_staged with
+    the batch's dataset indices.  A slot is handed to a worker again only after its copy event has been synchronised.  A pool thread
+    makes no HIP and no torch-device call, which is what keeps a hipGraph capture in the main thread legal while the pool runs.
+
+    num_workers sizes the pool (1 .. 8 threads); `timeout` (seconds) bounds the wait for one batch.  `streamed` counts the batches
+    handed out."""
+
+    noun = "images"
+    depth = 3
+
+    def __init__(self, ds, batch_size, device, shuffle, rank=0, world_size=1, seed=0, num_workers=1, timeout=600.0):
+        if not isinstance(ds, (ResidentImages, ShardedImages)):
+            raise TypeError(f"StreamedBatchLoader needs a ResidentImages or a ShardedImages, got {type(ds).__name__}")
+        super().__init__(ds, batch_size, device, shuffle, rank, world_size, seed)
+        self.workers, self.timeout, self.streamed = max(1, min(int(num_workers), 8)), float(timeout), 0
+        self._slots = self._slots_np = self._stage = self._lut = self._zeros = self._host_rows = None
+        self._active = None  # weak reference to the generator of the epoch under way
+
+    def _upload(self):  # (nothing of the set goes up: the ring, the staging buffer, the table)
+        shape = (self.batch_size, *self.dataset.image_shape)
+        self._slots = torch.empty((self.depth, *shape), dtype=torch.uint8, pin_memory=True)
+        self._slots_np = self._slots.numpy()
+        self._stage = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        self._lut = self.dataset.table.to(self.device)
+        self._zeros = torch.zeros(self.batch_size, dtype=torch.long, device=self.device)
+
+    def _checked(self, idx):
+        if idx and not 0 <= min(idx) <= max(idx) < len(self.dataset):
+            raise RuntimeError("StreamedBatchLoader: index list outside the set")
+        rows = torch.tensor(idx, dtype=torch.int32)
+        self._host_rows = rows.numpy()  # the same list, for the gathers (replaced with the device list, once per epoch)
+        return rows
+
+    def _convert(self, stage, ids):
+        ds = self.dataset
+        out = ops.batch_u8_staged(stage, ids, self._lut, flip=ds.train, seed=ds.seed, epoch=self.epoch)
+        return out.permute(0, 3, 1, 2), self._zeros[:ids.numel()]
+
+    def _batch(self, rows):
+        """The batch of ANY device row list, outside an epoch's iteration (visual.first_items): gathered here, in the caller's
+        thread, through a pageable buffer of its own, so the ring of an epoch under way is not touched."""
+        host = np.empty((rows.numel(), *self.dataset.image_shape), dtype=np.uint8)
+        self.dataset.gather(rows.cpu().numpy(), host)
+        return self._convert(torch.from_numpy(host).to(self.device), rows.contiguous())
+
+    def __iter__(self):
+        prev = self._active() if self._active is not None else None
+        if prev is not None:
+            prev.close()  # an epoch abandoned half-way gives up its pool and the ring before the next one starts
+        gen = self._epoch_batches()
+        self._active = weakref.ref(gen)
+        return gen
+
+    def _epoch_batches(self):
+        from concurrent.futures import ThreadPoolExecutor
+        from concurrent.futures import TimeoutError as FutureTimeout
+
+        idx = self._device_indices()
+        host, bs, depth = self._host_rows, self.batch_size, self.depth
+        starts = range(0, host.shape[0], bs)
+        pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="movae-stream")
+        futures, copied, wait = {}, [None] * depth, True
+
+        def submit(k):
+            rows = host[starts[k]:starts[k] + bs]
+            futures[k] = pool.submit(self.dataset.gather, rows, self._slots_np[k % depth][:rows.shape[0]])
+
+        try:
+            for k in range(min(depth, len(starts))):
+                submit(k)
+            for k, s in enumerate(starts):
+                if k >= 1 and k - 1 + depth < len(starts):  # the slot of batch k - 1 is free once its copy has left the host
+                    copied[(k - 1) % depth].synchronize()
+                    submit(k - 1 + depth)
+                try:
+                    futures.pop(k).result(self.timeout)  # (a worker's exception is raised here)
+                except FutureTimeout as e:
+                    wait = False  # the worker may never come back: do not wait for it below
+                    raise RuntimeError(f"StreamedBatchLoader: batch {k} of epoch {self.epoch} was not gathered within "
+                                       f"{self.timeout:g} s ({self.workers} workers)") from e
+                ids = idx[s:s + bs]
+                stage = self._stage[:ids.numel()]  # (the ragged last batch: the first rows of slot and stage)
+                stage.copy_(self._slots[k % depth][:ids.numel()], non_blocking=True)
+                copied[k % depth] = torch.cuda.Event()
+                copied[k % depth].record()
+                batch = self._convert(stage, ids)
+                self.streamed += 1
+                yield batch
+        finally:  # the epoch's end, an abandoned epoch (the generator is closed or collected), an exception in the consumer
+            pool.shutdown(wait=wait, cancel_futures=True)
 
 
 # ---- ragged sets: RandomResizedCrop (DESIGN.md section 3.22) -----------------------------------------------------------------------
@@ -460,11 +642,14 @@ class RaggedBatchLoader(ResidentLoader):
 
 
 # ---- readers -----------------------------------------------------------------------------------------------------------------------
-#: name -> image side of the .npy sets: <data_dir>/<name>_train_u8.npy and <name>_test_u8.npy, uint8 [N][S][S][3]
-NPY_SETS = {"celeba": 64, "celeba-128": 128, "celeba-hq": 256, "afhq": 256}
+#: name -> image side of the .npy sets: <data_dir>/<name>_train_u8.npy and <name>_test_u8.npy, uint8 [N][S][S][3]; either part may
+#: instead be split over shards <name>_<part>_u8_00000.npy, _00001.npy, ... of that form (a ShardedImages, which streams)
+NPY_SETS = {"celeba": 64, "celeba-128": 128, "celeba-hq": 256, "afhq": 256, "imagenet": 256}
 ALIASES = {"animal-face": "afhq"}
-REFUSED = {
-    "imagenet": "1.28 M images of 256 x 256 are 252 GB as uint8: they do not fit one device and would have to stream from host memory",
+#: sets whose missing train files are a NotImplementedError with this reason (tests/test_data_host.py pins type and the words 252 GB,
+#: as _ragged's does for RandomResizedCrop): without its prepared files such a set is still "not available" to an older caller
+UNPREPARED = {
+    "imagenet": "1.28 M images of 256 x 256 are 252 GB as uint8: they do not fit one device and stream from host memory",
 }
 #: name -> image side of the ragged sets: <data_dir>/<name>_train_ragged_u8.npy + <name>_train_ragged_index.npy (the images at their
 #: own sizes, cropped and resampled per item) and <name>_test_u8.npy, uint8 [N][S][S][3]; written by tools/prepare_images.py --ragged
@@ -504,6 +689,44 @@ def _npy(path, size):
     return a
 
 
+def _split_files(data_dir, key, part):
+    """-> (path of the one-file form, paths of the shards in order) of one split as they lie in data_dir; either may be absent.
+    ValueError for both forms at once and for a gap in the shard numbers."""
+    whole = os.path.join(data_dir, f"{key}_{part}_u8.npy")
+    pattern = re.compile(re.escape(f"{key}_{part}_u8_") + r"(\d{5})\.npy")
+    found = sorted(f for f in (os.listdir(data_dir) if os.path.isdir(data_dir) else ()) if pattern.fullmatch(f))
+    if found and os.path.isfile(whole):
+        raise ValueError(f"{whole} and the shards {found[0]} .. lie side by side: keep one form of the {part} split")
+    for k, f in enumerate(found):
+        want = f"{key}_{part}_u8_{k:05d}.npy"
+        if f != want:
+            raise ValueError(f"{os.path.join(data_dir, want)} is missing: shard numbers are consecutive from 00000, but {f} is there")
+    return whole, [os.path.join(data_dir, f) for f in found]
+
+
+def _split(data_dir, key, part, size):
+    """One split of an .npy set: its array (the one-file form) or the list of its shards' arrays, all maps."""
+    whole, shards = _split_files(data_dir, key, part)
+    return [_npy(p, size) for p in shards] if shards else _npy(whole, size)
+
+
+def _head(split, n):
+    """The first n images of a split (an array, or a list of shards: across a shard boundary if need be)."""
+    if not isinstance(split, list):
+        return split[:n]
+    kept = []
+    for s in split:
+        if n <= 0:
+            break
+        kept.append(s[:n])
+        n -= kept[-1].shape[0]
+    return kept
+
+
+def _images(split, normalize, train):
+    return (ShardedImages if isinstance(split, list) else ResidentImages)(split, normalize, train=train)
+
+
 def _ragged(name, key, data_dir, normalize, max_items):
     size = RAGGED_SETS[key]
     blob_path, index_path = (os.path.join(data_dir, f"{key}_train_ragged_{part}.npy") for part in ("u8", "index"))
@@ -530,13 +753,20 @@ def _ragged(name, key, data_dir, normalize, max_items):
 
 
 def get_real_dataset(name, data_dir="./data", normalize=False, max_items=None):
-    """-> (train set, test ResidentImages, image side) for a real dataset name of the reference (case-insensitive), or None for a name
-    this module does not know.  The train set is a ResidentImages, or a RaggedImages for a set whose pipeline is RandomResizedCrop.
+    """-> (train set, test set, image side) for a real dataset name of the reference (case-insensitive), or None for a name this
+    module does not know.  A set is a ResidentImages; a ShardedImages where the split lies on disk as shards; the train set a
+    RaggedImages for a set whose pipeline is RandomResizedCrop.
     `max_items` keeps the first max_items train and the first max(1, max_items // 10) test images."""
     key = name.lower()
     key = ALIASES.get(key, key)
-    if key in REFUSED:
-        raise NotImplementedError(f"dataset {name!r}: {REFUSED[key]}")
+    if key in UNPREPARED:
+        whole, shards = _split_files(data_dir, key, "train")
+        if not shards and not os.path.isfile(whole):
+            first = os.path.join(data_dir, f"{key}_train_u8_00000.npy")
+            raise NotImplementedError(
+                f"dataset {name!r}: {UNPREPARED[key]}.  Its train images are read from {first}, _00001.npy, ... (or from {whole}), "
+                f"written by tools/prepare_images.py --shard_images from the images on disk; {first} is missing, and nothing is "
+                f"downloaded")
     if key in RAGGED_SETS:
         return _ragged(name, key, data_dir, normalize, max_items)
     if key == "cifar10":
@@ -549,11 +779,11 @@ def get_real_dataset(name, data_dir="./data", normalize=False, max_items=None):
         size = 32
     elif key in NPY_SETS:
         size = NPY_SETS[key]
-        train = _npy(os.path.join(data_dir, f"{key}_train_u8.npy"), size)
+        train = _split(data_dir, key, "train", size)
         # AFHQ has one split in the reference (utils/utils.py:420-422): the train images serve as the test set too
-        test = train if key == "afhq" else _npy(os.path.join(data_dir, f"{key}_test_u8.npy"), size)
+        test = train if key == "afhq" else _split(data_dir, key, "test", size)
     else:
         return None
     if max_items:
-        train, test = train[:max_items], test[:max(1, max_items // 10)]
-    return ResidentImages(train, normalize, train=True), ResidentImages(test, normalize, train=False), size
+        train, test = _head(train, max_items), _head(test, max(1, max_items // 10))
+    return _images(train, normalize, True), _images(test, normalize, False), size

@@ -2503,6 +2503,24 @@ def batch_u8(store, idx, lut, flip, seed, epoch):
     return out
 
 
+def batch_u8_staged(stage, ids, lut, flip, seed, epoch):
+    """The device step of a streamed batch (csrc/data.hip; data.StreamedBatchLoader): stage uint8 [B][H][W][C], the batch's images in
+    batch order (a view into a larger staging buffer is fine: only its first byte need not be aligned), ids int32 [B] their dataset
+    indices, lut float32 [C][256] -> a fresh fp32 NHWC [B][H][W][C] with out[j] = lut[ch][stage[j]], row j mirrored along W where the
+    Philox bit of (seed, epoch, ids[j]) says so and `flip` is set: batch_u8's bits for stage = store[ids].  One launch."""
+    L.require_gpu(stage)
+    assert stage.dtype == torch.uint8 and stage.dim() == 4 and stage.is_contiguous(), "batch_u8_staged: stage is contiguous uint8 [B][H][W][C]"
+    b, h, w, c = stage.shape
+    assert ids.dtype == torch.int32 and tuple(ids.shape) == (b,) and ids.is_contiguous() and ids.device == stage.device, \
+        f"batch_u8_staged: ids is int32 [{b}]"
+    assert lut.dtype == torch.float32 and tuple(lut.shape) == (c, 256) and lut.is_contiguous() and lut.device == stage.device, \
+        f"batch_u8_staged: lut is float32 [{c}][256]"
+    out = torch.empty((b, h, w, c), dtype=torch.float32, device=stage.device)
+    _call("movae_batch_u8_staged", stage.data_ptr(), ids.data_ptr(), b, h, w, c, lut.data_ptr(), int(bool(flip)), int(seed), int(epoch),
+          out.data_ptr(), _st(stage))
+    return out
+
+
 def batch_rrc_u8(blob, offsets, dims, boxes, idx, size, channels, kmax, lut, flip, seed, epoch):
     """One RandomResizedCrop batch from a device-resident ragged image set (csrc/data.hip; data.RaggedBatchLoader): blob uint8 (the
     images back to back, HWC), offsets int64 [N] (bytes), dims int32 [N][2] = (h, w), boxes int32 [N][4] = (top, left, bh, bw), idx

@@ -24,7 +24,7 @@ from . import autojac
 from . import capture
 from .aggregation import COMFORT, MGDA
 from .data import ALIASES, NPY_SETS, RAGGED_SETS, DeviceBatchLoader, RaggedBatchLoader, RaggedImages, ResidentImages, ResidentLoader, \
-    get_real_dataset
+    ShardedImages, StreamedBatchLoader, get_real_dataset
 from .metrics import ReconMetricAccumulator, build_hv_indicator
 from .models import get_network
 from .optim import FusedAdam, FusedAdamW, clip_grad_norm_
@@ -586,8 +586,9 @@ class SyntheticImages(torch.utils.data.Dataset):
 def get_dataset(name, data_dir="./data", normalize=False, max_items=None):
     """utils/utils.py:144-426 -> (train set, test set, image side).  The reference's names (case-insensitive) are read from files
     already under `data_dir` as uint8 sets (data.get_real_dataset: nothing is downloaded; oxford-flower-102 is a ragged set, its images
-    at their own sizes for the per-item RandomResizedCrop, written by tools/prepare_images.py --ragged; imagenet is refused, with the
-    reason); synthetic_* names give seeded shape-compatible data."""
+    at their own sizes for the per-item RandomResizedCrop, written by tools/prepare_images.py --ragged; imagenet is a set of shards that
+    stay in host memory, written by tools/prepare_images.py --shard_images, and without them refused, with the reason); synthetic_*
+    names give seeded shape-compatible data."""
     key = name.lower()
     if key in SYNTHETIC:
         size, n = SYNTHETIC[key]
@@ -605,26 +606,55 @@ def make_loader(ds, batch_size, device, args, shuffle, sampler=None, dp=None):
     """The loader of one stage.  `--data_loader auto` (default): a ResidentImages set gets the device loader (data.DeviceBatchLoader:
     the set in HBM, one launch per batch), a RaggedImages set its own (data.RaggedBatchLoader: the same, the launch also crops and
     resamples), anything else the DataLoader this build always used; `host` forces the DataLoader, `device`
-    insists on the device loader.  `dp` (with the device loader) / `sampler` (with the DataLoader) shard a training set over the ranks."""
-    if uses_device_loader(ds, args):
+    insists on the device loader.  A ShardedImages set (imagenet: shards that stay in host memory) streams under `auto`, and `stream`
+    asks for that for a ResidentImages too (data.StreamedBatchLoader: --num_workers threads gather the rows, one copy and one launch
+    per batch).  `dp` (with these loaders) / `sampler` (with the DataLoader) shard a training set over the ranks."""
+    kind = loader_kind(ds, args)
+    if kind != "host":
         rank, world = (dp.rank, dp.world_size) if dp is not None else (0, 1)
-        cls = RaggedBatchLoader if isinstance(ds, RaggedImages) else DeviceBatchLoader
-        return cls(ds, batch_size, device, shuffle, rank=rank, world_size=world, seed=args.seed or 0)
+        kw = dict(rank=rank, world_size=world, seed=args.seed or 0)
+        if kind == "stream":
+            return StreamedBatchLoader(ds, batch_size, device, shuffle, num_workers=getattr(args, "num_workers", 1), **kw)
+        return (RaggedBatchLoader if kind == "ragged" else DeviceBatchLoader)(ds, batch_size, device, shuffle, **kw)
     # pinning in the main thread (num_workers == 0) allocates and frees page-locked memory per batch: ~20 ms per batch on ROCm.
     # A ResidentImages or RaggedImages set gets fresh workers per epoch: a worker holds a COPY of the set, taken when it starts, and
     # persistent workers would keep the epoch of that moment -- every later epoch would repeat its flips (and crops)
-    persistent = args.num_workers > 0 and not isinstance(ds, (ResidentImages, RaggedImages))
+    persistent = args.num_workers > 0 and not isinstance(ds, U8_SETS)
     kw = dict(num_workers=args.num_workers, pin_memory=args.num_workers > 0, drop_last=False, persistent_workers=persistent)
     return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=shuffle and sampler is None, sampler=sampler, **kw)
 
 
-def uses_device_loader(ds, args):
-    """Whether make_loader gives `ds` the device loader under `--data_loader` (ValueError: `device` asked for a set with no uint8 form)."""
+#: the sets held as uint8 images: their flips (and crops) follow --seed and the epoch, on the device and on the host alike
+U8_SETS = (ResidentImages, ShardedImages, RaggedImages)
+
+
+def loader_kind(ds, args):
+    """Which loader make_loader gives `ds` under `--data_loader`: "device" (DeviceBatchLoader), "ragged" (RaggedBatchLoader), "stream"
+    (StreamedBatchLoader) or "host" (the DataLoader).  ValueError where the mode asks for what the set cannot give."""
     mode = getattr(args, "data_loader", "auto")
-    resident = isinstance(ds, (ResidentImages, RaggedImages))
-    if mode == "device" and not resident:
-        raise ValueError(f"--data_loader device needs a dataset held as uint8 images; {type(ds).__name__} is generated on the host")
-    return resident and mode in ("auto", "device")
+    if mode == "host":
+        return "host"
+    if not isinstance(ds, U8_SETS):
+        if mode in ("device", "stream"):
+            raise ValueError(f"--data_loader {mode} needs a dataset held as uint8 images; {type(ds).__name__} is generated on the host")
+        return "host"
+    if isinstance(ds, RaggedImages):
+        if mode == "stream":
+            raise ValueError("--data_loader stream copies rows of one image shape; a RaggedImages set is cropped and resampled from its "
+                             "blob on the device: use --data_loader device or host")
+        return "ragged"
+    if isinstance(ds, ShardedImages):
+        if mode == "device":
+            raise ValueError("--data_loader device keeps one uint8 array on the device; a ShardedImages set stays in host memory: use "
+                             "--data_loader stream or host")
+        return "stream"
+    return "stream" if mode == "stream" else "device"
+
+
+def uses_device_loader(ds, args):
+    """Whether make_loader gives `ds` a loader that assembles its batches on the device and shards by dp itself (the device, the ragged
+    or the streamed one) under `--data_loader`; ValueError as loader_kind."""
+    return loader_kind(ds, args) != "host"
 
 
 # ---- CLI -----------------------------------------------------------------------------------------
@@ -740,10 +770,12 @@ def build_parser():
                    help="fp32 (default): the reference's arithmetic, the parity path.  bf16 (opt-in): bf16 operands / fp32 "
                         "accumulation in the 128x128 implicit-GEMM convolution kernels (the MFMA-bound layers of the 64x64+ "
                         "configurations); master weights, BatchNorm, losses, aggregation and optimizer stay fp32")
-    p.add_argument("--data_loader", choices=["auto", "device", "host"], default="auto",
+    p.add_argument("--data_loader", choices=["auto", "device", "stream", "host"], default="auto",
                    help="auto (default): a real image set is kept on the device as uint8 and each batch is assembled there by one "
-                        "kernel (gather, flip, ToTensor / Normalize); synthetic sets keep the host DataLoader.  host: the DataLoader "
-                        "for every set (a set too large for the device).  device: refuse a set that has no uint8 form")
+                        "kernel (gather, flip, ToTensor / Normalize); a set that lies on disk as shards (imagenet) streams; synthetic "
+                        "sets keep the host DataLoader.  host: the DataLoader for every set.  device: refuse a set that has no uint8 "
+                        "form or lies in shards.  stream: the uint8 set stays in host memory, --num_workers threads (1 .. 8) gather each "
+                        "batch's rows and the device flips and converts them (a set too large for the device)")
     p.add_argument("--gen_metrics", choices=["off", "on"], default="off",
                    help="on: after the final reconstruction pass, draw --max_gen_metrics_samples images from the model (VQ "
                         "architectures through the trained prior) and report gFID, Inception Score and KID against as many test "
@@ -826,7 +858,7 @@ def main(args):
         sampler = torch.utils.data.distributed.DistributedSampler(train_ds, num_replicas=dp.world_size, rank=dp.rank,
                                                                   shuffle=True, seed=args.seed or 0)
     for ds in (train_ds, test_ds):
-        if isinstance(ds, (ResidentImages, RaggedImages)):
+        if isinstance(ds, U8_SETS):
             ds.seed = args.seed or 0  # the flips (and crops) follow --seed, on the device and on the host alike
     train_loader = make_loader(train_ds, per_rank_bs, device, args, shuffle=True, sampler=sampler, dp=dp)
     test_loader = make_loader(test_ds, per_rank_bs, device, args, shuffle=False)
@@ -883,7 +915,7 @@ def main(args):
             sampler.set_epoch(epoch)
         if isinstance(train_loader, ResidentLoader):
             train_loader.set_epoch(epoch)  # the epoch's shuffle, flips and crops
-        elif isinstance(train_ds, (ResidentImages, RaggedImages)):
+        elif isinstance(train_ds, U8_SETS):
             train_ds.set_epoch(epoch)  # the host path's flips and crops (its order is the DataLoader's / the sampler's)
         if isinstance(aggregator, COMFORT):  # main.py:1290-1291
             aggregator.set_epoch(epoch, args.epochs)
@@ -958,6 +990,8 @@ def main(args):
         if log is not None:
             log({f"final/{k}": gen[k] for k in order}, step)
         LAST_FINAL["gen"] = gen
+    if rank0 and isinstance(train_loader, StreamedBatchLoader):
+        print(f"[movae] streamed {train_loader.streamed} batches of the training set from host memory ({train_loader.workers} gather threads)", flush=True)
     if dp is not None:
         dp.shutdown()
     LAST_RUN.clear()
