@@ -551,6 +551,18 @@ int movae_bn_stats(const float* y, int rows, int c, float* stats, size_t stats_c
 /* out = leaky_relu(scale[c] * y + shift[c], slope): materialises a fused BatchNorm output */
 int movae_scale_shift_act(const float* y, const float* scale, const float* shift, float* out, size_t rows, int c, float slope,
                           movae_stream_t stream);
+/* name of the host dispatch branch the most recent successful BatchNorm call on this process took (the sibling of
+ * movae_bench_last_kernel for this family; "" before the first one; a refused call leaves it as it was):
+ *   movae_bn_act_fwd             fwd_small | fwd_stats4+apply_vec | fwd_stats4+apply_scalar | fwd_stats+apply_scalar |
+ *                                fwd_eval+apply_vec | fwd_eval+apply_scalar
+ *   movae_bn_act_bwd[_grouped]   bwd_small | bwd_vec4 | bwd_scalar
+ *   movae_bn_finalize            finalize | fold+finalize
+ *   movae_bn_bwd_finalize        bwd_finalize | bwd_fold+finalize
+ *   movae_bn_bwd_apply           bwd_apply
+ *   movae_bn_bwd_finalize_apply  bwd_fused | bwd_finalize+apply | bwd_fold+finalize+apply
+ *   movae_scale_shift_act        scale_shift_act
+ * Tests assert it so that a moved dispatch threshold fails them instead of changing what they cover. */
+const char* movae_bn_last_path(void);
 
 /* ---- PixelCNN prior over the VQ code grids (models/pixelcnn_prior.py, trained by main.py:890-1085) -------
  * The prior's convolutions are movae_conv2d_* calls; MaskedConv2d (pixelcnn_prior.py:25-54) multiplies its weight by the

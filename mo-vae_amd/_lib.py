@@ -188,6 +188,7 @@ SIGNATURES = {
     "movae_bench_main_kernel_only": ([_i], _i),
     "movae_bench_last_kernel": ([], C.c_char_p),
     "movae_bench_last_reduce": ([], C.c_char_p),
+    "movae_bn_last_path": ([], C.c_char_p),
     "movae_reduce_defer": ([_i], _i),
     "movae_reduce_flush": ([], _i),
     "movae_reduce_defer_stats": ([_p, _i], _i),

@@ -3,6 +3,7 @@
 // reduction), the apply pass reads y and writes out once.  Backward mirrors it.
 #include "common.h"
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -742,13 +743,22 @@ inline bool al16(const void* a, const void* b = nullptr, const void* c = nullptr
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
+// movae_bn_last_path(): the host dispatch branch the most recent BatchNorm entry point took (per process; a pointer store, nothing
+// about the launches depends on it)
+const char* g_bn_path = "";
+
 }  // namespace
 
 extern "C" {
 
+const char* movae_bn_last_path(void) { return g_bn_path; }
+
 size_t movae_bn_ws_bytes(int rows, int c) {
     if (rows <= 0 || c <= 0) return 0;
-    const int nblk = (c % 4 == 0) ? make_split4(rows, c, 1024).nblk : make_split(rows, c).nblk;
+    // the scalar kernels also serve c % 4 == 0 when an operand is not 16-byte aligned, and their split can have more blocks
+    // (rows = 300, c = 8: 3 against 1): room for whichever path the pointers select
+    int nblk = make_split(rows, c).nblk;
+    if (c % 4 == 0 && make_split4(rows, c, 1024).nblk > nblk) nblk = make_split4(rows, c, 1024).nblk;
     return MOVAE_WS_HEADER_BYTES + (size_t)nblk * c * 2 * sizeof(double) + (size_t)c * 2 * sizeof(float) + 64;
 }
 
@@ -759,10 +769,12 @@ int movae_bn_act_fwd(const float* y, const float* gamma, const float* beta, floa
     MOVAE_CHECK_ARG(rows > 0 && c > 0, "movae_bn_act_fwd: bad shape rows=%d c=%d", rows, c);
     hipStream_t st = (hipStream_t)stream;
     long long* nbt = training ? num_batches_tracked : nullptr;
+    bool stats4 = false;
     if (training && rows <= small_rows() && c % 4 == 0 && al16(y, out) && al16(gamma, beta)) {
         hipLaunchKernelGGL(bn_fwd_small, dim3(c / 4), dim3(256), 0, st, y, gamma, beta, out, save_mean, save_rstd,
                            running_mean, running_var, nbt, rows, c, eps, momentum, act, slope);
         MOVAE_CHECK_LAUNCH("bn_fwd_small");
+        g_bn_path = "fwd_small";
         return MOVAE_OK;
     }
     if (training) {
@@ -772,6 +784,7 @@ int movae_bn_act_fwd(const float* y, const float* gamma, const float* beta, floa
         if (c % 4 == 0 && al16(y)) {
             const Split4 s = make_split4(rows, c);
             nblk = s.nblk;
+            stats4 = true;
             hipLaunchKernelGGL(bn_stats_partial4, dim3(s.nblk), dim3(256), 0, st, y, part, rows, c, s.CQB, s.rows_per_block);
         } else {
             const Split s = make_split(rows, c);
@@ -797,6 +810,10 @@ int movae_bn_act_fwd(const float* y, const float* gamma, const float* beta, floa
         hipLaunchKernelGGL(bn_apply<false>, dim3(grid_for(total)), dim3(256), 0, st, y, gamma, beta, save_mean, save_rstd,
                            out, total, c, act, slope);
     MOVAE_CHECK_LAUNCH("bn_apply");
+    // (scalar statistics mean c % 4 != 0 or a misaligned y, and then the apply is scalar too)
+    g_bn_path = !training ? (vec ? "fwd_eval+apply_vec" : "fwd_eval+apply_scalar")
+                : stats4  ? (vec ? "fwd_stats4+apply_vec" : "fwd_stats4+apply_scalar")
+                          : "fwd_stats+apply_scalar";
     return MOVAE_OK;
 }
 
@@ -819,6 +836,7 @@ int movae_bn_act_bwd_grouped(int groups, const float* dout, const float* y, cons
         hipLaunchKernelGGL(bn_bwd_small, dim3(c / 4, groups), dim3(256), 0, st, dout, y, gamma, beta, save_mean, save_rstd, dy, tab,
                            rows, c, act, slope, accumulate);
         MOVAE_CHECK_LAUNCH("bn_bwd_small");
+        g_bn_path = "bwd_small";
         return MOVAE_OK;
     }
     MOVAE_CHECK_ARG(ws && ws_bytes >= MOVAE_WS_HEADER_BYTES + (size_t)groups * (movae_bn_ws_bytes(rows, c) - MOVAE_WS_HEADER_BYTES),
@@ -835,6 +853,7 @@ int movae_bn_act_bwd_grouped(int groups, const float* dout, const float* y, cons
         hipLaunchKernelGGL(bn_bwd_apply4, dim3(grid_for(total / 16), groups), dim3(256), 0, st, dout, y, gamma, beta, save_mean,
                            save_rstd, sums, dy, total, c, act, slope);
         MOVAE_CHECK_LAUNCH("bn_bwd_apply");
+        g_bn_path = "bwd_vec4";
         return MOVAE_OK;
     }
     // generic path (C % 4 != 0 or unaligned operands): one group at a time
@@ -853,6 +872,7 @@ int movae_bn_act_bwd_grouped(int groups, const float* dout, const float* y, cons
                            save_rstd, sums, dy + g * total, total, c, act, slope);
         MOVAE_CHECK_LAUNCH("bn_bwd_apply");
     }
+    g_bn_path = "bwd_scalar";
     return MOVAE_OK;
 }
 
@@ -870,10 +890,12 @@ int movae_bn_finalize(const float* stats, size_t stats_cap, int parts, int rows,
                       float* running_var, long long* num_batches_tracked, movae_stream_t stream) {
     MOVAE_CHECK_ARG(stats && gamma && beta && save_mean && save_rstd && scale && shift, "movae_bn_finalize: null pointer");
     MOVAE_CHECK_ARG(parts > 0 && rows > 0 && c > 0, "movae_bn_finalize: bad shape parts=%d rows=%d c=%d", parts, rows, c);
+    const float* given = stats;
     stats = fold_partials(stats, stats_cap, &parts, 1, c, (hipStream_t)stream);
     hipLaunchKernelGGL(bn_finalize_k, dim3(c), dim3(256), 0, (hipStream_t)stream, stats, parts, rows, c, gamma, beta, eps, momentum,
                        save_mean, save_rstd, scale, shift, running_mean, running_var, num_batches_tracked);
     MOVAE_CHECK_LAUNCH("bn_finalize");
+    g_bn_path = stats != given ? "fold+finalize" : "finalize";
     return MOVAE_OK;
 }
 
@@ -884,6 +906,7 @@ int movae_scale_shift_act(const float* y, const float* scale, const float* shift
     const long nv = (long)rows * c / 4;
     hipLaunchKernelGGL(scale_shift_act_k, dim3(grid_for(nv / 4 + 1)), dim3(256), 0, (hipStream_t)stream, y, scale, shift, out, nv, c, slope);
     MOVAE_CHECK_LAUNCH("scale_shift_act");
+    g_bn_path = "scale_shift_act";
     return MOVAE_OK;
 }
 
@@ -892,6 +915,7 @@ int movae_bn_bwd_finalize(const float* bn_part, size_t bn_cap, int ppg, int grou
                           int accumulate, movae_stream_t stream) {
     MOVAE_CHECK_ARG(bn_part && gamma && save_mean && save_rstd && coef, "movae_bn_bwd_finalize: null pointer");
     MOVAE_CHECK_ARG(ppg > 0 && rows > 0 && c > 0 && groups >= 1 && groups <= MAX_GROUPS, "movae_bn_bwd_finalize: bad shape");
+    const float* given = bn_part;
     bn_part = fold_partials(bn_part, bn_cap, &ppg, groups, c, (hipStream_t)stream);
     BnOut tab;
     for (int g = 0; g < MAX_GROUPS; ++g) {
@@ -901,6 +925,7 @@ int movae_bn_bwd_finalize(const float* bn_part, size_t bn_cap, int ppg, int grou
     hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(c, groups), dim3(256), 0, (hipStream_t)stream, bn_part, ppg, rows, c, gamma, save_mean,
                        save_rstd, tab, coef, accumulate);
     MOVAE_CHECK_LAUNCH("bn_bwd_finalize");
+    g_bn_path = bn_part != given ? "bwd_fold+finalize" : "bwd_finalize";
     return MOVAE_OK;
 }
 
@@ -912,6 +937,7 @@ int movae_bn_bwd_apply(const float* dout, const float* y, const float* scale, co
     hipLaunchKernelGGL(bn_bwd_apply_coef_k, dim3(grid_for(nv / 4 + 1), groups), dim3(256), 0, (hipStream_t)stream, dout, y, scale, shift, slope,
                        coef, dy, nv, c);
     MOVAE_CHECK_LAUNCH("bn_bwd_apply");
+    g_bn_path = "bwd_apply";
     return MOVAE_OK;
 }
 
@@ -929,7 +955,10 @@ int movae_bn_bwd_finalize_apply(const float* bn_part, size_t bn_cap, int ppg, in
         if (int rc = movae_bn_bwd_finalize(bn_part, bn_cap, ppg, groups, (int)rows, c, gamma, save_mean, save_rstd, dgamma, dbeta, coef,
                                            accumulate, stream))
             return rc;
-        return movae_bn_bwd_apply(dout, y, scale, shift, slope, coef, dy, groups, rows, c, stream);
+        const bool folded = strcmp(g_bn_path, "bwd_fold+finalize") == 0;  // as the call above left it
+        if (int rc = movae_bn_bwd_apply(dout, y, scale, shift, slope, coef, dy, groups, rows, c, stream)) return rc;
+        g_bn_path = folded ? "bwd_fold+finalize+apply" : "bwd_finalize+apply";
+        return MOVAE_OK;
     }
     BnOut tab;
     for (int g = 0; g < MAX_GROUPS; ++g) {
@@ -946,6 +975,7 @@ int movae_bn_bwd_finalize_apply(const float* bn_part, size_t bn_cap, int ppg, in
     hipLaunchKernelGGL(bn_bwd_fused_k, dim3((unsigned)chunks, slices, groups), dim3(256), 0, (hipStream_t)stream, bn_part, ppg, (int)rows, c,
                        gamma, save_mean, save_rstd, tab, accumulate, dout, y, scale, shift, slope, dy, (int)rpc);
     MOVAE_CHECK_LAUNCH("bn_bwd_finalize_apply");
+    g_bn_path = "bwd_fused";
     return MOVAE_OK;
 }
 

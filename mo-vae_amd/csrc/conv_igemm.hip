@@ -1876,8 +1876,9 @@ int movae_bn_stats(const float* y, int rows, int c, float* stats, size_t stats_c
     g_fuse = FuseCtx();
     g_fuse.stats = stats, g_fuse.stats_cap = stats_cap;
     const bool ok = launch_reduce_stats(y, nullptr, rows, c, 1, nullptr, 0, 0, 0, nullptr, (hipStream_t)stream);
-    *parts_out = g_fuse.stats_parts;
+    const int parts = g_fuse.stats_parts;
     g_fuse = FuseCtx();
+    if (ok) *parts_out = parts;  // a refusal writes nothing, the caller's int included
     if (!ok) {
         movae_set_error("movae_bn_stats: unsupported shape rows=%d c=%d (needs c %% 4 == 0, 256 %% (c / 4) == 0, aligned operands, room for the partials)", rows, c);
         return MOVAE_EUNSUPPORTED;
