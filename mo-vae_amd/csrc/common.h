@@ -84,11 +84,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // ---- workspace header ----------------------------------------------------------------------------------
-// The first MOVAE_WS_HEADER_BYTES of a caller's workspace are reserved and zero on first use.  Words 64 .. 127 are the arrival
-// counters of the in-launch BatchNorm finish (kgemm.h: fin_*), one per column tile, re-armed to zero by the last block.
+// The first MOVAE_WS_HEADER_BYTES of a caller's workspace are reserved and zero on first use; no kernel uses them
+// at present.
 #define MOVAE_WS_HEADER_BYTES 4096
 
-// plain-scratch users skip the header so it stays zero between the launches that use it
+// plain-scratch users skip the header so it stays zero
 #define MOVAE_WS_SCRATCH(ws, ws_bytes)                                         \
     do {                                                                       \
         if ((ws) && (ws_bytes) > (size_t)MOVAE_WS_HEADER_BYTES) {              \

@@ -24,14 +24,12 @@ def _channels_last_param(t):
 
 
 def _take_lazy(x, fusion):
-    """(fusion, raw tensor) for a conv whose input is an unmaterialised BatchNorm / activation output (ops.LazyBN / ops.LazyAct): the
-    operand transform -- and a LazyAct's ActLink -- join whatever the caller already asked of this conv."""
+    """(fusion, raw tensor) for a conv whose input is an unmaterialised BatchNorm (+ activation) output (ops.LazyBN): the operand
+    transform joins whatever the caller already asked of this conv."""
     if fusion is None:
         fusion = x.fusion()
     elif fusion.in_scale is None:
         fusion.in_scale, fusion.in_shift, fusion.in_slope, fusion.link = x.scale, x.shift, x.slope, x.link
-        if getattr(x, "act_link", None) is not None:
-            fusion.act_in = x.act_link
     return fusion, x.y
 
 
@@ -209,8 +207,6 @@ class Stack(tnn.Sequential):
                     kind = act.kind if act is not None else None
                     if FUSE_BN and nxt.training and kind in (None, "lrelu", "relu") and m.out_channels % 4 == 0:
                         fusion = ops.ConvFusion(want_stats=True, act_in=link, res_in=rin)
-                        # (a producer that can finishes this BatchNorm inside its own launch: ops.ConvFusion.bn_fin)
-                        fusion.bn_fin = (nxt.weight, nxt.bias, nxt.running_mean, nxt.running_var, nxt.num_batches_tracked, nxt.eps, nxt.momentum)
                         if isinstance(x, ops.LazyBN):
                             fusion, x = _take_lazy(x, fusion)
                         x = nxt.forward_lazy(m(x, None, True, fusion), kind, fusion)
@@ -223,7 +219,7 @@ class Stack(tnn.Sequential):
                     # is the reconstruction loss -- ops.VAELosses applies the derivative in its backward kernel)
                     ends = i + 2 == n and nxt.kind in ("tanh", "sigmoid")
                     out = ops.ActLink() if (nxt.kind in ("lrelu", "relu") or ends) else None
-                    # (a LazyBN / LazyAct input adds its operand transform to this request: _take_lazy)
+                    # (a LazyBN input adds its operand transform to this request: _take_lazy)
                     x = m(x, nxt.kind, False, ops.ConvFusion(act_in=link, act_out=out, res_in=rin)
                           if (link is not None or out is not None or rin is not None) else None)
                     link = out
@@ -238,13 +234,7 @@ class Stack(tnn.Sequential):
                   and not isinstance(x, ops.LazyBN)):
                 # a stand-alone activation whose output only the next conv reads: that conv's input gradient applies its derivative
                 link = ops.ActLink()
-                nxt = mods[i + 1]
-                if ops.LAZY_ACT and isinstance(nxt, (Conv2d, ConvTranspose2d)) and x.shape[-1] % 4 == 0:
-                    # not written at all: the conv applies it while loading (ops.LazyAct); the link travels inside the LazyAct
-                    x = ops.LazyAct(x, m.kind, LRELU_SLOPE, link, rin)
-                    link = None
-                else:
-                    x = ops.activation(x, m.kind, LRELU_SLOPE, link, rin)
+                x = ops.activation(x, m.kind, LRELU_SLOPE, link, rin)
                 i += 1
             else:
                 x = m(ops.materialize(x))

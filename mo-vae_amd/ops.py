@@ -377,16 +377,12 @@ class ConvFusion:
     in_*: the input is the RAW output y of a producer conv whose BatchNorm + activation this conv applies while loading,
     x = leaky_relu(in_scale[c] * y + in_shift[c], in_slope).  want_stats: the epilogue (or split-K reduce) also emits the
     per-channel partial sums of this conv's own output for the BatchNorm that follows it: `stats` / `parts` on return."""
-    __slots__ = ("in_scale", "in_shift", "in_slope", "want_stats", "stats", "parts", "link", "act_in", "act_out", "res_in", "res_out",
-                 "bn_fin", "fin")
+    __slots__ = ("in_scale", "in_shift", "in_slope", "want_stats", "stats", "parts", "link", "act_in", "act_out", "res_in", "res_out")
 
     def __init__(self, in_scale=None, in_shift=None, in_slope=1.0, want_stats=False, link=None, act_in=None, act_out=None, res_in=None,
                  res_out=None):
         self.in_scale, self.in_shift, self.in_slope, self.want_stats = in_scale, in_shift, float(in_slope), want_stats
         self.stats, self.parts = None, 0
-        #: (gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum) of the training-mode BatchNorm that follows:
-        #: a producer that can (csrc/kgemm.h) finishes it inside its own launch; `fin` = [4, c] (mean, rstd, scale, shift) then
-        self.bn_fin, self.fin = None, None
         #: ActLink of the producer whose activation output is this conv's input / ActLink this conv fills for its consumer
         self.act_in, self.act_out = act_in, act_out
         #: ResCarrier of the residual block whose branch starts with THIS conv (its input is the block's input)
@@ -404,17 +400,6 @@ _NO_FUSE = set()
 #: A/B knobs of the fusion's three parts (development): the normalise-on-load of consumers, the statistics from producer epilogues
 FUSE_NORM = _knob("FUSE_NORM")
 FUSE_STATS = _knob("FUSE_STATS")
-
-
-#: MOVAE_BN_FIN=0: never ask a producer to finish the BatchNorm that follows (A/B knob; the kernels' own switch is MOVAE_KGEMM_BN_FIN)
-BN_FIN = _knob("BN_FIN")
-
-
-def _fuse_fin(f, bn_fin, out):
-    """movae_fuse_t::fin_*: bn_fin = (gamma, beta, running_mean, running_var, nbt, eps, momentum), out = [4, c] result buffer"""
-    gamma, beta, rm, rv, nbt, eps, mom = bn_fin
-    f.fin_gamma, f.fin_beta, f.fin_eps, f.fin_momentum = gamma.data_ptr(), beta.data_ptr(), float(eps), float(mom)
-    f.fin_out, f.fin_running_mean, f.fin_running_var, f.fin_nbt = out.data_ptr(), L.ptr(rm), L.ptr(rv), L.ptr(nbt)
 
 
 def _fuse_struct(in_norm, stats=None, bn=None, ep=None):
@@ -533,7 +518,7 @@ def _act_bwd(dest, G, dy, y, dx, act, slope):
 
 
 def _call_f(name, geom, x, in_norm, args, fuse):
-    """The *_f form of entry point `name` on the operand x with the virtual transform in_norm (or None): args(x) -> the plain argument
+    """The *_f form of entry point `name` on the operand x with the fused-BatchNorm transform in_norm (or None): args(x) -> the plain argument
     list, fuse(in_norm, retry) -> the movae_fuse_t.  Where the dispatched kernel cannot apply the transform (L.Unsupported) the shape is
     remembered in _NO_FUSE, the transformed operand is materialised and the call repeated without it (retry=True).
     -> (x as used, in_norm as used, the fuse struct of the call that ran)."""
@@ -591,21 +576,11 @@ class Conv(Function):
         if in_norm is None and stats is None and ep_fwd is None:
             _call(fn, x.data_ptr(), wm.data_ptr(), L.ptr(b), y.data_ptr(), *geom, L.ACT[act], float(slope), wsp, wsb, _st(x))
         else:
-            fin_out = None
-            if stats is not None and fusion.bn_fin is not None and BN_FIN:
-                fin_out = torch.empty((4, co), dtype=torch.float32, device=x.device)
-
-            def fuse(nrm, retry):
-                f = _fuse_struct(nrm, stats, None, ep_fwd)
-                if fin_out is not None:
-                    _fuse_fin(f, fusion.bn_fin, fin_out)
-                return f
-
             x, in_norm, f = _call_f(fn, geom, x, in_norm, lambda x: (x.data_ptr(), wm.data_ptr(), L.ptr(b), y.data_ptr(), *geom, L.ACT[act],
-                                                                     float(slope), wsp, wsb, _st(x)), fuse)
+                                                                     float(slope), wsp, wsb, _st(x)),
+                                    lambda nrm, retry: _fuse_struct(nrm, stats, None, ep_fwd))
             if fusion is not None:
                 fusion.stats, fusion.parts = stats, int(f.stats_parts)
-                fusion.fin = fin_out if (fin_out is not None and int(f.fin_done)) else None
             if ep_fwd is not None and not int(f.ep_act_done):  # this kernel has no such epilogue: one explicit add
                 _call("movae_add", y.data_ptr(), ep_fwd[1].data_ptr(), y.data_ptr(), y.numel(), _st(x))
         ctx.geom = geom
@@ -613,8 +588,8 @@ class Conv(Function):
         ctx.bias_grad_is_zero = bias_grad_is_zero
         ctx.in_slope = in_norm[2] if in_norm is not None else None
         ctx.bn_link = fusion.link if (fusion is not None and in_norm is not None) else None
-        # (with a transformed input: only the virtual stand-alone activation -- no BatchNorm link -- carries an ActLink too)
-        ctx.act_in = fusion.act_in if (fusion is not None and (in_norm is None or fusion.link is None)) else None
+        # (a transformed input is a LazyBN's, whose backward goes through `link`: no ActLink with it)
+        ctx.act_in = fusion.act_in if (fusion is not None and in_norm is None) else None
         ctx.res_in = fusion.res_in if fusion is not None else None
         ctx.res_out = res_out[1] if res_out is not None else None
         ctx.act_out = None
@@ -633,7 +608,7 @@ class Conv(Function):
 
     @staticmethod
     def _wgrad_call(name, in_norm, geom, args, bn=None, ep=None):
-        """One weight-gradient (or paired dgrad + wgrad) call; with a virtual activation operand the *_f form, falling back
+        """One weight-gradient (or paired dgrad + wgrad) call; with the fused-BatchNorm operand transform the *_f form, falling back
         to a materialised activation where the dispatched kernel cannot apply the transform.  args: (head, x_index, tail).
         bn: BatchNorm-backward request for the paired call's dgrad (_bn_request).  Returns (x as used, fuse struct or None)."""
         head, xi, tail = args
@@ -644,12 +619,9 @@ class Conv(Function):
         if in_norm is None and bn is None and ep is None:
             _call(name, *argv(x))
             return x, None
-        # The repeated call asks for no `ep`.  Only a paired call gets here with one (its input a virtual activation, MOVAE_LAZY_ACT=1,
-        # on a shape whose weight gradient takes a kernel without the operand transform), and its first attempt has by then run the
-        # dgrad WITH the epilogue (the library issues the pair's dgrad before it asks the wgrad
-        # dispatch).  Harmless: the repeat overwrites dx with the plain input gradient and reports ep_act_done == 0, so _act_publish
-        # publishes nothing -- the producer runs its own activation backward, the carrier keeps its cotangent for _res_finish.  From
-        # the next step on _NO_FUSE materialises up front and the epilogue is asked for again.
+        # The repeated call asks for no `ep` (only a paired call on a LazyBN input without a `bn` request, its conv opening a residual
+        # branch -- ctx.res_in -- gets here with one): it overwrites dx with the plain input gradient and reports ep_act_done == 0, so
+        # _act_publish publishes nothing and _res_finish adds the carrier's cotangent explicitly.
         x, _, f = _call_f(name, geom, x, in_norm, argv, lambda nrm, retry: _fuse_struct(nrm, None, bn, None if retry else ep))
         return x, f
 
@@ -926,41 +898,6 @@ class LazyBN:
         return ScaleShiftAct.apply(self.y, self.scale, self.shift, self.slope)
 
 
-#: MOVAE_LAZY_ACT=1: a stand-alone ReLU / LeakyReLU in front of a conv is not written to memory -- the conv applies it while loading
-#: (LazyAct).  OFF by default: measured SLOWER (C4 4.56 vs 4.44 ms, C3 10.61 vs 10.56): the operand transform in the consumer's
-#: forward and weight-gradient kernels costs more than the twelve 6 us activation launches it removes.
-LAZY_ACT = _knob("LAZY_ACT", "0")
-_UNIT_MAP = {}
-
-
-def _unit_map(c, device):
-    """(ones[c], zeros[c]): the identity scale / shift of a virtual activation, one pair per channel count and device for life"""
-    key = (c, device.type, device.index)
-    m = _UNIT_MAP.get(key)
-    if m is None:
-        m = _UNIT_MAP[key] = (torch.ones(c, dtype=torch.float32, device=device), torch.zeros(c, dtype=torch.float32, device=device))
-    return m
-
-
-class LazyAct(LazyBN):
-    """A stand-alone ReLU / LeakyReLU whose output only the next conv reads, NOT written to memory: the conv applies it while loading
-    (the fused-BatchNorm operand transform with scale 1, shift 0), its input-gradient epilogue applies the derivative (ActLink, read
-    off the sign of the raw x).  `y` is the raw x as an Activation tape node (virtual=True)."""
-    __slots__ = ("act_link",)
-
-    def __init__(self, x, act, slope, link, res_in):
-        sl = 0.0 if act == "relu" else float(slope)
-        y = Activation.apply(x, act, sl, link, res_in, True)
-        one, zero = _unit_map(x.shape[-1], x.device)
-        super().__init__(y, one, zero, sl, None)
-        self.act_link = link
-
-    def fusion(self, want_stats=False):
-        f = ConvFusion(self.scale, self.shift, self.slope, want_stats, None)
-        f.act_in = self.act_link
-        return f
-
-
 def materialize(x):
     return x.materialize() if isinstance(x, LazyBN) else x
 
@@ -994,24 +931,21 @@ class BatchNormLazy(Function):
     (movae_bn_act_bwd) on the saved raw y."""
 
     @staticmethod
-    def forward(ctx, y, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, slope, stats, parts, link=None, fin=None):
+    def forward(ctx, y, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, slope, stats, parts, link=None):
         L.require_gpu(y)
         c = y.shape[-1]
         rows = y.numel() // c
         st = _st(y)
-        if fin is not None:  # the producer conv finished this BatchNorm inside its own launch (movae_fuse_t::fin_*)
-            mean, rstd, scale, shift = fin[0], fin[1], fin[2], fin[3]
-        else:
-            if not parts:
-                stats = torch.empty(1100 * 2 * c, dtype=torch.float32, device=y.device)  # movae_bn_stats: at most 1024 partials (+ room to fold them)
-                pout = C.c_int(0)
-                _call("movae_bn_stats", y.data_ptr(), rows, c, stats.data_ptr(), stats.numel(), C.byref(pout), st)
-                parts = pout.value
-            mean = torch.empty(c, dtype=y.dtype, device=y.device)
-            rstd, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-            _call("movae_bn_finalize", stats.data_ptr(), stats.numel(), int(parts), rows, c, gamma.data_ptr(), beta.data_ptr(), float(eps),
-                  float(momentum), mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), L.ptr(running_mean),
-                  L.ptr(running_var), L.ptr(num_batches_tracked), st)
+        if not parts:
+            stats = torch.empty(1100 * 2 * c, dtype=torch.float32, device=y.device)  # movae_bn_stats: at most 1024 partials (+ room to fold them)
+            pout = C.c_int(0)
+            _call("movae_bn_stats", y.data_ptr(), rows, c, stats.data_ptr(), stats.numel(), C.byref(pout), st)
+            parts = pout.value
+        mean = torch.empty(c, dtype=y.dtype, device=y.device)
+        rstd, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
+        _call("movae_bn_finalize", stats.data_ptr(), stats.numel(), int(parts), rows, c, gamma.data_ptr(), beta.data_ptr(), float(eps),
+              float(momentum), mean.data_ptr(), rstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), L.ptr(running_mean),
+              L.ptr(running_var), L.ptr(num_batches_tracked), st)
         ctx.act, ctx.slope = ("lrelu" if slope not in _ACT_OF_SLOPE else _ACT_OF_SLOPE[slope]), slope
         ctx.link = link
         ctx.save_for_backward(y, gamma, beta, mean, rstd, scale, shift)
@@ -1054,12 +988,12 @@ class BatchNormLazy(Function):
     @staticmethod
     def backward(ctx, dout, _ds, _dh):
         if dout is None:
-            return (None,) * 13
-        return tuple(t[0] for t in BatchNormLazy._run(ctx, 1, _c(dout).unsqueeze(0), _ENGINE)) + (None,) * 10
+            return (None,) * 12
+        return tuple(t[0] for t in BatchNormLazy._run(ctx, 1, _c(dout).unsqueeze(0), _ENGINE)) + (None,) * 9
 
     @staticmethod
     def backward_batched(ctx, G, dout, _ds=None, _dh=None):
-        return BatchNormLazy._run(ctx, G, _stacked(dout, G), _WALKER) + (None,) * 10
+        return BatchNormLazy._run(ctx, G, _stacked(dout, G), _WALKER) + (None,) * 9
 
 
 def batch_norm_lazy(y, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, act, slope, fusion):
@@ -1069,7 +1003,7 @@ def batch_norm_lazy(y, gamma, beta, running_mean, running_var, num_batches_track
     link = {}
     try:
         yv, scale, shift = BatchNormLazy.apply(y, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, sl, stats,
-                                               parts, link, fusion.fin if fusion is not None else None)
+                                               parts, link)
     except L.Unsupported:  # no partial sums from the producer and a shape the stand-alone statistics pass does not take
         return batch_norm_act(y, gamma, beta, running_mean, running_var, True, eps, momentum, act, slope, num_batches_tracked)
     return LazyBN(yv, scale, shift, sl, link)
@@ -1087,18 +1021,12 @@ class Activation(Function):
     may apply this activation's derivative itself (nn.Stack arranges that); the backward then passes the gradient through."""
 
     @staticmethod
-    def forward(ctx, x, act, slope, act_out=None, res_in=None, virtual=False):
+    def forward(ctx, x, act, slope, act_out=None, res_in=None):
         ctx.set_materialize_grads(False)  # an absent cotangent arrives as None: no zero-fill, no kernels on zeros
         L.require_gpu(x)
         x = _c(x)
-        if virtual:
-            # no kernel: the ONE consumer (a conv) applies the activation while it loads x (ops.LazyAct); `y` is x itself as a new
-            # tape node, and stands in for the output wherever only its SIGN matters (ReLU / LeakyReLU derivative: act'(x) from x)
-            assert act in ("relu", "lrelu") and act_out is not None
-            y = x.view_as(x)
-        else:
-            y = torch.empty_like(x)
-            _call("movae_act_fwd", x.data_ptr(), y.data_ptr(), x.numel(), L.ACT[act], float(slope), _st(x))
+        y = torch.empty_like(x)
+        _call("movae_act_fwd", x.data_ptr(), y.data_ptr(), x.numel(), L.ACT[act], float(slope), _st(x))
         ctx.act, ctx.slope = act, slope
         ctx.act_out, ctx.res_in = act_out, res_in  # res_in: this activation is the first op of a residual branch (ResCarrier)
         if act_out is not None:
@@ -1128,12 +1056,12 @@ class Activation(Function):
     @staticmethod
     def backward(ctx, dy):
         if dy is None:
-            return (None,) * 6
-        return (Activation._run(ctx, 1, _c(dy).unsqueeze(0), _ENGINE)[0],) + (None,) * 5
+            return (None,) * 5
+        return (Activation._run(ctx, 1, _c(dy).unsqueeze(0), _ENGINE)[0],) + (None,) * 4
 
     @staticmethod
     def backward_batched(ctx, G, dy):
-        return (Activation._run(ctx, G, _stacked(dy, G), _WALKER),) + (None,) * 5
+        return (Activation._run(ctx, G, _stacked(dy, G), _WALKER),) + (None,) * 4
 
 
 def activation(x, act, slope=0.01, act_out=None, res_in=None):

@@ -4,7 +4,9 @@ dispatches to and computes, on an MI355X.  The committed file was recorded from 
 for the big conv tiles ..."), the last one before the host code that plans and pairs these launches was consolidated;
 test_conv_pair_parent.py replays the same cases on the current build and holds it to every recorded field.  The kernels fold in a
 fixed order and use no float atomics, so the results are recorded as SHA-256 of their bytes.  The library is loaded by path through
-ctypes, not through the package, so a build of another commit can be given.
+ctypes, not through the package, so a build of another commit can be given -- but run the recorder with the _lib.MovaeFuse of the
+SAME commit as the library it records: movae_fuse_t has since lost its last members, and an older library writes an output field of
+its own past the end of the shorter struct.
 
 Cases (ids "<row of PAIR_SHAPES>-g<groups>-k<force_kgemm>-<variant>"): every row of test_hip_ops.PAIR_SHAPES, 1 and 2 cotangent
 groups, movae_bench_force_kgemm 0 and 1, with no fuse struct ("plain"), with an ep_act ReLU request ("act") and ep_res on top of it
