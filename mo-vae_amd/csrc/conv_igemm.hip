@@ -1131,6 +1131,7 @@ inline int pair_flush(hipStream_t st);
 #include "conv_thin.h"
 #include "linear_small.h"
 #include "kgemm.h"
+#include "convt_img.h"
 #include "pair.h"
 namespace kg {
 inline bool g_force_kgemm_on() { return g_force_kgemm > 0; }
@@ -1268,8 +1269,9 @@ int launch_bwd_t(const float* X, const float* W, float* Y, const Geom& g, const 
     return MOVAE_OK;
 }
 
+// convt_fwd: the call is the FORWARD pass of a transposed conv (never an input gradient, whose kernels and bits are recorded)
 int launch_bwd(const float* X, const float* W, float* Y, const Geom& g, const Epilogue& ep, void* ws, size_t ws_bytes,
-               hipStream_t st) {
+               hipStream_t st, bool convt_fwd = false) {
     const long Ml = (long)g.Nimg * g.Ho * g.Wo;
     if (Ml <= 0 || g.Nn <= 0 || g.Cr <= 0 || Ml > 0x7fffffffL) {
         movae_set_error("conv bwd-form: bad shape M=%ld N=%d Cr=%d", Ml, g.Nn, g.Cr);
@@ -1304,6 +1306,7 @@ int launch_bwd(const float* X, const float* W, float* Y, const Geom& g, const Ep
         if (int rc = kg::launch_kbwd(X, W, Y, g, ep, st, &handled)) return rc;
         if (handled) return MOVAE_OK;
     }
+    if (convt_fwd && img::img_ok(X, W, Y, g, ep)) return img::launch_img(X, W, Y, g, ep, st);  // whole image rows per block (convt_img.h)
     if (g.Cr % 4 == 0 && g.Nn % 4 == 0 && g.stride <= 2 && aligned16(X) && aligned16(W) && aligned16(Y) && span_ok) {
         if (g.Nn <= 32) return (g_last_kernel = "igemm2_bwd<128,32>", v2::launch_bwd2<128, 32>(X, W, Y, g, ep, ws, ws_bytes, st));
         if (g.Nn >= 128 && (Mc / 128) * (g.Nn / 128) * g.stride * g.stride >= big_tile_min())
@@ -1522,7 +1525,7 @@ static int conv_fwd(bool transposed, const float* x, const float* w, const float
     MOVAE_CHECK_FUSE(fuse, ci);
     FuseScope scope(fuse, 0);
     Geom g{n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad};
-    return transposed ? launch_bwd(x, w, y, g, Epilogue{bias, act, slope}, ws, ws_bytes, (hipStream_t)stream)
+    return transposed ? launch_bwd(x, w, y, g, Epilogue{bias, act, slope}, ws, ws_bytes, (hipStream_t)stream, true)
                       : launch_fwd(x, w, y, g, Epilogue{bias, act, slope}, ws, ws_bytes, (hipStream_t)stream);
 }
 
