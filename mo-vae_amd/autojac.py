@@ -71,14 +71,14 @@ def _ones_like(t):
 
 
 def _accumulate(p, g, taken=()):
-    """p.grad += g.  `taken`: parameters whose gradient a kernel already added into p.grad in place (ops.GRAD_ACCUM_TAKEN).
+    """p.grad += g.  `taken`: parameters whose gradient a kernel already added into p.grad in place (Destinations.taken).
     Such a parameter must come back as that very tensor: a parameter that feeds TWO nodes of one loss (weight sharing) is
     accumulated in place by the first node only, autograd then sums the two results into a NEW tensor (old + g1) + g2, and adding
     that to p.grad would count old + g1 twice -- raised, not silently added."""
     if p.grad is None:
         p.grad = g
     elif g.data_ptr() == p.grad.data_ptr() and g.shape == p.grad.shape:
-        pass  # the kernels already added this loss's gradient into p.grad (ops.GRAD_ACCUM)
+        pass  # the kernels already added this loss's gradient into p.grad (Destinations.accum)
     elif p.data_ptr() in taken:
         raise RuntimeError("a parameter's gradient was accumulated in place by a weight-gradient kernel, but autograd returned a "
                            "different tensor for it (the parameter feeds more than one node of this loss?): in-place accumulation "
@@ -97,8 +97,9 @@ class JacobianBuffer:
 
     A slice nobody writes must read zero (a loss with no path to a parameter; the bias in front of a training-mode BatchNorm).
     `JacobianBuffer.persistent` keeps the arena across steps instead of zero-filling K x m floats per step (13.6 MB at C2,
-    180 MB at C5): the slices written in a step are known from ops.SINK_LOG / write_row, `settle()` zeroes exactly those that
-    an EARLIER step wrote and this one did not (normally none: the step's graph does not change)."""
+    180 MB at C5): the slices written in a step are recorded here -- `written` through the sinks of `destinations()`, `copied` by
+    write_row / the walker -- and `settle()` zeroes exactly those that an EARLIER step wrote and this one did not (normally none:
+    the step's graph does not change).  A non-persistent arena's records go with it."""
 
     def __init__(self, params, k, device):
         self.params = params
@@ -112,6 +113,7 @@ class JacobianBuffer:
         self.buf = torch.zeros((k, max(self.ld, 4)), dtype=torch.float32, device=device)
         self.dirty = None      # persistent use: data_ptr -> (row, parameter index) of every slice some step wrote
         self.copied = set()    # slices written by write_row / the walker's leaf copies in the current step
+        self.written = []      # ... and by the backward kernels in place, through the sinks of destinations()
 
     @classmethod
     def persistent(cls, params, k, device):
@@ -128,9 +130,7 @@ class JacobianBuffer:
             jb = cls(params, k, device)
             jb.dirty = {}
             arenas.append(jb)
-        jb.copied = set()
-        ops.SINK_LOG.clear()
-        ops.SINK_ZERO_LOG.clear()
+        jb.copied, jb.written = set(), []
         return jb
 
     def settle(self):
@@ -142,24 +142,27 @@ class JacobianBuffer:
             base = self.buf[i].data_ptr()
             for j, (p, off) in enumerate(zip(self.params, self.offsets)):
                 where[base + 4 * off] = (i, j)
-        now = {ptr for ptr in list(ops.SINK_LOG) + list(self.copied) if ptr in where}
+        now = {ptr for ptr in self.written + list(self.copied) if ptr in where}
         for ptr in [q for q in self.dirty if q not in now]:
             i, j = self.dirty[ptr]
             self.buf[i][self.offsets[j]: self.offsets[j] + self.params[j].numel()].zero_()
             del self.dirty[ptr]
         for ptr in now:
             self.dirty[ptr] = where[ptr]
-        ops.SINK_LOG.clear()
-        ops.SINK_ZERO_LOG.clear()
+        self.written = []
 
     @property
     def J(self):
         return self.buf[:, : self.m]
 
     def sinks(self, i):
-        """{param data_ptr: row slice}: lets the backward kernels write row i of J in place (ops.GRAD_SINK)."""
+        """{param data_ptr: row slice}: lets the backward kernels write row i of J in place (a row of ops.Destinations)."""
         row = self.buf[i]
         return {p.data_ptr(): row[off: off + p.numel()] for p, off in zip(self.params, self.offsets)}
+
+    def destinations(self, rows, engine):
+        """ops.Destinations over the sinks of `rows` (one group each); what is written through them joins this step's record."""
+        return ops.Destinations(engine, [self.sinks(r) for r in rows], written=self.written)
 
     def write_row(self, i, grads):
         row = self.buf[i]
@@ -254,7 +257,7 @@ def _batched_pullback(features, feat_grads, rows, jb):
             continue
         ref = next(x for x in gs if x is not None)
         gs = [x if x is not None else torch.zeros_like(ref) for x in gs]
-        roots.append((fn, feat.output_nr, _restack(gs)))  # (adjacent slices of one buffer -- ops.COT_SINK -- become one [G, ...] view)
+        roots.append((fn, feat.output_nr, _restack(gs)))  # (adjacent slices of one buffer -- Destinations.cot -- become one [G, ...] view)
     deps, seen, stack = {}, set(), [fn for fn, _, _ in roots]
     while stack:
         fn = stack.pop()
@@ -271,8 +274,7 @@ def _batched_pullback(features, feat_grads, rows, jb):
         slot[nr] = _accumulate_stacked(slot.get(nr), gs, G)
     ready = [fn for fn in {r[0] for r in roots} if deps.get(fn, 0) == 0]
     col = {id(p): (p, off) for p, off in zip(jb.params, jb.offsets)}
-    ops.GRAD_SINK_ROWS = [jb.sinks(r) for r in rows]
-    try:
+    with jb.destinations(rows, engine=False):
         while ready:
             fn = ready.pop()
             got = pending.pop(fn, {})
@@ -336,8 +338,6 @@ def _batched_pullback(features, feat_grads, rows, jb):
                 deps[nf] -= 1
                 if deps[nf] == 0:
                     ready.append(nf)
-    finally:
-        ops.GRAD_SINK_ROWS = None
 
 
 def _aggregate_into_grads(jb, aggregator):
@@ -375,7 +375,7 @@ def mtl_backward_begin(losses, features, aggregator, tasks_params=None, shared_p
     st.feat_grads = []
     st.task_params = []
     # the K cotangents of every feature are born stacked: [K, ...] buffers whose slice i the op that produces d(loss i)/d(feature)
-    # writes directly (ops.COT_SINK) -- no torch.stack launch in front of the batched pull-back
+    # writes directly (Destinations.cot) -- no torch.stack launch in front of the batched pull-back
     cot = [torch.empty_strided((len(losses),) + tuple(f.shape), (f.numel(),) + tuple(f.stride()), dtype=f.dtype, device=f.device)
            if _dense(f) else None for f in st.feat_diff]  # (slice i has the feature's own strides: NHWC memory under an NCHW view)
     for i, (loss, tp) in enumerate(zip(losses, tasks_params)):
@@ -383,52 +383,41 @@ def mtl_backward_begin(losses, features, aggregator, tasks_params=None, shared_p
         # the seed cotangent is a persistent ones tensor: autograd would launch a fill per loss for its implicit ones_like
         seed = _ones_like(loss) if loss.dim() == 0 and loss.dtype == torch.float32 else None
         # task-side parameters an earlier loss already reached get this loss's gradient added inside the weight-gradient kernels
-        ops.GRAD_ACCUM.clear()
-        ops.GRAD_ACCUM_TAKEN.clear()
-        if i > 0:
-            ops.GRAD_ACCUM.update({p.data_ptr(): p.grad for p in tp if p.grad is not None})
-        ops.COT_SINK.clear()
-        ops.COT_SINK.update({f.data_ptr(): c[i] for f, c in zip(st.feat_diff, cot) if c is not None})
+        accum = {p.data_ptr(): p.grad for p in tp if p.grad is not None} if i > 0 else None
         # a task-side parameter no earlier loss reached gets its gradient written into a buffer kept across steps (no allocation;
         # and a destination the kernels know nobody reads before the optimizer: its split-K reduce may ride on a later launch)
-        ops.GRAD_SINK.clear()
-        owned = {}
+        sinks, owned = {}, {}
         for p in tp:
             if p.grad is None:
-                buf = ops.GRAD_SINK[p.data_ptr()] = _task_grad_buffer(p)
+                buf = sinks[p.data_ptr()] = _task_grad_buffer(p)
                 owned[buf.data_ptr()] = p
-        n_w, n_z = len(ops.SINK_LOG), len(ops.SINK_ZERO_LOG)
+        d = ops.Destinations(True, [sinks], accum, {f.data_ptr(): c[i] for f, c in zip(st.feat_diff, cot) if c is not None})
         try:
-            with ops.deferred_reduces():
+            with d, ops.deferred_reduces():
                 got = torch.autograd.grad(loss, tp + st.feat_diff, grad_outputs=seed, retain_graph=True, allow_unused=True)
         finally:
-            # a buffer handed out as an untouched all-zero gradient (ops._sink_zeros) must BE zero: it is, unless an earlier
+            # a buffer handed out as an untouched all-zero gradient (Destinations.zeros) must BE zero: it is, unless an earlier
             # step wrote it (a BatchNorm switched between eval and training mode) -- re-zeroed then, once
-            for ptr in ops.SINK_LOG[n_w:]:
+            for ptr in d.written:
                 if ptr in owned:
                     owned[ptr]._movae_grad_written = True
-            for ptr in ops.SINK_ZERO_LOG[n_z:]:
+            for ptr in d.zeroed:
                 if ptr in owned and getattr(owned[ptr], "_movae_grad_written", False):
                     owned[ptr]._movae_grad_buf.zero_()
                     owned[ptr]._movae_grad_written = False
-            ops.GRAD_SINK.clear()
-            ops.COT_SINK.clear()
-            ops.GRAD_ACCUM.clear()
-            taken = frozenset(ops.GRAD_ACCUM_TAKEN)
-            ops.GRAD_ACCUM_TAKEN.clear()
         for p, g in zip(tp, got[: len(tp)]):
             if g is not None:
-                _accumulate(p, g, taken)
+                _accumulate(p, g, d.taken)
                 st.task_params.append(p)
         st.feat_grads.append(got[len(tp):])
     return st
 
 
 def _task_grad_buffer(p):
-    """Flat fp32 buffer of p's size, one per parameter for life (the memory image of the gradient: ops._sink views it)."""
+    """Flat fp32 buffer of p's size, one per parameter for life (the memory image of the gradient: a sink of ops.Destinations views it)."""
     buf = getattr(p, "_movae_grad_buf", None)
     if buf is None or buf.numel() != p.numel() or buf.device != p.device:
-        buf = torch.zeros(p.numel(), dtype=p.dtype, device=p.device)  # (zero: ops._sink_zeros hands a sink out untouched)
+        buf = torch.zeros(p.numel(), dtype=p.dtype, device=p.device)  # (zero: Destinations.zeros hands a sink out untouched)
         p._movae_grad_buf, p._movae_grad_written = buf, False
     return buf
 
@@ -454,13 +443,9 @@ def _mtl_backward_finish(st):
         live = [(f, g) for f, g in zip(feat_diff, gf) if g is not None]
         if not live or not shared_params:
             continue  # no path from this loss to the shared parameters: zero Jacobian row
-        ops.GRAD_SINK.clear()
-        ops.GRAD_SINK.update(jb.sinks(i))
-        try:
+        with jb.destinations([i], engine=True):
             js = torch.autograd.grad([f for f, _ in live], shared_params, grad_outputs=[g for _, g in live],
                                      retain_graph=True, allow_unused=True)
-        finally:
-            ops.GRAD_SINK.clear()
         jb.write_row(i, js)
     if shared_params:
         ops.flush_deferred()  # the last weight gradient's reduce may still be parked; the aggregator may start with a torch op on J

@@ -24,93 +24,116 @@ def _knob(name, default="1"):
     return v == "1" if default == "0" else v != "0"
 
 
-#: data_ptr of a parameter -> 1-D destination tensor for its gradient.  autojac.mtl_backward points this at
-#: the current row of the Jacobian arena so wgrad / BN-backward kernels write their results in place
-#: (consumed on first use; a second use of the same parameter falls back to a fresh buffer).
-GRAD_SINK = {}
+class Destinations:
+    """Where the results of ONE autograd call or one batched pull-back go, and with it what only one of a backward body's (`_run`)
+    two callers does.  Two kinds, no subclasses: the engine's (engine=True) serves Function.backward (torch's engine: one cotangent,
+    stacked as [1, ...], one row), the walker's serves backward_batched (autojac._batched_pullback: G cotangents, G = 1 included,
+    one row per group).  The caller (autojac) builds one, installs it (`with d:`) around the call and reads its records afterwards.
+      rows      per group {param data_ptr: flat slice}: the gradient is written there in place (a Jacobian row, a task-side
+                parameter's buffer) -- consumed on first use, a second use of the same parameter gets a fresh buffer
+      accum     {param data_ptr: its EXISTING gradient}: the weight-gradient kernels add into it (split-K reduce with accumulate)
+                instead of writing a tensor that a torch add then folds in -- a task-side parameter an earlier loss already reached
+      cot       {FEATURE data_ptr: slice i of a stacked [K, ...] buffer}: the op that produces d(loss i)/d(feature) (reparameterize,
+                the KL term, ...) writes there, so the K cotangents of a feature are born stacked -- no torch.stack launch before
+                the batched pull-back; an op that does not know about it simply returns its own buffer (and the stack copies)
+      written, zeroed, taken   its records: data_ptr of every slice handed out for WRITING / as an untouched all-zero gradient, and
+                of every parameter accumulated in place (autojac._accumulate checks what autograd hands back against it)
+      engine    the engine takes the entry points of one cotangent (movae_act_bwd, movae_bn_act_bwd) where the walker takes the
+                grouped ones: the caller's choice, never G == 1's"""
+    __slots__ = ("engine", "rows", "accum", "cot", "written", "zeroed", "taken", "prev")
 
+    def __init__(self, engine, rows=(), accum=None, cot=None, written=None):
+        self.engine, self.rows, self.accum, self.cot = engine, rows, accum or {}, cot or {}
+        self.written, self.zeroed, self.taken = [] if written is None else written, [], set()
 
-#: data_ptr of every sink slice a kernel was handed for WRITING since the log was last cleared (SINK_LOG), and of every slice
-#: handed out as an untouched all-zero gradient (SINK_ZERO_LOG): autojac.JacobianBuffer keeps its arena across steps without
-#: re-zeroing it and uses the two logs to find slices that were written in an earlier step but not in this one.
-SINK_LOG = []
-SINK_ZERO_LOG = []
+    def __enter__(self):
+        global _INSTALLED
+        self.prev, _INSTALLED = _INSTALLED, self
+        return self
 
+    def __exit__(self, *exc):
+        global _INSTALLED
+        _INSTALLED = self.prev
+        return False
 
-def _registered(sinks, param, shape, log):
-    """The sink registered for `param` in the dict `sinks` (consumed, and its data_ptr logged), or None."""
-    dst = sinks.pop(param.data_ptr(), None) if sinks else None
-    if dst is not None and dst.numel() == param.numel():
-        log.append(dst.data_ptr())
-        return dst.view(shape)
-    return None
+    def _registered(self, g, param, shape, record):
+        """Group g's sink registered for `param` (consumed, and its data_ptr recorded), or None."""
+        row = self.rows[g] if self.rows else None
+        dst = row.pop(param.data_ptr(), None) if row else None
+        if dst is not None and dst.numel() == param.numel():
+            record.append(dst.data_ptr())
+            return dst.view(shape)
+        return None
 
+    def sink(self, g, param, shape):
+        """Destination of group g's gradient of `param`: the registered sink, else a fresh buffer."""
+        dst = self._registered(g, param, shape, self.written)
+        return dst if dst is not None else torch.empty(shape, dtype=param.dtype, device=param.device)
 
-def _sink(g, param, shape):
-    """Destination of the gradient of `param` for the engine's single cotangent (g is 0)."""
-    dst = _registered(GRAD_SINK, param, shape, SINK_LOG)
-    return dst if dst is not None else torch.empty(shape, dtype=param.dtype, device=param.device)
+    def sinks(self, G, param, shape):
+        """([sink(g, ...) for the G groups], was every one of them a registered sink?)"""
+        got = [self._registered(g, param, shape, self.written) for g in range(G)]
+        sunk = all(d is not None for d in got)  # (`None not in got` would compare None with every tensor by ==: a torch dispatch each)
+        return got if sunk else [torch.empty(shape, dtype=param.dtype, device=param.device) if d is None else d for d in got], sunk
 
-
-#: data_ptr of a parameter -> its EXISTING gradient tensor: the weight-gradient kernels add into it (split-K reduce with
-#: accumulate) instead of writing a fresh tensor that a torch add then folds in.  autojac.mtl_backward_begin sets this for the
-#: task-side parameters that an earlier loss already reached (torchjd sums the per-loss gradients of those).
-GRAD_ACCUM = {}
-
-
-#: data_ptr of every parameter whose gradient a kernel accumulated in place during the current autograd call (filled by
-#: _accum_targets, cleared together with GRAD_ACCUM): autojac._accumulate checks what autograd hands back against it.
-GRAD_ACCUM_TAKEN = set()
-
-
-def _accum_targets(w, b, need_b):
-    """(dW destination in memory order, dbias destination) when BOTH of a layer's gradients can be accumulated in place."""
-    if not GRAD_ACCUM:
-        return None, None
-    gw = GRAD_ACCUM.get(w.data_ptr())
-    gb = GRAD_ACCUM.get(b.data_ptr()) if (b is not None and need_b) else None
-    if gw is None or (b is not None and need_b and gb is None):
-        return None, None
-    v = gw.permute(0, 2, 3, 1) if gw.dim() == 4 else gw
-    if not v.is_contiguous() or gw.shape != w.shape:
-        return None, None
-    GRAD_ACCUM.pop(w.data_ptr(), None)
-    GRAD_ACCUM_TAKEN.add(w.data_ptr())
-    if gb is not None:
-        GRAD_ACCUM.pop(b.data_ptr(), None)
-        GRAD_ACCUM_TAKEN.add(b.data_ptr())
-    return v, gb
-
-
-#: data_ptr of a FEATURE tensor (autojac.mtl_backward's `features`) -> destination for the gradient of the loss being differentiated
-#: w.r.t. that feature: slice i of a stacked [K, ...] buffer.  The op that produces the feature's cotangent (reparameterize, the KL
-#: term, ...) writes there, so the K cotangents of a feature are born stacked -- no torch.stack launch before the batched
-#: pull-back.  Consumed on first use; an op that does not know about it simply returns its own buffer (and the stack copies).
-COT_SINK = {}
-
-
-def _cot(feature_ptr, like):
-    """Destination for the gradient w.r.t. the tensor `like` (contiguous) whose memory the feature at `feature_ptr` views: the
-    registered sink slice, seen with `like`'s shape (the feature may be a permuted view of the same memory -- logical NCHW over
-    an NHWC buffer; the slice was allocated with the feature's strides, i.e. in that memory order), else a fresh buffer."""
-    dst = COT_SINK.pop(feature_ptr, None) if COT_SINK else None
-    if dst is not None and dst.numel() == like.numel() and dst.dtype == like.dtype and like.is_contiguous():
-        if dst.shape == like.shape and dst.is_contiguous():
+    def zeros(self, g, param, shape):
+        """An all-zero gradient: sinks are zero-initialised by their owner (autojac.JacobianBuffer) and written at most
+        once, so a registered sink is returned untouched -- no fill launch.  Without a sink the walker gets a new zero tensor; the
+        engine's parameter gets ONE persistent zero tensor for life, kept on the parameter itself (a bias in front of a
+        training-mode BatchNorm: its gradient is identically zero, so whatever is accumulated into this tensor later is zero as
+        well); nothing there launches a fill per step."""
+        dst = self._registered(g, param, shape, self.zeroed)
+        if dst is not None:
             return dst
-        if sorted(zip(dst.stride(), dst.shape), reverse=True) == sorted(zip(like.stride(), like.shape), reverse=True):  # same memory order
-            return dst.as_strided(like.shape, like.stride())
-    return torch.empty_like(like)
+        if not self.engine:
+            return torch.zeros(shape, dtype=param.dtype, device=param.device)
+        z = getattr(param, "_movae_zero_grad", None)
+        if z is None or z.numel() != param.numel() or z.dtype != param.dtype or z.device != param.device:
+            z = param._movae_zero_grad = torch.zeros(param.numel(), dtype=param.dtype, device=param.device)
+        return z.view(shape)
+
+    def accum_targets(self, w, b, need_b):
+        """(dW destination in memory order, dbias destination) when BOTH of a layer's gradients can be accumulated in place, the
+        engine's alone; else (None, None)."""
+        if not self.accum or not self.engine:
+            return None, None
+        gw = self.accum.get(w.data_ptr())
+        gb = self.accum.get(b.data_ptr()) if (b is not None and need_b) else None
+        if gw is None or (b is not None and need_b and gb is None):
+            return None, None
+        v = gw.permute(0, 2, 3, 1) if gw.dim() == 4 else gw
+        if not v.is_contiguous() or gw.shape != w.shape:
+            return None, None
+        for p in (w,) if gb is None else (w, b):
+            self.accum.pop(p.data_ptr(), None)
+            self.taken.add(p.data_ptr())
+        return v, gb
+
+    def cotangent(self, feature_ptr, like):
+        """Destination for the gradient w.r.t. the tensor `like` (contiguous) whose memory the feature at `feature_ptr` views: the
+        registered slice (consumed), seen with `like`'s shape (the feature may be a permuted view of the same memory -- logical NCHW
+        over an NHWC buffer; the slice was allocated with the feature's strides, i.e. in that memory order), else a fresh buffer."""
+        dst = self.cot.pop(feature_ptr, None) if self.cot else None
+        if dst is not None and dst.numel() == like.numel() and dst.dtype == like.dtype and like.is_contiguous():
+            if dst.shape == like.shape and dst.is_contiguous():
+                return dst
+            if sorted(zip(dst.stride(), dst.shape), reverse=True) == sorted(zip(like.stride(), like.shape), reverse=True):  # same memory order
+                return dst.as_strided(like.shape, like.stride())
+        return torch.empty_like(like)
 
 
-#: batched pull-back (autojac._batched_pullback): one sink dict per cotangent group, same keys as GRAD_SINK
-GRAD_SINK_ROWS = None
+#: the instance in scope (`with d:`), and what an op gets with none of its kind in scope: fresh buffers, the persistent zero, no
+#: accumulation, nothing recorded
+_INSTALLED = None
+_NONE = {True: Destinations(True), False: Destinations(False)}
 
 
-def _sink_row(g, param, shape, zeros=False):
-    """Destination of group g's gradient of `param` in a batched backward (J row of that group when registered)."""
-    rows = GRAD_SINK_ROWS
-    dst = _registered(rows[g] if rows else None, param, shape, SINK_ZERO_LOG if zeros else SINK_LOG)  # (zeros: handed out untouched)
-    return dst if dst is not None else (torch.zeros if zeros else torch.empty)(shape, dtype=param.dtype, device=param.device)
+def installed(engine):
+    """The Destinations in scope if it is of the asking kind, else the empty one of that kind: Function.backward asks for the
+    engine's, backward_batched for the walker's.  The walker calls `backward` once per group on a node without `backward_batched`;
+    that call must not see the walker's rows (it would write every group's gradient into row 0)."""
+    d = _INSTALLED
+    return d if d is not None and d.engine is engine else _NONE[engine]
 
 
 def _stacked(t, G):
@@ -118,40 +141,6 @@ def _stacked(t, G):
     if isinstance(t, (list, tuple)):
         return torch.stack([_c(x) for x in t])
     return _c(t)
-
-
-def _sink_zeros(g, param, shape):
-    """An all-zero gradient: sinks are zero-initialised by their owner (autojac.JacobianBuffer) and written at most
-    once, so a registered sink is returned untouched -- no fill launch.  Without a sink the parameter gets ONE persistent
-    zero tensor for life, kept on the parameter itself (a bias in front of a training-mode BatchNorm: its gradient is identically
-    zero, so whatever is accumulated into this tensor later is zero as well); nothing here launches a fill per step."""
-    dst = _registered(GRAD_SINK, param, shape, SINK_ZERO_LOG)
-    if dst is not None:
-        return dst
-    z = getattr(param, "_movae_zero_grad", None)
-    if z is None or z.numel() != param.numel() or z.dtype != param.dtype or z.device != param.device:
-        z = param._movae_zero_grad = torch.zeros(param.numel(), dtype=param.dtype, device=param.device)
-    return z.view(shape)
-
-
-class _Dest:
-    """Where a backward body (`_run`) puts group g's gradient of a parameter, and with it what only one of its two callers does.
-    Two instances, no subclasses: _ENGINE serves Function.backward (torch's engine: one cotangent, stacked as [1, ...]), _WALKER
-    serves backward_batched (autojac._batched_pullback: G cotangents, G = 1 included).
-      sink(g, param, shape)   the destination -- a registered sink (logged in SINK_LOG) or a fresh buffer
-      zeros(g, param, shape)  an identically zero gradient, handed out untouched (SINK_ZERO_LOG); the engine's form keeps ONE
-                              persistent zero tensor per parameter that has no sink
-      accum(w, b, need_b)     in-place accumulation targets (GRAD_ACCUM), the engine's alone; else (None, None)
-      engine                  the engine takes the entry points of one cotangent (movae_act_bwd, movae_bn_act_bwd) where the
-                              walker takes the grouped ones"""
-    __slots__ = ("sink", "zeros", "accum", "engine")
-
-    def __init__(self, sink, zeros, accum, engine):
-        self.sink, self.zeros, self.accum, self.engine = sink, zeros, accum, engine
-
-
-_ENGINE = _Dest(_sink, _sink_zeros, _accum_targets, True)
-_WALKER = _Dest(_sink_row, lambda g, p, shape: _sink_row(g, p, shape, zeros=True), lambda w, b, need_b: (None, None), False)
 
 
 def _first(t):
@@ -299,8 +288,8 @@ DEFER_REDUCE = _knob("DEFER_REDUCE")
 
 class deferred_reduces:
     """Inside this block a convolution's weight-gradient split-K reduce whose destinations are gradient SINKS (a Jacobian row, an
-    in-place accumulation target: autojac registers them, and reads them only through this library's aggregation / optimizer
-    entry points) is not launched on the spot: the library parks it and the next implicit-GEMM launch of the backward carries it
+    in-place accumulation target: autojac hands them over in a Destinations, and reads them only through this library's aggregation /
+    optimizer entry points) is not launched on the spot: the library parks it and the next implicit-GEMM launch of the backward carries it
     as extra blocks (include/movae.h: movae_reduce_defer).  The block's exit -- and every library call that
     is not one of the backward's own ops (_lib.DEFER_PASS) -- launches a reduce that is still parked; code that hands a weight
     gradient to anything else (torch arithmetic, a collective, a caller's aggregator) inside the block calls flush_deferred()
@@ -630,7 +619,7 @@ class Conv(Function):
         """The backward of the G stacked cotangents dy [G, n, ho, wo, co] -> (dx [G, ...], [dW per group], [dbias per group]).
         dgrad runs as ONE launch over G*n images -- the pull-back is linear and per-sample, and the deep layers' grids are far
         too small to fill the chip one cotangent at a time; wgrad is one grouped launch (each group reduces over its own
-        pixels, x is shared) writing straight into the groups' destinations (`dest`: _ENGINE / _WALKER)."""
+        pixels, x is shared) writing straight into the groups' destinations (`dest`: a Destinations)."""
         x, w, y, b, in_norm = Conv._saved(ctx)
         if ctx.res_out is not None:  # this conv's output is branch + block input: dy is the identity branch's cotangent too
             ctx.res_out.res = dy
@@ -673,10 +662,9 @@ class Conv(Function):
             wm_shape = (ci, kh, kw, co) if ctx.transposed else (co, kh, kw, ci)
             # a task-side parameter that an earlier loss already reached: add into its gradient inside the kernels' reduce
             plain_bias = need_b and db_done is None and not ctx.bias_grad_is_zero
-            acc_w, acc_b = dest.accum(w, b, plain_bias) if (db_done is None and not (ctx.has_bias and ctx.bias_grad_is_zero)) else (None, None)
+            acc_w, acc_b = dest.accum_targets(w, b, plain_bias) if (db_done is None and not (ctx.has_bias and ctx.bias_grad_is_zero)) else (None, None)
             acc = 1 if acc_w is not None else 0
-            nlog = len(SINK_LOG)
-            dwm = [acc_w.view(wm_shape)] if acc else [dest.sink(g, w, wm_shape) for g in range(G)]
+            dwm, sunk = ([acc_w.view(wm_shape)], True) if acc else dest.sinks(G, w, wm_shape)
             db_k = None
             if db_done is not None:
                 db = db_done  # already produced by the fused activation-backward pass
@@ -685,12 +673,13 @@ class Conv(Function):
                 # identically (the reference's value is rounding noise of order 1e-9); no column-sum pass
                 db = [dest.zeros(g, b, (co,)) for g in range(G)]
             elif need_b:
-                db = db_k = [acc_b] if acc else [dest.sink(g, b, (co,)) for g in range(G)]
+                db, sunk_b = ([acc_b], True) if acc else dest.sinks(G, b, (co,))
+                db_k, sunk = db, sunk and sunk_b
             dbp = arr(*[t.data_ptr() for t in db_k]) if db_k is not None else None
             # one grouped launch: blockIdx.z = group * splits + split, x is read by every group, dy by its own; with the
             # input gradient wanted too, dgrad and wgrad share the launch (igemm2_pair).  Every destination a sink (or an
             # in-place accumulation target): the split-K reduce may ride on a later launch (deferred_reduces)
-            armed = _defer_ws(dy, acc or len(SINK_LOG) - nlog == G * (1 + (db_k is not None)))
+            armed = _defer_ws(dy, sunk)
             if armed is not None:
                 wsp, wsb = armed
             tail = (n, hi, wi, ci, ho, wo, co, kh, kw, stride, pad, acc, wsp, wsb, st)
@@ -708,13 +697,13 @@ class Conv(Function):
     def backward(ctx, dy):
         if dy is None:
             return (None,) * 11
-        dx, dw, db = Conv._run(ctx, 1, _c(dy).unsqueeze(0), _ENGINE)
+        dx, dw, db = Conv._run(ctx, 1, _c(dy).unsqueeze(0), installed(True))
         return (_first(dx), _first(dw), _first(db)) + (None,) * 8
 
     @staticmethod
     def backward_batched(ctx, G, dy):
         """autojac._batched_pullback: dy is [G, n, ho, wo, co] (or a list of G tensors)."""
-        return Conv._run(ctx, G, _stacked(dy, G), _WALKER) + (None,) * 8
+        return Conv._run(ctx, G, _stacked(dy, G), installed(False)) + (None,) * 8
 
 
 def _fuse_bias_grad(ctx, dy, y, co):
@@ -778,7 +767,7 @@ class LinearPair(Function):
 
     @staticmethod
     def _run(ctx, G, dy1, dy2, dest):
-        """dy_i: [G, m, n] stacked (or None: that output had no cotangent).  dest: _ENGINE / _WALKER."""
+        """dy_i: [G, m, n] stacked (or None: that output had no cotangent).  dest: a Destinations."""
         x, w1, b1, w2, b2 = ctx.saved_tensors
         m, k = x.shape
         n = w1.shape[0]
@@ -806,14 +795,14 @@ class LinearPair(Function):
         if dy1 is None and dy2 is None:
             return None, None, None, None, None
         one = lambda t: _c(t).unsqueeze(0) if t is not None else None  # noqa: E731
-        return tuple(_first(t) for t in LinearPair._run(ctx, 1, one(dy1), one(dy2), _ENGINE))
+        return tuple(_first(t) for t in LinearPair._run(ctx, 1, one(dy1), one(dy2), installed(True)))
 
     @staticmethod
     def backward_batched(ctx, G, dy1, dy2):
         if dy1 is None and dy2 is None:
             return None, None, None, None, None
         st = lambda t: _stacked(t, G) if t is not None else None  # noqa: E731
-        return LinearPair._run(ctx, G, st(dy1), st(dy2), _WALKER)
+        return LinearPair._run(ctx, G, st(dy1), st(dy2), installed(False))
 
 
 def linear_pair(x, w1, b1, w2, b2):
@@ -857,11 +846,11 @@ class BatchNormAct(Function):
     def backward(ctx, dout):
         if dout is None:
             return (None,) * 11
-        return tuple(t[0] for t in BatchNormAct._run(ctx, 1, _c(dout).unsqueeze(0), _ENGINE)) + (None,) * 8
+        return tuple(t[0] for t in BatchNormAct._run(ctx, 1, _c(dout).unsqueeze(0), installed(True))) + (None,) * 8
 
     @staticmethod
     def backward_batched(ctx, G, dout):
-        return BatchNormAct._run(ctx, G, _stacked(dout, G), _WALKER) + (None,) * 8
+        return BatchNormAct._run(ctx, G, _stacked(dout, G), installed(False)) + (None,) * 8
 
 
 def _bn_act_bwd(dest, G, dout, saved, dgs, dbs, act, slope):
@@ -989,11 +978,11 @@ class BatchNormLazy(Function):
     def backward(ctx, dout, _ds, _dh):
         if dout is None:
             return (None,) * 12
-        return tuple(t[0] for t in BatchNormLazy._run(ctx, 1, _c(dout).unsqueeze(0), _ENGINE)) + (None,) * 9
+        return tuple(t[0] for t in BatchNormLazy._run(ctx, 1, _c(dout).unsqueeze(0), installed(True))) + (None,) * 9
 
     @staticmethod
     def backward_batched(ctx, G, dout, _ds=None, _dh=None):
-        return BatchNormLazy._run(ctx, G, _stacked(dout, G), _WALKER) + (None,) * 9
+        return BatchNormLazy._run(ctx, G, _stacked(dout, G), installed(False)) + (None,) * 9
 
 
 def batch_norm_lazy(y, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, act, slope, fusion):
@@ -1057,11 +1046,11 @@ class Activation(Function):
     def backward(ctx, dy):
         if dy is None:
             return (None,) * 5
-        return (Activation._run(ctx, 1, _c(dy).unsqueeze(0), _ENGINE)[0],) + (None,) * 4
+        return (Activation._run(ctx, 1, _c(dy).unsqueeze(0), installed(True))[0],) + (None,) * 4
 
     @staticmethod
     def backward_batched(ctx, G, dy):
-        return (Activation._run(ctx, G, _stacked(dy, G), _WALKER),) + (None,) * 4
+        return (Activation._run(ctx, G, _stacked(dy, G), installed(False)),) + (None,) * 4
 
 
 def activation(x, act, slope=0.01, act_out=None, res_in=None):
@@ -1189,7 +1178,7 @@ class Reparameterize(Function):
             return (None,) * 3
         log_var, eps = ctx.saved_tensors
         dz = _c(dz)
-        dmu, dlv = _cot(ctx.in_ptrs[0], dz), _cot(ctx.in_ptrs[1], dz)
+        dmu, dlv = installed(True).cotangent(ctx.in_ptrs[0], dz), installed(True).cotangent(ctx.in_ptrs[1], dz)
         _call("movae_reparam_bwd", dz.data_ptr(), log_var.data_ptr(), eps.data_ptr(), dmu.data_ptr(), dlv.data_ptr(), dz.numel(), _st(dz))
         return dmu, dlv, None
 
@@ -1221,7 +1210,7 @@ class ReparameterizeRNG(Function):
             return (None,) * 3
         log_var, eps = ctx.saved_tensors
         dz = _c(dz)
-        dmu, dlv = _cot(ctx.in_ptrs[0], dz), _cot(ctx.in_ptrs[1], dz)
+        dmu, dlv = installed(True).cotangent(ctx.in_ptrs[0], dz), installed(True).cotangent(ctx.in_ptrs[1], dz)
         _call("movae_reparam_bwd", dz.data_ptr(), log_var.data_ptr(), eps.data_ptr(), dmu.data_ptr(), dlv.data_ptr(), dz.numel(), _st(dz))
         return dmu, dlv, None
 
@@ -1257,7 +1246,7 @@ class ReparameterizePriorRNG(Function):
             return (None,) * 4
         log_var, eps = ctx.saved_tensors
         dz = _c(dz)
-        dmu, dlv = _cot(ctx.in_ptrs[0], dz), _cot(ctx.in_ptrs[1], dz)
+        dmu, dlv = installed(True).cotangent(ctx.in_ptrs[0], dz), installed(True).cotangent(ctx.in_ptrs[1], dz)
         _call("movae_reparam_bwd", dz.data_ptr(), log_var.data_ptr(), eps.data_ptr(), dmu.data_ptr(), dlv.data_ptr(), dz.numel(), _st(dz))
         return dmu, dlv, None, None
 
@@ -1414,7 +1403,7 @@ class KLDivergence(Function):
         mu, log_var = ctx.saved_tensors
         g = _c(g)
         b, d = mu.shape
-        dmu, dlv = _cot(mu.data_ptr(), mu), _cot(log_var.data_ptr(), mu)
+        dmu, dlv = installed(True).cotangent(mu.data_ptr(), mu), installed(True).cotangent(log_var.data_ptr(), mu)
         _call("movae_kl_bwd", mu.data_ptr(), log_var.data_ptr(), g.data_ptr(), dmu.data_ptr(), dlv.data_ptr(), b, d,
               float(ctx.scale), _st(mu))
         return dmu, dlv, None
@@ -1468,7 +1457,7 @@ class VAELosses(Function):
         if gk is not None and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
             gk = _c(gk)
             b, d = mu.shape
-            dmu, dlv = _cot(mu.data_ptr(), mu), _cot(log_var.data_ptr(), mu)
+            dmu, dlv = installed(True).cotangent(mu.data_ptr(), mu), installed(True).cotangent(log_var.data_ptr(), mu)
             _call("movae_kl_bwd", mu.data_ptr(), log_var.data_ptr(), gk.data_ptr(), dmu.data_ptr(), dlv.data_ptr(), b, d,
                   float(ctx.scale_k), _st(mu))
         return dr, None, None, None, dmu, dlv, None, None
@@ -1524,9 +1513,9 @@ class RecursiveLosses(Function):
         if reach(g_rec) and ctx.needs_input_grad[0]:
             dr = torch.empty_like(recons)
         if has_kl and reach(g_kl) and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
-            dmh, dlh = _cot(mu_hat.data_ptr(), mu_hat), _cot(log_var_hat.data_ptr(), mu_hat)
+            dmh, dlh = installed(True).cotangent(mu_hat.data_ptr(), mu_hat), installed(True).cotangent(log_var_hat.data_ptr(), mu_hat)
         if has_cyc and reach(g_cyc) and ctx.needs_input_grad[9]:
-            dmg = _cot(mu_gen.data_ptr(), mu_gen)
+            dmg = installed(True).cotangent(mu_gen.data_ptr(), mu_gen)
         if dr is None and dmh is None and dmg is None:
             return (None,) * 11
         p = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
@@ -1879,7 +1868,7 @@ class VectorQuantize(Function):
         # a cotangent that reaches neither the straight-through output nor the commitment term (the embedding loss alone) has NO
         # gradient w.r.t. x: None, not a tensor of zeros -- mtl_backward then skips that loss's pull-back through the encoder
         # (a zero Jacobian row costs nothing); likewise no codebook gradient without an embedding-loss cotangent
-        dx = _cot(ctx.x_ptr, x) if (need_x and (dq is not None or gc is not None)) else None  # (x is a feature: born stacked)
+        dx = installed(True).cotangent(ctx.x_ptr, x) if (need_x and (dq is not None or gc is not None)) else None  # (x is a feature: born stacked)
         de = torch.empty((k, d), dtype=x.dtype, device=x.device) if (need_e and ge is not None) else None
         if dx is None and de is None:
             return None, None
@@ -2236,8 +2225,8 @@ class RowNorm(Function):
         rows = x.numel() // d
         need = ctx.needs_input_grad
         dx = torch.empty_like(x) if need[0] else None
-        dw = _sink(0, weight, (d,)) if weight is not None and need[1] else None
-        db = _sink(0, bias, (d,)) if bias is not None and need[2] else None
+        dw = installed(True).sink(0, weight, (d,)) if weight is not None and need[1] else None
+        db = installed(True).sink(0, bias, (d,)) if bias is not None and need[2] else None
         if dx is None and dw is None and db is None:
             return (None,) * 6
         ws = _ws_at_least(x.device, L.load().movae_rownorm_ws_bytes(rows, d))
@@ -2284,7 +2273,7 @@ class BiasGelu(Function):
         _call("movae_bias_gelu_bwd", dy.data_ptr(), x.data_ptr(), _p(bias), dx.data_ptr(), rows, c, _st(x))
         db = None
         if bias is not None and ctx.needs_input_grad[1]:
-            db = _sink(0, bias, (c,))
+            db = installed(True).sink(0, bias, (c,))
             wsp, wsb = _ws(x)
             _call("movae_colsum", dx.data_ptr(), db.data_ptr(), rows, c, 0, wsp, wsb, _st(x))
         return (dx if ctx.needs_input_grad[0] else None), db

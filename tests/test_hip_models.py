@@ -232,7 +232,7 @@ def test_batched_pullback_residual_graph_and_native_nodes(gpu_device, monkeypatc
 
 def test_shared_task_side_weight_is_not_double_counted(gpu_device):
     """A task-side conv applied twice (weight sharing) under two losses: the second loss's weight gradient is added in place by the
-    FIRST of the two nodes (ops.GRAD_ACCUM) and autograd sums both nodes' results into a new tensor -- adding that to .grad would
+    FIRST of the two nodes (ops.Destinations.accum) and autograd sums both nodes' results into a new tensor -- adding that to .grad would
     count the first loss's gradient twice.  Either the result is exact or the step refuses loudly; never a silent double count."""
     import movae_amd  # noqa: F401
     from movae_amd import aggregation, autojac, nn as mnn
