@@ -376,9 +376,9 @@ def run_dgrad(L, lib, dev, g, dy, w, expect, groups=1, ws=None, fuse=None, off="
 
 def run_wgrad(L, lib, dev, g, dy, x, expect, groups=1, nrm=None, init=None, bias=True, ws=None, off=""):
     """-> ([dW per group], [dbias per group] or None); init = ([dW0 per group], [db0 per group]): accumulate into them.
-    off: "x" puts x one float past a 16-byte boundary."""
+    off: "x" puts x one float past a 16-byte boundary, "d" every dW."""
     dyd, xd = dy.to(dev), put(x, dev, "x" in off)
-    dws = [Out(g.wshape, dev, None if init is None else init[0][i]) for i in range(groups)]
+    dws = [Out(g.wshape, dev, None if init is None else init[0][i], off=1 if "d" in off else 0) for i in range(groups)]
     dbs = [Out((g.co,), dev, None if init is None else init[1][i]) for i in range(groups)] if bias else None
     arr = C.c_void_p * groups
     dwp = arr(*[o.ptr() for o in dws])
